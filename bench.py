@@ -14,6 +14,10 @@ the steady state and primes every launch pattern); then W warm-up and K timed it
 The timed region records the samples and the statistics of every iteration (MALA.cpp:706-716) and copies them back.
 
 The spectrum is resident in HBM before the timed region; the iteration itself runs on the device (no per-step host traffic).
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, --dump-outputs, the result line.  --full adds the
+STRICT end-to-end check of the final states and, at N=1, the extra legs (red giant, MALA-FD, learning phase, packed stars), the other
+launch shapes and the cpu_baseline leg.
 """
 import argparse
 import json
@@ -54,6 +58,13 @@ def parse():
                     help="device = whole MCMC iteration resident on the GPU; host = host-driven loop (one device call per step)")
     ap.add_argument("--bins-per-thread", type=int, default=0, choices=[0, 1, 2, 4, 8, 16], help="tile = workgroup*K bins (0 = library default)")
     ap.add_argument("--workgroup", type=int, default=0, choices=[0, 64, 256], help="workgroup size of the likelihood kernel (0 = library default)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the STRICT end-to-end check of the final states and, at N=1, the extra legs (red giant, MALA-FD, "
+                         "learning phase, packed stars), the other launch shapes and the cpu_baseline leg.  Without it a run only sets up, warms up, "
+                         "times the K steps, writes --dump-outputs and prints the result line; the options of the extra legs below apply with --full only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, save what the last timed step returned to its caller as DIR/samples.npy [Nchains x Nvars] and "
+                         "DIR/stats.npy [Nchains x 3: tempered logL, logPrior, logPosterior], float64 (rank 0)")
     ap.add_argument("--mala-steps", type=int, default=60, help="extra MALA-FD measurement (0 = skip)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the cpu_baseline leg (rank 0, N=1 only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -67,8 +78,8 @@ def parse():
                     help="extra leg at N=1: the same star in the LEARNING phase -- the proposal law adapted after every test (MALA.cpp:656-667, "
                          "config_default.cfg:17-18), this many timed iterations (0 = skip); reported under 'learning', never as 'value'")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the timed headline run (no packed / red-giant / MALA / launch-shape / CPU legs): the command profiled under "
-                         "rocprofv3 for profiles/, so that the per-kernel averages are those of the headline launches")
+                    help="no packed / red-giant / MALA / launch-shape / CPU legs, even with --full (which then adds only the end-to-end check): "
+                         "the command profiled under rocprofv3 for profiles/, so that the per-kernel averages are those of the headline launches")
     ap.add_argument("--dn-mixing", type=int, default=1, help="parallel-tempering swap attempt every N iterations (reference default 1, config_default.cfg:28)")
     ap.add_argument("--step-scheme", type=int, default=0, choices=[0, 1, 2, 3],
                     help="device engine: 0 = fused launches (one or two per iteration: automatic), 1 = lockstep kernels only, 2 = fused, one launch per iteration, "
@@ -77,7 +88,7 @@ def parse():
     a = ap.parse_args()
     a.steps = max(a.steps, 1)
     a.warmup = max(a.warmup, 0)
-    if a.headline_only:
+    if a.headline_only or not a.full:
         a.mala_steps, a.packed_stars, a.rgb_steps, a.learn_steps, a.no_cpu_baseline = 0, 0, 0, 0, True
     return a
 
@@ -201,21 +212,27 @@ def main():
     value = shard.aggregate_rate(a.steps, world, elapsed)
     mark("TIMED REGION (the K steps behind `value`), fences included")
 
-    # ---- end-to-end check of what the timed region left behind: the chains' tempered logL recomputed with STRICT arithmetic from the
-    # final positions (the recorded last sample), and the recorded statistics against the state
     samples, stats = rec
     if a.dump_samples:
         np.save(f"{a.dump_samples}_rank{rank}.npy", np.array(samples))
-    Pfin = np.tile(star.params, (a.chains, 1))
-    Pfin[:, star.index_to_relax] = st["vars"]
-    ctx.set_option(pkg.OPT_PRECISION, pkg.PRECISION_STRICT)
-    strict_logL, _, strict_status = ctx.loglike_params_batch(star.model_id, Pfin, star.plength, T)
-    ctx.set_option(pkg.OPT_PRECISION, prec)
-    end_err = float(np.max(np.abs(strict_logL - st["logL"]) / np.abs(strict_logL)))
-    assert (strict_status == 0).all() and end_err <= 1e-11, f"end-to-end check failed: {end_err}"
-    assert np.array_equal(samples[-1], st["vars"]) and np.array_equal(stats[-1][:, 0], st["logL"]), "recorded samples do not match the final state"
+    if a.dump_outputs and rank == 0:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "samples.npy"), np.array(samples[-1], dtype=np.float64))
+        np.save(os.path.join(a.dump_outputs, "stats.npy"), np.array(stats[-1], dtype=np.float64))
     moved = np.mean(np.any(samples[1:] != samples[:-1], axis=2), axis=0) if a.steps > 1 else np.zeros(a.chains)
-    mark("end-to-end check (STRICT re-evaluation of the final states)")
+
+    if a.full:
+        # ---- end-to-end check of what the timed region left behind: the chains' tempered logL recomputed with STRICT arithmetic from the
+        # final positions (the recorded last sample), and the recorded statistics against the state
+        Pfin = np.tile(star.params, (a.chains, 1))
+        Pfin[:, star.index_to_relax] = st["vars"]
+        ctx.set_option(pkg.OPT_PRECISION, pkg.PRECISION_STRICT)
+        strict_logL, _, strict_status = ctx.loglike_params_batch(star.model_id, Pfin, star.plength, T)
+        ctx.set_option(pkg.OPT_PRECISION, prec)
+        end_err = float(np.max(np.abs(strict_logL - st["logL"]) / np.abs(strict_logL)))
+        assert (strict_status == 0).all() and end_err <= 1e-11, f"end-to-end check failed: {end_err}"
+        assert np.array_equal(samples[-1], st["vars"]) and np.array_equal(stats[-1][:, 0], st["logL"]), "recorded samples do not match the final state"
+        mark("end-to-end check (STRICT re-evaluation of the final states)")
 
     extra = {}
     # (the red-giant leg runs first among the extra legs: measured right after another leg has released its device memory -- the Langevin
@@ -355,7 +372,7 @@ def main():
         mark("extra leg: packed (set-up of the co-resident stars + their learning phase + timed steps)")
 
     shapes = []
-    if world == 1 and a.sampler == "mh" and not a.headline_only:
+    if a.full and world == 1 and a.sampler == "mh" and not a.headline_only:
         # the likelihood kernel on its own at other launch sizes (standalone batched calls through the C ABI, live HIP-event timing)
         rng = np.random.default_rng(3)
         for Bs, reps in ((a.chains, 20), (10 * a.chains, 5)):
@@ -434,10 +451,11 @@ def main():
             "accept_rate_chain0": (st["accepted0"] - acc0["accepted0"]) / max(a.steps + a.warmup, 1),   # (warm-up + timed iterations)
             "position_change_rate_mean": float(moved.mean()),
             "swap_rate": (st["swaps"] - acc0["swaps"]) / max(st["swap_attempts"] - acc0["swap_attempts"], 1),
-            "end_to_end_check": {"max_rel_err_logL_final_states_vs_STRICT": end_err, "tolerance": 1e-11,
-                                 "recorded_last_sample_equals_state": True},
             "kernel_time_fraction": k_ms * 1e-3 / elapsed,   # (> 1 with two launches in flight)
         }
+        if a.full:
+            out["end_to_end_check"] = {"max_rel_err_logL_final_states_vs_STRICT": end_err, "tolerance": 1e-11,
+                                       "recorded_last_sample_equals_state": True}
         out.update(extra)
         mark("other launch shapes, mode table for the report")
         if world == 1 and not a.no_cpu_baseline:

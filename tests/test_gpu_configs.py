@@ -204,8 +204,9 @@ def test_two_ranks_run_the_bench_path_and_match_solo_runs(pkg, synth, tmp_path):
 @pytest.mark.parametrize("steps,warm", [(20, 5), (7, 0), (100, 3)])
 def test_the_drivers_bench_command_prints_its_line(steps, warm):
     """`python bench.py --gpus 1 --steps 20 --warmup 5` is what the driver records; short windows must still carry a live measurement of
-    the dominant kernel (a window whose middle iteration is a joint launch of both chain groups once left none: round 3)."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warm), "--headline-only"]
+    the dominant kernel (a window whose middle iteration is a joint launch of both chain groups once left none: round 3).  --full for the
+    end-to-end check, --headline-only to leave out the extra legs."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warm), "--full", "--headline-only"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -214,3 +215,30 @@ def test_the_drivers_bench_command_prints_its_line(steps, warm):
     assert k["us_per_launch"] > 1.0 and 0 < k["frac"] < 1 and 0 < d["roofline"]["frac"] < 1
     assert d["value"] == pytest.approx(steps / (d["ms_per_step"] * 1e-3 * steps))
     assert d["end_to_end_check"]["max_rel_err_logL_final_states_vs_STRICT"] <= 1e-11
+
+
+def test_plain_bench_run_dumps_what_its_last_timed_step_returned(pkg, synth, tmp_path):
+    """`bench.py --dump-outputs DIR` without --full: the result line carries the headline alone (no extra leg, no end-to-end check), and
+    DIR holds the last timed step's samples and statistics -- those a solo run of the same star, seed and phases returns."""
+    steps, warm = 7, 3
+    out = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warm), "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["steps"] == steps and d["warmup"] == warm and d["unit"] == "samples/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["value"] == pytest.approx(steps / (d["ms_per_step"] * 1e-3 * steps))
+    assert not {"end_to_end_check", "cpu_baseline", "c5_rgb", "mala_fd", "learning", "packed"} & set(d)
+    assert d["roofline"]["other_launch_shapes"] == []
+    got_smp, got_st = np.load(out / "samples.npy"), np.load(out / "stats.npy")
+    assert got_smp.dtype == np.float64 and got_st.dtype == np.float64
+    sys.path.insert(0, ROOT)
+    import bench
+    star, ctx = _c3_with_spectrum(pkg, synth, 0)
+    s = pkg.Sampler(ctx, star, nchains=20, lambda_temp=1.3, seed=7, engine="device", Nt_learn=bench.SETUP_LEARN, periods_learn=(1,),
+                    dN_mixing=1, c0=2.0)
+    s.run(bench.SETUP_ITERS, record=False)
+    s.run(warm, stats=True)
+    ref_smp, ref_st = s.run(steps, stats=True)
+    s.close(); ctx.close()
+    assert np.array_equal(got_smp, ref_smp[-1]) and np.array_equal(got_st, ref_st[-1])

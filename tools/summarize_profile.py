@@ -34,7 +34,7 @@ if ks:
 try:
     b = json.loads(open(f"{src}/bench.json").read())
     kb = b.get("roofline", {}).get("kernel", {})
-    lines += ["## `python3 bench.py` line of the same build (un-profiled default run, all legs)", "", "```json", json.dumps(b, indent=1), "```", ""]
+    lines += ["## `python3 bench.py --full` line of the same build (un-profiled run, all legs)", "", "```json", json.dumps(b, indent=1), "```", ""]
 except Exception as e:
     lines += [f"(no bench.json: {e})", ""]
 agg = collections.defaultdict(list)
