@@ -1,13 +1,16 @@
 // fit_star.cpp -- a complete fit of one star driven from C++ through the C ABI only (include/tamcmc_*.h), the way a host that
 // keeps the reference's Config / .model / .data surface would use the library: no Python, no torch.
 //
-//   fit_star <local|global|asymptotic> <star.model> <star.data> <sampler.cfg> <errors.cfg> <output root> [slice index]
+//   fit_star <local|global|asymptotic|simple> <star.model> <star.data> <sampler.cfg> <errors.cfg> <output root> [slice index]
+//
+//   simple: the Gaussian-envelope fits (model ids 0, 1) -- their `.model` does not name its model, the .cfg's !Modeling model_fct_name does
 //
 //   .data + .model  -> spectrum cut to the model's range, parameter vector, prior table      (tamcmc_io_*,   config.cpp:167-396)
 //   sampler.cfg     -> !MALA / !Modeling / !Outputs settings                                 (tamcmc_cfg_*,  config.cpp:1223-1732)
 //   errors.cfg      -> initial proposal scales                                               (config.cpp:2096-2150)
 //   run             -> learning phases + Nsamples recorded iterations on the device-resident engine (host-driven engine for the
-//                      red-giant models, whose mixed-mode solver runs as a device pre-step), MALA::execute MALA.cpp:623-745
+//                      red-giant models, whose mixed-mode solver runs as a device pre-step, and for the Gaussian-envelope fits),
+//                      MALA::execute MALA.cpp:623-745
 //   outputs         -> <root>params.hdr/.bin per chain, stat_criteria, restore files, evidence line, summary table
 //                      (outputs.cpp:863-1025, :1231-1333, :1472-1550; diagnostics.cpp:980-1066; bin2txt_params.cpp:165-168)
 #include <cstdio>
@@ -37,7 +40,7 @@ static const char *err() {
 
 int main(int argc, char **argv) {
     if (argc < 7) {
-        std::fprintf(stderr, "usage: %s <local|global|asymptotic> <star.model> <star.data> <sampler.cfg> <errors.cfg> <output root> [slice]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <local|global|asymptotic|simple> <star.model> <star.data> <sampler.cfg> <errors.cfg> <output root> [slice]\n", argv[0]);
         return 2;
     }
     const std::string dialect = argv[1], root = argv[6];
@@ -52,6 +55,17 @@ int main(int argc, char **argv) {
     if (dialect == "local") CHECK(tamcmc_io_load_model_local(argv[2], slice, resol, &in), "load_model_local");
     else if (dialect == "global") CHECK(tamcmc_io_load_model_global(argv[2], resol, &in), "load_model_global");
     else if (dialect == "asymptotic") CHECK(tamcmc_io_load_model_asymptotic(argv[2], resol, &in), "load_model_asymptotic");
+    else if (dialect == "simple") {
+        tamcmc_cfg *mc = nullptr;
+        char fct[256] = {0};
+        CHECK(tamcmc_cfg_open(argv[4], &mc), "cfg_open");
+        const int rc = tamcmc_cfg_string(mc, "Modeling", "model_fct_name", fct, (int)sizeof fct);
+        tamcmc_cfg_free(mc);
+        CHECK(rc, "cfg_string (!Modeling model_fct_name)");
+        const int id = tamcmc_model_id_from_name(fct);
+        if (id < 0) { std::fprintf(stderr, "fit_star: model_fct_name '%s' is not in models_ctrl.list\n", fct); return 1; }
+        CHECK(tamcmc_io_load_model_simple(argv[2], id, &in), "load_model_simple");
+    }
     else { std::fprintf(stderr, "fit_star: unknown dialect %s\n", dialect.c_str()); return 2; }
     const int Np = tamcmc_inputs_nparams(in);
     std::vector<double> params((size_t)Np), priors((size_t)4 * Np);
@@ -65,6 +79,10 @@ int main(int argc, char **argv) {
     std::vector<double> x((size_t)Nx), y((size_t)Nx);
     for (int64_t i = 0; i < Nx; i++) { x[(size_t)i] = tab[(i0 + i) * nc]; y[(size_t)i] = tab[(i0 + i) * nc + 1]; }
     tamcmc_io_free(tab);
+    // the plength the output header records: the fixed [11] form, or the simple dialect's own (count of each distinct name)
+    const int n_pl = tamcmc_inputs_plength(in, nullptr, 0);
+    std::vector<int32_t> pl_out((size_t)(n_pl > 0 ? n_pl : 1));
+    tamcmc_inputs_plength(in, pl_out.data(), n_pl);
     std::vector<const char *> names((size_t)Np), vnames;
     std::vector<double> vvals;
     for (int i = 0; i < Np; i++) {
@@ -90,7 +108,8 @@ int main(int argc, char **argv) {
     sc.init_errors = errs.data();
     sc.seed = 20240229;
     const bool red_giant = (model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4 || model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4);
-    sc.engine = (sc.use_drift || red_giant) ? 0 : 1;
+    const bool envelope = (model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN || model_id == TAMCMC_MODEL_HARVEY_GAUSSIAN);
+    sc.engine = (sc.use_drift || red_giant || envelope) ? 0 : 1;
     // ---- device
     CHECK(tamcmc_hip_create(&g_ctx, 0), "hip_create (the product path has no CPU fallback)");
     CHECK(tamcmc_hip_set_option(g_ctx, TAMCMC_OPT_PRECISION, TAMCMC_PRECISION_FAST), "set_option");
@@ -106,7 +125,7 @@ int main(int argc, char **argv) {
     for (int64_t done = 0; done < Nsamples; done += chunk) {
         const int64_t n = Nsamples - done < chunk ? Nsamples - done : chunk;
         CHECK(tamcmc_sampler_run(s, n, smp.data(), st.data()), "sampler_run");
-        CHECK(tamcmc_outputs_write_params(root.c_str(), smp.data(), n, C, (int32_t)Nv, Nsamples, relax.data(), plength, 11, Np, params.data(), names.data(),
+        CHECK(tamcmc_outputs_write_params(root.c_str(), smp.data(), n, C, (int32_t)Nv, Nsamples, relax.data(), pl_out.data(), n_pl, Np, params.data(), names.data(),
                                           done > 0), "write_params");
         CHECK(tamcmc_outputs_write_stat_criteria(root.c_str(), st.data(), n, C, done > 0), "write_stat_criteria");
         all_stats.insert(all_stats.end(), st.begin(), st.begin() + (size_t)(n * C * 3));

@@ -38,6 +38,20 @@ extern "C" {
 #define TAMCMC_ERR_NO_DEVICE (-7)    /* no HIP device: the product path has NO CPU fallback */
 
 /* ---------------- model ids (Config/default/models_ctrl.list) ---------------- */
+/* Gaussian-envelope background fits (ids 0, 1): the first fit of a star, over the whole spectrum -- background + Gaussian envelope of the
+ * modes, no mode table.  Only through tamcmc_hip_loglike_params_batch and the tamcmc_hip_fd_gradient* entry points (plength is not read
+ * and may be NULL); tamcmc_build_mode_table returns TAMCMC_ERR_BAD_MODEL.  Kernels: csrc/envelope.hip.
+ *   id 0 params: [k_Agran, s_Agran, k_taugran, s_taugran, c_gran, a1, a2, k1, s1, c1, k2, s2, c2, N0, Amax, numax, sigma, mu_numax,
+ *                 omega_numax] (19; omega_numax is read by the prior only)
+ *   id 1 params: [H1, tc1, p1, H2, tc2, p2, B0, Amax, numax, Gauss_sigma] (10)
+ * Known deviation from Kallinger et al. (2014), kept from the reference: the sinc^2 leakage filter eta^2 multiplies the Gaussian only.
+ * The reference's `Power.cwiseProduct(eta_squared);` (noise_models.cpp:150) discards its result, so the noise terms are not filtered.
+ * One arithmetic mode for both (TAMCMC_OPT_PRECISION does not apply): double per bin, power laws as exp(c (ln x - ln b)) on the resident
+ * ln x, the three normalisation integrals of id 0 as fixed-order tree sums.  Stated tolerance against a long-double restatement of the
+ * reference: |dM|/M <= 1e-12 per bin, |dlogL|/|logL| <= 1e-12 (tests/test_gpu_envelope.py).  A vector's logL is bit-identical in any
+ * batch at any position. */
+#define TAMCMC_MODEL_KALLINGER2014_GAUSSIAN 0 /* model_Kallinger2014_Gaussian, models.cpp (after model_Harvey_Gaussian); prior class 0 */
+#define TAMCMC_MODEL_HARVEY_GAUSSIAN 1        /* model_Harvey_Gaussian, models.cpp:5674; prior class 1 */
 #define TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC 3 /* model_MS_Global_a1etaa3_HarveyLike_Classic, models.cpp:1943 */
 #define TAMCMC_MODEL_MS_LOCAL_BASIC 11           /* model_MS_local_basic, models.cpp:3012 */
 #define TAMCMC_MODEL_MS_GLOBAL_AJ 23             /* model_MS_Global_aj_HarveyLike, models.cpp:1195 */
@@ -117,7 +131,7 @@ int tamcmc_hip_loglike_batch(tamcmc_hip_ctx *ctx, int B, const tamcmc_multiplet 
                              const double *noise, int noise_stride, const int32_t *nharvey, const int32_t *nnoise,
                              const double *Tcoefs, double p, double *logL, double *model);
 
-/* Table builders: the host-side scalar part of the model functions
+/* Table builders (Lorentzian models only; ids 0 and 1 have no multiplets: TAMCMC_ERR_BAD_MODEL): the host-side scalar part of the model functions
  *   VectorXd model_X(params, params_length, x, outparams)   tamcmc/headers/models.h:21-57
  * (parameter unpack, amplitude_ratio, lin_interpol, eta0, set_imin_imax) for ids 3, 11, 23.
  * Writes at most max_mults rows; *n_mults = rows needed.  noise_abs receives |noise params| (plength[8] values). */
@@ -127,7 +141,8 @@ int tamcmc_build_mode_table(int model_id, const double *params, const int32_t *p
 
 /* model id + params level: table build on the host for each of the B vectors, then one batched device call.
  * This is the batched body of Model_def::generate_model without the prior (model_def.cpp:473-474).
- * status (may be NULL) receives the per-vector table status; vectors with a failed table get logL = NaN. */
+ * status (may be NULL) receives the per-vector table status; vectors with a failed table get logL = NaN.
+ * Ids 0 and 1 are dispatched first, before plength is read: see the model ids above (at most 65535 vectors per call). */
 int tamcmc_hip_loglike_params_batch(tamcmc_hip_ctx *ctx, int model_id, int B, const double *params, int64_t Nparams,
                                     const int32_t *plength, const double *Tcoefs, double p, double *logL,
                                     double *model, int32_t *status);
@@ -157,13 +172,17 @@ int tamcmc_hip_rgb_mixed_modes(tamcmc_hip_ctx *ctx, int model_id, const double *
  * base point -- per bin as the series in u = dM/M0 (five terms, closed form beyond |u| = 0.01), and on tiles where every changed
  * multiplet is in the far field from moments of the base point (first and second order in u; used where max|u| <= 1e-5, what is
  * omitted is below 1e-10 of the leading term).  Against the brute-force difference of two full evaluations it agrees to that
- * difference's own cancellation noise (~5e-15 Nx / h) + 1e-6 of the gradient's scale (tests/test_gpu_parity.py). */
+ * difference's own cancellation noise (~5e-15 Nx / h) + 1e-6 of the gradient's scale (tests/test_gpu_parity.py).
+ * Ids 0 and 1: every parameter moves every bin, so the batch is brute force -- C x (Nvars+1) full evaluations in one batched launch
+ * (C x (Nvars+1) <= 65535), grad = (logL(theta + h e_k) - logL(theta)) / h_applied; plength is not read. */
 int tamcmc_hip_fd_gradient(tamcmc_hip_ctx *ctx, int model_id, int C, const double *params, int64_t Nparams,
                            const int32_t *plength, const int32_t *index_to_relax, int Nvars, const double *hstep,
                            const double *Tcoefs, double p, double *logL0, double *grad);
 
 /* Same batch, gradient of the tempered log-POSTERIOR: each of the C*(Nvars+1) workgroups also evaluates the log-prior of
- * its perturbed vector on the device (prior_class 2 = io_MS_Global, 3 = io_local; priors = 4 x Nparams row-major table,
+ * its perturbed vector on the device (prior_class 2 = io_MS_Global, 3 = io_local, 0 = priors_Kallinger2014_Gaussian with model id 0,
+ * 1 = priors_Harvey_Gaussian with model id 1 -- these two on the device in double, one thread per point, extra_priors not read;
+ * priors = 4 x Nparams row-major table,
  * priors_switch = primitive ids, extra_priors[10]: Input_Data of tamcmc/headers/data.h:51-62).  Where the forward point
  * leaves a prior's support the backward difference of the prior is used, else that prior term is flat.
  * Out: logL0[C] (tempered), logPr0[C] (may be NULL), grad[C x Nvars], grad_prior[C x Nvars] (may be NULL: the prior's

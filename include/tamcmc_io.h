@@ -11,8 +11,10 @@
  *   read_MCMC_file_local                   tamcmc/sources/io_local.cpp:25-327   (.model)
  *   build_init_local + set_noise_params_local   io_local.cpp:329-1238, IO_models io_models.cpp:40-297
  *   Config::convert_priors_names_to_switch config.cpp:725-752 (ids of Config/default/primepriors_ctrl.list)
+ * Also read: the global (ids 3, 23), red-giant (ids 25, 27) and simple-matrix (Gaussian-envelope fits, ids 0 and 1) dialects and the
+ * .cfg files (below).
  * Not covered yet (TAMCMC_IO_ERR_UNSUPPORTED): model_MS_local_Hnlm, the other global variants (a1n/a1l/a2a3/ajAlm/AppWidth/
- * Classic_v2,v3), the asymptotic (RGB) and ajfit dialects, the .cfg files.
+ * Classic_v2,v3), the ajfit dialect.
  * Parity: the reference cannot be run here and ships no expected Input_Data dump: "parity unpinned"; tests pin the
  * result against values derived by hand from the shipped file with the rules cited above.
  */
@@ -59,7 +61,18 @@ int tamcmc_io_load_model_global(const char *model_path, double resol, tamcmc_inp
  * build_init_asymptotic + settings_aj_splittings_RGB (tamcmc/sources/io_asymptotic.cpp:32-955) and set_width_App2016_params_v2
  * (io_ms_global.cpp:1625-1720); prior_class 4. */
 int tamcmc_io_load_model_asymptotic(const char *model_path, double resol, tamcmc_inputs **out);
+/* `.model` of a Gaussian-envelope fit, the "simple matrix" dialect (Config::read_inputs_prior_Simple_Matrix, config.cpp:560-664):
+ * '#' comments, '* xmin xmax', '! names' + a line of values, '! relax' + a line of flags, '! prior names' + up to 4 rows of prior values.
+ * The file does not name its model: model_id (0 = model_Kallinger2014_Gaussian, 1 = model_Harvey_Gaussian) comes from the .cfg's
+ * model_fct_name (tamcmc_model_id_from_name); prior_class = model_id.  The plength of this dialect (count of each distinct name, length up
+ * to Nparams) comes from tamcmc_inputs_plength; tamcmc_inputs_get's fixed [11] receives {Nparams, 0, ...}. */
+int tamcmc_io_load_model_simple(const char *model_path, int model_id, tamcmc_inputs **out);
 void tamcmc_inputs_free(tamcmc_inputs *in);
+/* the inputs' plength at its own length: returns the number of entries (writes at most max of them; plength may be NULL to query).
+ * 11 for the local / global / red-giant dialects (what tamcmc_inputs_get writes), the count of distinct names for the simple dialect. */
+int tamcmc_inputs_plength(const tamcmc_inputs *in, int32_t *plength, int max);
+/* Config/default/models_ctrl.list: model function name (a .cfg's model_fct_name) -> model id, -1 when not listed */
+int tamcmc_model_id_from_name(const char *name);
 
 int tamcmc_inputs_nparams(const tamcmc_inputs *in);
 /* any pointer may be NULL.  priors: 4 x Nparams row-major; extra_priors: 10 slots (unused ones 0);

@@ -23,15 +23,16 @@ typedef struct tamcmc_sampler tamcmc_sampler;
 
 typedef struct tamcmc_sampler_config {
     /* modeling (config_default.cfg !Modeling; ids from Config/default/{models,priors,likelihoods}_ctrl.list) */
-    int32_t model_id;        /* model_fct_name_switch: 3, 11, 23 */
-    int32_t prior_class;     /* prior_fct_name_switch: 2 = io_MS_Global, 3 = io_local */
+    int32_t model_id;        /* model_fct_name_switch: 0, 1, 3, 11, 23, 25, 27 */
+    int32_t prior_class;     /* prior_fct_name_switch: 0 = priors_Kallinger2014_Gaussian, 1 = priors_Harvey_Gaussian, 2 = io_MS_Global,
+                                3 = io_local, 4 = io_asymptotic */
     int32_t likelihood_id;   /* 0 = chi(2,2p) */
     int32_t use_drift;       /* 0 = adaptive random-walk MH (the reference), 1 = Langevin drift with FD gradient */
     double likelihood_params;/* p */
     int64_t Nparams;
     const double *inputs;          /* [Nparams] initial parameter vector */
     const int32_t *relax;          /* [Nparams] 1 = free */
-    const int32_t *plength;        /* [11] */
+    const int32_t *plength;        /* [11], summing to Nparams (ids 0 and 1: {Nparams, 0, ...}, see tamcmc_io_load_model_simple) */
     const double *priors;          /* [4 x Nparams] row-major */
     const int32_t *priors_switch;  /* [Nparams] primitive prior ids (primepriors_ctrl.list) */
     const double *extra_priors;    /* [n_extra] */
@@ -81,6 +82,8 @@ int64_t tamcmc_sampler_nvars(const tamcmc_sampler *s);
  *     engine, fused step                                 candidate roles; longer vectors run every iteration on the lockstep kernels
  *                                                        (TAMCMC_INFO_FUSED_AVAILABLE = 0) -- same chains bit for bit
  *   red-giant models (ids 25/27)   lockstep kernels only; no Langevin step (use_drift = 1 -> TAMCMC_ERR_BAD_MODEL)
+ *   Gaussian-envelope models       host-driven engine only (random walk or Langevin); engine = 1 -> TAMCMC_ERR_BAD_MODEL at
+ *     (ids 0/1)                    tamcmc_sampler_create
  * The host-driven engine has no size-dependent branches (host memory, column Cholesky).
  * tamcmc_sampler_get_info reports which side of each limit a sampler is on and how many iterations each scheme has run. */
 #define TAMCMC_INFO_ENGINE 0          /* 0 host-driven, 1 device-resident */
@@ -191,7 +194,8 @@ int tamcmc_outputs_write_evidence(const char *file, int64_t n_samples, int32_t N
                                   int32_t interp_factor, double evidence, int32_t first);
 
 /* Host log-prior of one parameter vector = Model_def::call_prior (model_def.cpp:421-464) for the model classes
- * io_MS_Global (2) and io_local (3): long double arithmetic, the reference's term order.  *status (may be NULL) receives
+ * io_MS_Global (2), io_local (3), io_asymptotic (4), priors_Kallinger2014_Gaussian (0) and priors_Harvey_Gaussian (1; classes 0 and 1
+ * read neither plength nor extra_priors, which may be NULL): long double arithmetic, the reference's term order.  *status (may be NULL) receives
  * TAMCMC_ERR_BAD_MODEL for prior ids / model families this build does not carry. */
 double tamcmc_log_prior(int prior_class, const double *params, int64_t Nparams, const int32_t *plength, const double *priors,
                         const int32_t *priors_switch, const double *extra_priors, int32_t n_extra, int32_t *status);

@@ -14,6 +14,7 @@
 #include "kernels.h"
 #include "rgb_prestep.h"
 #include "mode_tables.h"
+#include "envelope.h"
 
 #include "ctx.h"
 
@@ -67,7 +68,7 @@ void tamcmc_hip_destroy(tamcmc_hip_ctx *c) {
     c->h_stage.release(); c->d_stage.release();
     c->d_part.release(); c->d_S.release(); c->d_model.release(); c->h_S.release();
     c->d_fd.release(); c->d_poly.release(); c->h_fd.release();
-    c->d_rgb.release(); c->h_rgb.release(); c->d_bg.release();
+    c->d_rgb.release(); c->h_rgb.release(); c->d_bg.release(); c->d_env.release();
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -120,6 +121,8 @@ int tamcmc_hip_set_spectrum(tamcmc_hip_ctx *c, const double *x, const double *y,
     if (!c || !x || !y || Nx < 2 || Nx > 0x7fffffff) return TAMCMC_ERR_BAD_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     c->hx.assign(x, x + Nx);
+    c->xmax = x[0];
+    for (int64_t i = 1; i < Nx; i++) c->xmax = x[i] > c->xmax ? x[i] : c->xmax;  // x.maxCoeff()
     std::vector<double> lx((size_t)Nx);
     for (int64_t i = 0; i < Nx; i++) lx[(size_t)i] = std::log(x[i]);  // FAST Harvey terms: (a x)^p = exp(p (ln a + ln x))
     HIPCHK(c, c->dx.reserve((size_t)Nx));
@@ -304,6 +307,13 @@ int tamcmc_hip_loglike_params_batch(tamcmc_hip_ctx *c, int model_id, int B, cons
                                     double *model, int32_t *status) {
     if (!c) return TAMCMC_ERR_BAD_ARG;
     if (c->Nx <= 0) return TAMCMC_ERR_NO_SPECTRUM;
+    // Gaussian-envelope fits: no mode table, plength is not read (may be NULL)
+    if (tamcmc::is_envelope_model(model_id)) {
+        if (B < 0 || !params || !logL || Nparams < 1 || B > 65535) return TAMCMC_ERR_BAD_ARG;
+        if (B == 0) return TAMCMC_OK;
+        HIPCHK(c, hipSetDevice(c->device));
+        return tamcmc::envelope_loglike_params_batch(c, model_id, B, params, Nparams, Tcoefs, p, logL, model, status);
+    }
     if (B < 0 || !params || !plength || !logL || Nparams < 1) return TAMCMC_ERR_BAD_ARG;
     if (B == 0) return TAMCMC_OK;
     HIPCHK(c, hipSetDevice(c->device));

@@ -71,6 +71,7 @@ struct tamcmc_hip_ctx {
     // resident spectrum
     int64_t Nx = 0;
     std::vector<double> hx;  // host copy of x (table builders need x[0], x[Nx-1], step)
+    double xmax = 0;         // largest x (the leakage filter of the Kallinger model, envelope.hip)
     tamcmc::DevBuf<double> dx, dy, dlogx;
     // ONE pinned staging block and its device image per call (a single H2D copy):
     //   [int32 begin/end pairs 2B | int32 nharvey B | int32 nnoise B | pad] [double noise B*stride] [multiplets]
@@ -79,6 +80,7 @@ struct tamcmc_hip_ctx {
     tamcmc::DevBuf<double> d_part, d_S, d_model;
     tamcmc::DevBuf<unsigned char> d_rgb;  // red-giant pre-step workspace (rgb_prestep.hip)
     tamcmc::PinBuf<unsigned char> h_rgb;  // its pinned host image: [Prep B | RowIn B] going up, [int status B] coming back
+    tamcmc::DevBuf<double> d_env;  // Gaussian-envelope fits: per (vector, chunk) trapezoid sums of the Kallinger normalisations
     tamcmc::DevBuf<double> d_bg;  // FAST far field: background series per (evaluation, tile) (bg_series.h)
     // finite-difference batches built on the device (fd_batch.hip)
     tamcmc::DevBuf<unsigned char> d_fd, d_poly;

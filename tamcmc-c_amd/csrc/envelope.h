@@ -1,0 +1,35 @@
+// envelope.h -- Gaussian-envelope background fits (model ids 0 and 1) on the device (envelope.hip).
+//   model_Kallinger2014_Gaussian (id 0)   tamcmc/sources/models.cpp (after model_Harvey_Gaussian), Kallinger2014 / get_ksinorm /
+//                                         eta_squared_Kallinger2014 in noise_models.cpp:70-153
+//   model_Harvey_Gaussian (id 1)          tamcmc/sources/models.cpp (before model_Kallinger2014_Gaussian), harvey_like noise_models.cpp:15-39
+// Every bin of the fitted range depends on every parameter: no mode table, no window.  The host forms a few scalars per vector
+// (EnvRow); the device walks the bins.
+#pragma once
+#include <stdint.h>
+
+#include "ctx.h"
+
+namespace tamcmc {
+
+inline bool is_envelope_model(int model_id) {
+    return model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN || model_id == TAMCMC_MODEL_HARVEY_GAUSSIAN;
+}
+// parameters each model reads: [H1, tc1, p1, H2, tc2, p2, B0, Amax, numax, Gauss_sigma] / 14 noise, Amax, numax, sigma, mu_numax, omega_numax
+inline int64_t envelope_nparams(int model_id) { return model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN ? 19 : 10; }
+
+// B parameter vectors (B x Nparams) -> S[b] = sum_i (y_i/M_i + ln M_i) on the resident spectrum, in a fixed order (a vector's S does not
+// depend on the batch it sits in).  model (device pointer or nullptr): B x Nx rows.  Enqueued on the context stream; S_dev is the
+// context's d_S (B doubles); the caller copies it back.
+int envelope_enqueue(tamcmc_hip_ctx *c, int model_id, int B, const double *params, int64_t Nparams, double *model_dev);
+
+// tamcmc_hip_loglike_params_batch for ids 0 and 1
+int envelope_loglike_params_batch(tamcmc_hip_ctx *c, int model_id, int B, const double *params, int64_t Nparams, const double *Tcoefs,
+                                  double p, double *logL, double *model, int32_t *status);
+
+// tamcmc_hip_fd_gradient(_posterior) for ids 0 and 1: brute force, C x (Nvars + 1) full evaluations in one batch; with_prior: the
+// log-priors of the forward and backward points (prior class 0 / 1, priors_impl.h) on the device, one thread per point
+int envelope_fd_run(tamcmc_hip_ctx *c, int model_id, bool with_prior, int prior_class, int C, const double *params, int64_t Nparams,
+                    const int32_t *index_to_relax, int Nvars, const double *hstep, const double *Tcoefs, double p, const double *priors,
+                    const int32_t *priors_switch, double *logL0, double *logPr0, double *grad, double *grad_prior);
+
+}  // namespace tamcmc

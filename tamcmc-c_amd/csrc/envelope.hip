@@ -1,0 +1,393 @@
+// envelope.hip -- Gaussian-envelope background fits on the device: model_Kallinger2014_Gaussian (id 0), model_Harvey_Gaussian (id 1).
+//
+// Both models are evaluated on every bin of the fitted range for every parameter vector: there is no window to skip.  Per bin they cost
+// one exp for the Gaussian, one exp per active power law ((a x)^p = exp(p (ln a + ln x)) on the context's resident ln x), an IEEE
+// reciprocal-by-divide per power law, the sinc^2 leakage filter (id 0) and the log of the likelihood term.
+//
+// Kernel sequence of one batch (stream order, no grid-wide barrier, no cooperative launch):
+//   k_env_ksi   (id 0 only)  grid (chunks, B): per (vector, chunk of 4096 bins) the three trapezoid partial sums of get_ksinorm
+//                            sum_i w_i / (1 + (x_i/b_k)^c_k), w = 1/2 on the first and last bin of the spectrum;
+//   k_env_eval               grid (tiles, B): every workgroup of vector b first reduces b's chunk partials in a fixed order (so every tile
+//                            of b sees the same xi_k bit for bit), then forms the model on its 1024 bins, writes the row (optional) and
+//                            its partial sums of y/M and ln M;
+//   k_finalize (kernels.hip) one workgroup per vector: the tile partials in a fixed order -> S[b].
+// The chunk and tile sizes depend on Nx only, never on B, and every sum runs in a fixed order: a vector's logL is bit-identical whatever
+// batch it sits in and whatever its position there.
+//
+// One arithmetic mode (TAMCMC_OPT_PRECISION does not apply): double, the reference's order of operations per bin except for the power laws
+// taken through exp/log and the trapezoid sums taken as a tree instead of a left-to-right loop.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "../../include/tamcmc_hip.h"
+#include "ctx.h"
+#include "envelope.h"
+#include "kernels.h"
+#include "priors_impl.h"
+
+namespace tamcmc {
+
+namespace {
+
+constexpr int EWG = 256;          // workgroup of both passes: four waves
+constexpr int EK = 4;             // k_env_eval: bins per thread -> 1024-bin tiles
+constexpr int EK1 = 16;           // k_env_ksi: bins per thread -> 4096-bin chunks
+constexpr int ETILE = EWG * EK;
+constexpr int ECHUNK = EWG * EK1;
+
+// what the host forms once per parameter vector (double, the reference's expressions)
+struct EnvRow {
+    double amp, numax, sig2;  // Gaussian: amp * exp((-0.5 (x - numax)^2) / sig2)       (id 0: amp * eta^2 first)
+    double N0;                // white noise
+    double H[2], lna[2], pw[2];  // id 1: H_k / (1 + exp(pw_k (lna_k + ln x))), lna_k = ln(1e-3 tc_k), term skipped when tc_k == 0
+    double b[3], lnb[3], c[3], a2[3];  // id 0: (xi_k a_k^2 / b_k) / (1 + exp(c_k (ln x - ln b_k))), xi_k from the trapezoid sums
+    int32_t hon[2];
+    int32_t pad[2];
+};
+
+// t^p as the reference's pow(t, p) for t >= 0, from ln t: pow(t, 0) = 1 also at t = 0 (exp(0 * -inf) would be NaN)
+__device__ __forceinline__ double pow_from_log(double p, double lt) { return p == 0.0 ? 1.0 : exp(p * lt); }
+
+template <int NV>
+__device__ __forceinline__ void env_block_reduce(double (&v)[NV], double *s_red, double *out) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < NV; i++) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) v[i] = v[i] + __shfl_down(v[i], off, 64);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < NV; i++) s_red[wave * NV + i] = v[i];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < NV; i++) {
+            double s = s_red[i];
+            for (int w = 1; w < EWG / 64; w++) s = s + s_red[w * NV + i];
+            out[i] = s;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(EWG) k_env_ksi(const double *logx, int Nx, int nchunk, const EnvRow *rows, double *part) {
+    __shared__ double s_red[3 * (EWG / 64)];
+    const int chunk = blockIdx.x, b = blockIdx.y;
+    const EnvRow &R = rows[b];
+    const double lnb0 = R.lnb[0], lnb1 = R.lnb[1], lnb2 = R.lnb[2], c0 = R.c[0], c1 = R.c[1], c2 = R.c[2];
+    double s[3] = {0.0, 0.0, 0.0};
+    const int base = chunk * ECHUNK + threadIdx.x;
+#pragma unroll 4
+    for (int k = 0; k < EK1; k++) {
+        const int i = base + k * EWG;
+        if (i < Nx) {
+            const double lx = logx[i];
+            const double w = (i == 0 || i == Nx - 1) ? 0.5 : 1.0;
+            s[0] = s[0] + w * (1.0 / (1.0 + pow_from_log(c0, lx - lnb0)));
+            s[1] = s[1] + w * (1.0 / (1.0 + pow_from_log(c1, lx - lnb1)));
+            s[2] = s[2] + w * (1.0 / (1.0 + pow_from_log(c2, lx - lnb2)));
+        }
+    }
+    double out[3];
+    env_block_reduce<3>(s, s_red, out);
+    if (threadIdx.x == 0) {
+        double *p = part + ((size_t)b * nchunk + chunk) * 3;
+        p[0] = out[0];
+        p[1] = out[1];
+        p[2] = out[2];
+    }
+}
+
+template <int KIND, bool WRITE_MODEL>  // KIND: model id (0 Kallinger, 1 Harvey)
+__global__ void __launch_bounds__(EWG) k_env_eval(const double *x, const double *y, const double *logx, int Nx, int ntiles, int nchunk,
+                                                  double h, double xmax, const EnvRow *rows, const double *ksi_part,
+                                                  double *model, double *part) {
+    __shared__ double s_red[3 * (EWG / 64)];
+    __shared__ double s_coef[3];
+    const int tile = blockIdx.x, b = blockIdx.y;
+    const EnvRow &R = rows[b];
+    if (KIND == 0) {
+        // xi_k = b_k / (h * sum_k): get_ksinorm (noise_models.cpp:70-89), the chunk partials summed in a fixed order
+        double s[3] = {0.0, 0.0, 0.0};
+        for (int ch = threadIdx.x; ch < nchunk; ch += EWG) {
+            const double *p = ksi_part + ((size_t)b * nchunk + ch) * 3;
+            s[0] = s[0] + p[0];
+            s[1] = s[1] + p[1];
+            s[2] = s[2] + p[2];
+        }
+        double out[3];
+        env_block_reduce<3>(s, s_red, out);
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const double integral = out[k] * h;
+                const double ksi = R.b[k] / integral;
+                s_coef[k] = ksi * R.a2[k] / R.b[k];
+            }
+        }
+        __syncthreads();
+    }
+    const double amp = R.amp, numax = R.numax, sig2 = R.sig2, N0 = R.N0;
+    double acc[2] = {0.0, 0.0};
+    const int base = tile * ETILE + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < EK; k++) {
+        const int i = base + k * EWG;
+        if (i < Nx) {
+            const double xi = x[i], yi = y[i], lx = logx[i];
+            const double d = xi - numax;
+            const double g = exp((-0.5 * (d * d)) / sig2);
+            double M;
+            if (KIND == 0) {
+                // eta^2 = sinc^2(pi x / (2 x_max)), 1 at a first bin x = 0 (eta_squared_Kallinger2014)
+                double eta2 = 1.0;
+                if (!(i == 0 && xi == 0.0)) {
+                    const double a = 0.5 * M_PI * xi / xmax;  // ((0.5 pi) x) / x_max, the reference's grouping
+                    const double sn = sin(a) / a;
+                    eta2 = sn * sn;
+                }
+                M = (amp * eta2) * g;
+                M = M + N0;  // Kallinger2014: Power = y + white noise, then the three super-Lorentzians, unfiltered (see tamcmc_hip.h)
+#pragma unroll
+                for (int q = 0; q < 3; q++) M = M + s_coef[q] * (1.0 / (pow_from_log(R.c[q], lx - R.lnb[q]) + 1.0));
+            } else {
+                M = amp * g;
+#pragma unroll
+                for (int q = 0; q < 2; q++)
+                    if (R.hon[q]) M = M + R.H[q] * (1.0 / (pow_from_log(R.pw[q], R.lna[q] + lx) + 1.0));
+                M = M + N0;
+            }
+            if (WRITE_MODEL) model[(size_t)b * Nx + i] = M;
+            acc[0] = acc[0] + yi / M;
+            acc[1] = acc[1] + log(M);
+        }
+    }
+    double out[2];
+    env_block_reduce<2>(acc, s_red, out);
+    if (threadIdx.x == 0) {
+        double *p = part + ((size_t)b * ntiles + tile) * 2;
+        p[0] = out[0];
+        p[1] = out[1];
+    }
+}
+
+// log-priors of n parameter vectors (rows of Np doubles): one thread each, the serial evaluation of priors_impl.h in double
+__global__ void __launch_bounds__(64) k_env_prior(int prior_class, int n, const double *P, long Np, const double *pp, const int *sw, double *lp,
+                                                  int *status) {
+    const int v = blockIdx.x * 64 + threadIdx.x;
+    if (v >= n) return;
+    int st = TAMCMC_OK;
+    lp[v] = (double)pr::prior_serial(prior_class, P + (size_t)v * Np, nullptr, Np, pp, sw, nullptr, &st);
+    status[v] = st;
+}
+
+// EnvRow of one vector: the scalar part of the model functions
+void env_row(int model_id, const double *p, EnvRow &R) {
+    std::memset(&R, 0, sizeof R);
+    if (model_id == TAMCMC_MODEL_HARVEY_GAUSSIAN) {
+        R.amp = std::fabs(p[7]);
+        R.numax = p[8];  // (not taken in absolute value by model_Harvey_Gaussian)
+        R.sig2 = std::pow(std::fabs(p[9]), 2);
+        for (int q = 0; q < 2; q++) {  // harvey_like(|params[0:7]|, ...): [H, tc, p] x 2, then B0
+            const double H = std::fabs(p[3 * q]), tc = std::fabs(p[3 * q + 1]), pw = std::fabs(p[3 * q + 2]);
+            R.hon[q] = (tc != 0) ? 1 : 0;
+            R.H[q] = H;
+            R.lna[q] = std::log((1e-3) * tc);
+            R.pw[q] = pw;
+        }
+        R.N0 = std::fabs(p[6]);
+        return;
+    }
+    // model_Kallinger2014_Gaussian + Kallinger2014(numax, mu_numax, params[0:14], ...)
+    const double Amax = std::fabs(p[14]), numax = std::fabs(p[15]), sig = std::fabs(p[16]), mu_numax = p[17];
+    R.amp = std::fabs(Amax);
+    R.numax = numax;
+    R.sig2 = std::pow(std::fabs(sig), 2);
+    const double a0 = std::fabs(p[0] * std::pow(std::fabs(numax), p[1]));
+    const double b0 = std::fabs(p[2] * std::pow(std::fabs(numax + mu_numax), p[3]));
+    const double c0 = std::fabs(p[4]);
+    const double a1 = p[5], a2 = p[6];
+    const double b1 = std::fabs(p[7] * std::pow(std::fabs(numax + mu_numax), p[8]));
+    const double b2 = std::fabs(p[10] * std::pow(std::fabs(numax + mu_numax), p[11]));
+    const double c1 = std::fabs(p[9]), c2 = std::fabs(p[12]);
+    R.N0 = std::fabs(p[13]);
+    const double bb[3] = {b0, b1, b2}, cc[3] = {c0, c1, c2}, aa[3] = {a0, a1, a2};
+    for (int k = 0; k < 3; k++) {
+        R.b[k] = bb[k];
+        R.lnb[k] = std::log(bb[k]);
+        R.c[k] = cc[k];
+        R.a2[k] = std::pow(aa[k], 2);
+    }
+}
+
+}  // namespace
+
+int envelope_enqueue(tamcmc_hip_ctx *c, int model_id, int B, const double *params, int64_t Nparams, double *model_dev) {
+    const int Nx = (int)c->Nx;
+    const int ntiles = (Nx + ETILE - 1) / ETILE, nchunk = (Nx + ECHUNK - 1) / ECHUNK;
+    const size_t row_bytes = (size_t)B * sizeof(EnvRow);
+    HIPCHK(c, c->h_stage.reserve(row_bytes));
+    HIPCHK(c, c->d_stage.reserve(row_bytes));
+    HIPCHK(c, c->d_part.reserve((size_t)B * ntiles * 2));
+    HIPCHK(c, c->d_S.reserve((size_t)B));
+    EnvRow *hr = (EnvRow *)c->h_stage.p;
+    for (int b = 0; b < B; b++) env_row(model_id, params + (size_t)b * Nparams, hr[b]);
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(c->d_stage.p, c->h_stage.p, row_bytes, hipMemcpyHostToDevice, st));
+    const EnvRow *rows = (const EnvRow *)c->d_stage.p;
+    const double h = c->hx[1] - c->hx[0];  // get_ksinorm's step: x(1) - x(0), whatever the rest of the grid does
+    if (c->timing) HIPCHK(c, hipEventRecord(c->ev0, st));
+    if (model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN) {
+        HIPCHK(c, c->d_env.reserve((size_t)B * nchunk * 3));
+        hipLaunchKernelGGL(k_env_ksi, dim3(nchunk, B), dim3(EWG), 0, st, c->dlogx.p, Nx, nchunk, rows, c->d_env.p);
+        HIPCHK(c, hipGetLastError());
+    }
+    const dim3 grid(ntiles, B);
+    if (model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN) {
+        if (model_dev) hipLaunchKernelGGL((k_env_eval<0, true>), grid, dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, Nx, ntiles, nchunk, h, c->xmax, rows, c->d_env.p, model_dev, c->d_part.p);
+        else hipLaunchKernelGGL((k_env_eval<0, false>), grid, dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, Nx, ntiles, nchunk, h, c->xmax, rows, c->d_env.p, model_dev, c->d_part.p);
+    } else {
+        if (model_dev) hipLaunchKernelGGL((k_env_eval<1, true>), grid, dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, Nx, ntiles, nchunk, h, c->xmax, rows, nullptr, model_dev, c->d_part.p);
+        else hipLaunchKernelGGL((k_env_eval<1, false>), grid, dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, Nx, ntiles, nchunk, h, c->xmax, rows, nullptr, model_dev, c->d_part.p);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, launch_finalize(c->d_part.p, B, ntiles, c->d_S.p, st));
+    if (c->timing) HIPCHK(c, hipEventRecord(c->ev1, st));
+    return TAMCMC_OK;
+}
+
+static int env_check(tamcmc_hip_ctx *c, int model_id, int64_t Nparams) {
+    if (Nparams < envelope_nparams(model_id)) return TAMCMC_ERR_BAD_ARG;
+    if (c->Nx > 0x7fffffff / 2) return TAMCMC_ERR_BAD_ARG;
+    return TAMCMC_OK;
+}
+
+static int env_account(tamcmc_hip_ctx *c, int B) {
+    if (!c->timing) return TAMCMC_OK;
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->kernel_ms += ms;
+    c->launches += 1;
+    c->evals += B;
+    return TAMCMC_OK;
+}
+
+int envelope_loglike_params_batch(tamcmc_hip_ctx *c, int model_id, int B, const double *params, int64_t Nparams, const double *Tcoefs,
+                                  double p, double *logL, double *model, int32_t *status) {
+    int rc = env_check(c, model_id, Nparams);
+    if (rc) return rc;
+    const int64_t Nx = c->Nx;
+    if (model) HIPCHK(c, c->d_model.reserve((size_t)B * Nx));
+    rc = envelope_enqueue(c, model_id, B, params, Nparams, model ? c->d_model.p : nullptr);
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    HIPCHK(c, c->h_S.reserve((size_t)B));
+    HIPCHK(c, hipMemcpyAsync(c->h_S.p, c->d_S.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (model) HIPCHK(c, hipMemcpyAsync(model, c->d_model.p, (size_t)B * Nx * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    rc = env_account(c, B);
+    if (rc) return rc;
+    // call_likelihood (model_def.cpp:399-401): f = -p*(sum1+sum2) in long double, then / Tcoefs[m]
+    const long pl = (long)p;
+    for (int b = 0; b < B; b++) {
+        long double f = c->h_S.p[b];
+        f = -pl * f;
+        logL[b] = (double)(f / (Tcoefs ? Tcoefs[b] : 1.0));
+        if (status) status[b] = TAMCMC_OK;  // these models have no table that can fail: a non-finite vector gives a non-finite logL
+    }
+    return TAMCMC_OK;
+}
+
+int envelope_fd_run(tamcmc_hip_ctx *c, int model_id, bool with_prior, int prior_class, int C, const double *params, int64_t Nparams,
+                    const int32_t *index_to_relax, int Nvars, const double *hstep, const double *Tcoefs, double p, const double *priors,
+                    const int32_t *priors_switch, double *logL0, double *logPr0, double *grad, double *grad_prior) {
+    int rc = env_check(c, model_id, Nparams);
+    if (rc) return rc;
+    if (with_prior && prior_class != model_id) return TAMCMC_ERR_BAD_MODEL;  // priors_ctrl.list pairs class 0 with id 0, class 1 with id 1
+    const int E = Nvars + 1;
+    const size_t B = (size_t)C * E, Np = (size_t)Nparams, Nv = (size_t)Nvars;
+    if (B > 65535) return TAMCMC_ERR_BAD_ARG;  // grid.y
+    // forward points theta + h e_k (the same double addition the gradient's divisor uses), then the backward points theta - h e_k
+    std::vector<double> P((with_prior ? 2 : 1) * B * Np);
+    for (int ch = 0; ch < C; ch++)
+        for (int e = 0; e < E; e++) {
+            double *f = P.data() + ((size_t)ch * E + e) * Np;
+            std::memcpy(f, params + (size_t)ch * Np, Np * 8);
+            if (e > 0) f[index_to_relax[e - 1]] = params[(size_t)ch * Np + index_to_relax[e - 1]] + hstep[e - 1];
+            if (with_prior) {
+                double *g = P.data() + (B + (size_t)ch * E + e) * Np;
+                std::memcpy(g, params + (size_t)ch * Np, Np * 8);
+                if (e > 0) g[index_to_relax[e - 1]] = params[(size_t)ch * Np + index_to_relax[e - 1]] - hstep[e - 1];
+            }
+        }
+    rc = envelope_enqueue(c, model_id, (int)B, P.data(), Nparams, nullptr);
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    HIPCHK(c, c->h_S.reserve(B));
+    HIPCHK(c, hipMemcpyAsync(c->h_S.p, c->d_S.p, B * sizeof(double), hipMemcpyDeviceToHost, st));
+    std::vector<double> lp;
+    std::vector<int> lst;
+    if (with_prior) {
+        // one block: [vectors 2B x Np | priors 4 x Np | switch Np (int) ] in, [lp 2B | status 2B (int)] out
+        const size_t nP = 2 * B * Np, o_pp = nP * 8, o_sw = o_pp + 4 * Np * 8, o_lp = (o_sw + Np * 4 + 15) & ~(size_t)15,
+                     o_st = o_lp + 2 * B * 8, bytes = o_st + 2 * B * 4;
+        HIPCHK(c, c->h_fd.reserve(bytes));
+        HIPCHK(c, c->d_fd.reserve(bytes));
+        unsigned char *hb = c->h_fd.p, *db = c->d_fd.p;
+        std::memcpy(hb, P.data(), nP * 8);
+        std::memcpy(hb + o_pp, priors, 4 * Np * 8);
+        std::memcpy(hb + o_sw, priors_switch, Np * 4);
+        HIPCHK(c, hipMemcpyAsync(db, hb, o_lp, hipMemcpyHostToDevice, st));
+        const int n = (int)(2 * B);
+        hipLaunchKernelGGL(k_env_prior, dim3((n + 63) / 64), dim3(64), 0, st, prior_class, n, (const double *)db, (long)Np,
+                           (const double *)(db + o_pp), (const int *)(db + o_sw), (double *)(db + o_lp), (int *)(db + o_st));
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(hb + o_lp, db + o_lp, bytes - o_lp, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        lp.assign((const double *)(hb + o_lp), (const double *)(hb + o_lp) + 2 * B);
+        lst.assign((const int *)(hb + o_st), (const int *)(hb + o_st) + 2 * B);
+    } else {
+        HIPCHK(c, hipStreamSynchronize(st));
+    }
+    rc = env_account(c, (int)B);
+    if (rc) return rc;
+    int first_err = TAMCMC_OK;
+    for (size_t s = 0; s < lst.size(); s++)
+        if (lst[s] != TAMCMC_OK && first_err == TAMCMC_OK) first_err = lst[s];
+    const long pl = (long)p;
+    for (int ch = 0; ch < C; ch++) {
+        const double T = Tcoefs ? Tcoefs[ch] : 1.0;
+        auto scaled = [&](double S) {
+            long double f = S;
+            f = -pl * f;
+            return (double)(f / T);
+        };
+        const double L0 = scaled(c->h_S.p[(size_t)ch * E]);
+        logL0[ch] = L0;
+        const double pr0 = with_prior ? lp[(size_t)ch * E] : 0.0;
+        if (logPr0) logPr0[ch] = pr0;
+        for (int k = 0; k < Nvars; k++) {
+            const double x0 = params[(size_t)ch * Np + index_to_relax[k]];
+            volatile double xp = x0 + hstep[k];
+            const double happ = xp - x0;
+            double g = (scaled(c->h_S.p[(size_t)ch * E + k + 1]) - L0) / happ;
+            if (with_prior) {  // same combination as the Lorentzian batches (fd_batch.hip)
+                if (!std::isfinite(g)) g = 0.0;
+                const double prp = lp[(size_t)ch * E + k + 1], prm = lp[B + (size_t)ch * E + k + 1];
+                double gp;
+                if (std::isfinite(prp)) gp = (prp - pr0) / happ;
+                else gp = std::isfinite(prm) ? (pr0 - prm) / happ : 0.0;
+                g += gp;
+                if (grad_prior) grad_prior[(size_t)ch * Nv + k] = gp;
+            }
+            grad[(size_t)ch * Nv + k] = g;
+        }
+    }
+    return first_err;
+}
+
+}  // namespace tamcmc

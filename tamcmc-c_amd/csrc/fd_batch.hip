@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "envelope.h"
 #include "dev_unpack.h"
 #include "kernels.h"
 #include "fd_batch.h"
@@ -476,6 +477,17 @@ extern "C" {
 int tamcmc_hip_fd_gradient(tamcmc_hip_ctx *c, int model_id, int C, const double *params, int64_t Nparams,
                            const int32_t *plength, const int32_t *index_to_relax, int Nvars, const double *hstep,
                            const double *Tcoefs, double p, double *logL0, double *grad) {
+    if (tamcmc::is_envelope_model(model_id)) {  // every parameter moves every bin: Nvars + 1 full evaluations per chain, one batch
+        if (!c) return TAMCMC_ERR_BAD_ARG;
+        if (c->Nx <= 0) return TAMCMC_ERR_NO_SPECTRUM;
+        if (C < 0 || Nvars < 0 || !params || !index_to_relax || !hstep || !logL0 || !grad || Nparams < 1) return TAMCMC_ERR_BAD_ARG;
+        for (int k = 0; k < Nvars; k++)
+            if (index_to_relax[k] < 0 || index_to_relax[k] >= Nparams) return TAMCMC_ERR_BAD_ARG;
+        if (C == 0) return TAMCMC_OK;
+        HIPCHK(c, hipSetDevice(c->device));
+        return tamcmc::envelope_fd_run(c, model_id, false, 0, C, params, Nparams, index_to_relax, Nvars, hstep, Tcoefs, p, nullptr, nullptr,
+                                       logL0, nullptr, grad, nullptr);
+    }
     return fd_run(c, model_id, 0, C, params, Nparams, plength, index_to_relax, Nvars, hstep, Tcoefs, p, nullptr, nullptr, nullptr,
                   logL0, nullptr, grad, nullptr);
 }
@@ -485,6 +497,19 @@ int tamcmc_hip_fd_gradient_posterior(tamcmc_hip_ctx *c, int model_id, int prior_
                                      const double *hstep, const double *Tcoefs, double p, const double *priors,
                                      const int32_t *priors_switch, const double *extra_priors, double *logL0, double *logPr0,
                                      double *grad, double *grad_prior) {
+    if (tamcmc::is_envelope_model(model_id)) {  // brute force, priors of classes 0 / 1 on the device (envelope.hip)
+        if (!c) return TAMCMC_ERR_BAD_ARG;
+        if (c->Nx <= 0) return TAMCMC_ERR_NO_SPECTRUM;
+        if (C < 0 || Nvars < 0 || !params || !index_to_relax || !hstep || !logL0 || !grad || Nparams < 1 || !priors || !priors_switch)
+            return TAMCMC_ERR_BAD_ARG;
+        for (int k = 0; k < Nvars; k++)
+            if (index_to_relax[k] < 0 || index_to_relax[k] >= Nparams) return TAMCMC_ERR_BAD_ARG;
+        if (prior_class != 0 && prior_class != 1) return TAMCMC_ERR_BAD_MODEL;
+        if (C == 0) return TAMCMC_OK;
+        HIPCHK(c, hipSetDevice(c->device));
+        return tamcmc::envelope_fd_run(c, model_id, true, prior_class, C, params, Nparams, index_to_relax, Nvars, hstep, Tcoefs, p, priors,
+                                       priors_switch, logL0, logPr0, grad, grad_prior);
+    }
     if (prior_class != 2 && prior_class != 3) return TAMCMC_ERR_BAD_MODEL;
     return fd_run(c, model_id, prior_class, C, params, Nparams, plength, index_to_relax, Nvars, hstep, Tcoefs, p, priors,
                   priors_switch, extra_priors, logL0, logPr0, grad, grad_prior);

@@ -67,6 +67,9 @@ int tamcmc_sampler_create(tamcmc_sampler **out, tamcmc_hip_ctx *ctx, const tamcm
     if (!out || !ctx || !c || !c->inputs || !c->relax || !c->plength || !c->priors || !c->priors_switch) return TAMCMC_ERR_BAD_ARG;
     if (c->Nchains < 1 || c->Nparams < 1) return TAMCMC_ERR_BAD_ARG;
     *out = nullptr;
+    // Gaussian-envelope fits (ids 0, 1): host-driven engine only (random walk or Langevin); the device-resident engine has no kernels for them
+    if ((c->model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN || c->model_id == TAMCMC_MODEL_HARVEY_GAUSSIAN) && c->engine == 1)
+        return TAMCMC_ERR_BAD_MODEL;
     auto s = std::make_unique<tamcmc_sampler>();
     Config &g = s->cfg;
     g.modeling.model_fct_name_switch = c->model_id;
@@ -415,18 +418,25 @@ int tamcmc_sampler_read_restore(tamcmc_sampler *s, const char *root, int32_t res
 double tamcmc_log_prior(int prior_class, const double *params, int64_t Nparams, const int32_t *plength, const double *priors,
                         const int32_t *priors_switch, const double *extra_priors, int32_t n_extra, int32_t *status) {
     if (status) *status = TAMCMC_OK;
-    if (!params || !plength || !priors || !priors_switch || !extra_priors || Nparams < 1) {
+    const bool envelope = (prior_class == 0 || prior_class == 1);  // these two read neither plength nor the extra priors
+    if (!params || (!envelope && (!plength || !extra_priors)) || !priors || !priors_switch || Nparams < 1) {
         if (status) *status = TAMCMC_ERR_BAD_ARG;
         return NAN;
     }
-    std::vector<int> pl(plength, plength + 11), sw(priors_switch, priors_switch + Nparams);
+    if (envelope && Nparams < (prior_class == 0 ? 19 : 10)) {
+        if (status) *status = TAMCMC_ERR_BAD_ARG;
+        return NAN;
+    }
+    std::vector<int> sw(priors_switch, priors_switch + Nparams);
+    std::vector<int> pl = envelope ? std::vector<int>(11, 0) : std::vector<int>(plength, plength + 11);
     std::vector<double> extra(10, 0.0);
-    for (int i = 0; i < n_extra && i < 10; i++) extra[(size_t)i] = extra_priors[i];
+    for (int i = 0; i < n_extra && i < 10 && extra_priors; i++) extra[(size_t)i] = extra_priors[i];
     Matrix pp(4, Nparams);
     std::memcpy(pp.a.data(), priors, 4 * (size_t)Nparams * sizeof(double));
     int st = TAMCMC_OK;
     long double r;
-    if (prior_class == 2) r = priors_MS_Global(params, pl, pp, sw, extra, &st);
+    if (envelope) r = priors_envelope(prior_class, params, (long)Nparams, pp, sw, &st);
+    else if (prior_class == 2) r = priors_MS_Global(params, pl, pp, sw, extra, &st);
     else if (prior_class == 3) r = priors_local(params, pl, pp, sw, extra, &st);
     else if (prior_class == 4) r = priors_asymptotic(params, pl, pp, sw, extra, &st);
     else { st = TAMCMC_ERR_BAD_MODEL; r = NAN; }

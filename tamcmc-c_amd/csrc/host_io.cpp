@@ -148,6 +148,7 @@ struct tamcmc_inputs {
     double dnu, c_l;
     int model_id, prior_class;
     std::string model_name;
+    std::vector<int> plength_simple;  // simple-matrix dialect: counts of each distinct parameter name (length <= Nparams)
 };
 
 namespace {
@@ -989,6 +990,119 @@ int tamcmc_io_load_model_asymptotic(const char *model_path, double resol, tamcmc
     if (rc) { delete in; return rc; }
     *out = in;
     return TAMCMC_IO_OK;
+}
+
+// Config::read_inputs_prior_Simple_Matrix (config.cpp:560-664), the dialect of the Gaussian-envelope fits (config.cpp:1996-2007):
+//   '#' comment lines; '* xmin xmax'; '! names' + one line of values; '! relax' + one line of flags (the reference drops the line's first
+//   character, substr(1)); '! prior names' + up to 4 rows of prior values (-9999 where empty).  plength = the count of each distinct name,
+//   in order of first appearance.  The file does not name its model: model_id comes from the .cfg's model_fct_name.
+int tamcmc_io_load_model_simple(const char *model_path, int model_id, tamcmc_inputs **out) {
+    if (!model_path || !out) return fail(TAMCMC_IO_ERR_ARG, "bad argument");
+    *out = nullptr;
+    if (model_id != TAMCMC_MODEL_KALLINGER2014_GAUSSIAN && model_id != TAMCMC_MODEL_HARVEY_GAUSSIAN)
+        return fail(TAMCMC_IO_ERR_UNSUPPORTED, "the simple-matrix dialect serves model ids 0 and 1 only");
+    std::ifstream f(model_path);
+    if (!f.is_open()) return fail(TAMCMC_IO_ERR_OPEN, std::string("cannot open ") + model_path);
+    std::vector<std::string> raw;
+    for (std::string ln; std::getline(f, ln);) raw.push_back(ln);
+    size_t ip = 0;
+    while (ip < raw.size() && (trim(raw[ip]).empty() || trim(raw[ip])[0] == '#')) ip++;
+    auto next = [&](std::string &ln) {
+        if (ip >= raw.size()) return false;
+        ln = raw[ip++];
+        return true;
+    };
+    auto numbers = [](const std::string &s, std::vector<double> &v) {
+        v.clear();
+        for (const std::string &w : split(s, " \t\r")) {
+            double d;
+            if (!to_double(w, &d)) return false;
+            v.push_back(d);
+        }
+        return true;
+    };
+    std::string ln;
+    std::vector<double> range, values, row;
+    if (!next(ln) || trim(ln).empty() || trim(ln)[0] != '*' || !numbers(trim(ln).substr(1), range) || range.size() != 2)
+        return fail(TAMCMC_IO_ERR_SYNTAX, "simple .model: expected the '* xmin xmax' line");
+    if (!next(ln) || trim(ln).empty() || trim(ln)[0] != '!') return fail(TAMCMC_IO_ERR_SYNTAX, "simple .model: expected the '!' names line");
+    const std::vector<std::string> names = split(trim(ln).substr(1), " \t\r");
+    const int N = (int)names.size();
+    if (N < 1) return fail(TAMCMC_IO_ERR_SYNTAX, "simple .model: no parameter names");
+    if (!next(ln) || !numbers(trim(ln), values) || (int)values.size() != N)
+        return fail(TAMCMC_IO_ERR_SYNTAX, "simple .model: the values line does not match the names");
+    if (!next(ln) || trim(ln).empty() || trim(ln)[0] != '!') return fail(TAMCMC_IO_ERR_SYNTAX, "simple .model: expected the '! relax' line");
+    if (!next(ln) || ln.empty()) return fail(TAMCMC_IO_ERR_SYNTAX, "simple .model: missing relax flags");
+    std::vector<int> relax;
+    for (const std::string &w : split(ln.substr(1), " \t\r")) {  // (substr(1) on the untrimmed line, config.cpp:608)
+        std::istringstream is(w);
+        long v;
+        if (!(is >> v) || !is.eof()) return fail(TAMCMC_IO_ERR_SYNTAX, "simple .model: bad relax flag '" + w + "'");
+        relax.push_back((int)v);
+    }
+    if ((int)relax.size() != N) return fail(TAMCMC_IO_ERR_SYNTAX, "simple .model: the relax line does not match the names");
+    if (!next(ln) || trim(ln).empty() || trim(ln)[0] != '!') return fail(TAMCMC_IO_ERR_SYNTAX, "simple .model: expected the '!' prior names line");
+    const std::vector<std::string> pnames = split(trim(ln).substr(1), " \t\r");
+    if ((int)pnames.size() != N) return fail(TAMCMC_IO_ERR_SYNTAX, "simple .model: the prior names do not match the parameters");
+    for (const std::string &pn : pnames)
+        if (prior_id(pn) < 0) return fail(TAMCMC_IO_ERR_SYNTAX, "simple .model: unknown prior '" + pn + "'");
+    std::vector<double> priors((size_t)4 * N, -9999.0);
+    int nrow = 0;
+    while (next(ln)) {
+        if (trim(ln).empty()) continue;
+        if (nrow >= 4) return fail(TAMCMC_IO_ERR_SYNTAX, "simple .model: more than 4 rows of prior values");
+        if (!numbers(trim(ln), row) || (int)row.size() != N) return fail(TAMCMC_IO_ERR_SYNTAX, "simple .model: a prior row does not match the parameters");
+        for (int i = 0; i < N; i++) priors[(size_t)nrow * N + i] = row[(size_t)i];
+        nrow++;
+    }
+    const int need = model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN ? 19 : 10;
+    if (N < need) return fail(TAMCMC_IO_ERR_SYNTAX, "simple .model: too few parameters for the model");
+    tamcmc_inputs *in = new tamcmc_inputs();
+    in->all.n = N;
+    in->all.names = names;
+    in->all.prior_names = pnames;
+    in->all.inputs = values;
+    in->all.relax = relax;
+    in->all.priors = priors;
+    in->plength[0] = N;  // the fixed [11] of tamcmc_inputs_get: one block holding every parameter (sums to Nparams)
+    std::vector<std::string> seen;
+    for (const std::string &nm : names) {
+        size_t k = 0;
+        while (k < seen.size() && seen[k] != nm) k++;
+        if (k == seen.size()) { seen.push_back(nm); in->plength_simple.push_back(0); }
+        in->plength_simple[k]++;
+    }
+    in->range[0] = range[0];
+    in->range[1] = range[1];
+    in->model_id = model_id;
+    in->prior_class = model_id;  // priors_ctrl.list: 0 = priors_Kallinger2014_Gaussian, 1 = priors_Harvey_Gaussian
+    in->model_name = model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN ? "model_Kallinger2014_Gaussian" : "model_Harvey_Gaussian";
+    *out = in;
+    return TAMCMC_IO_OK;
+}
+
+int tamcmc_inputs_plength(const tamcmc_inputs *in, int32_t *plength, int max) {
+    if (!in || max < 0) return fail(TAMCMC_IO_ERR_ARG, "bad argument");
+    std::vector<int> v = in->plength_simple;
+    if (v.empty()) v.assign(in->plength, in->plength + 11);
+    for (int k = 0; k < (int)v.size() && k < max && plength; k++) plength[k] = v[(size_t)k];
+    return (int)v.size();
+}
+
+int tamcmc_model_id_from_name(const char *name) {
+    static const struct { const char *n; int id; } tab[] = {  // Config/default/models_ctrl.list
+        {"model_Kallinger2014_Gaussian", 0}, {"model_Harvey_Gaussian", 1}, {"model_MS_Global_a1etaa3_HarveyLike_Classic", 3},
+        {"model_MS_Global_a1l_etaa3_HarveyLike", 6}, {"model_MS_Global_a1n_etaa3_HarveyLike", 7}, {"model_MS_Global_a1nl_etaa3_HarveyLike", 8},
+        {"model_MS_Global_a1etaa3_AppWidth_HarveyLike_v1", 9}, {"model_MS_Global_a1etaa3_AppWidth_HarveyLike_v2", 10},
+        {"model_MS_local_basic", 11}, {"model_MS_Global_a1etaa3_HarveyLike_Classic_v2", 12},
+        {"model_MS_Global_a1etaa3_HarveyLike_Classic_v3", 13}, {"model_MS_local_Hnlm", 14}, {"model_MS_Global_a1n_a2a3_HarveyLike", 18},
+        {"model_MS_Global_a1nl_a2a3_HarveyLike", 19}, {"model_MS_Global_ajAlm_HarveyLike", 21}, {"model_MS_Global_aj_HarveyLike", 23},
+        {"model_RGB_asympt_aj_AppWidth_HarveyLike_v4", 25}, {"model_ajfit", 26}, {"model_RGB_asympt_aj_CteWidth_HarveyLike_v4", 27}};
+    if (!name) return -1;
+    const std::string nm = trim(name);
+    for (const auto &e : tab)
+        if (nm == e.n) return e.id;
+    return -1;
 }
 
 void tamcmc_inputs_free(tamcmc_inputs *in) { delete in; }

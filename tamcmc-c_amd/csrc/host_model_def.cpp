@@ -64,6 +64,7 @@ long double Model_def::call_prior_params(const double *p) {
     int st = TAMCMC_OK;
     long double r;
     switch (prior_fct_name_switch) {  // Config/default/priors_ctrl.list
+    case 0: case 1: r = priors_envelope(prior_fct_name_switch, p, Nparams, priors_params, priors_params_names_switch, &st); break;
     case 2: r = priors_MS_Global(p, plength, priors_params, priors_params_names_switch, extra_priors, &st); break;
     case 3: r = priors_local(p, plength, priors_params, priors_params_names_switch, extra_priors, &st); break;
     case 4: r = priors_asymptotic(p, plength, priors_params, priors_params_names_switch, extra_priors, &st); break;

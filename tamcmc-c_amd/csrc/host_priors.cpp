@@ -38,6 +38,10 @@ long double priors_local(const double *params, const std::vector<int> &pl, const
     return pr::prior_serial(3, params, pl.data(), nparams_of(pl), pp.a.data(), sw.data(), extra.data(), status);
 }
 
+long double priors_envelope(int prior_class, const double *params, long Nparams, const Matrix &pp, const std::vector<int> &sw, int *status) {
+    return pr::prior_serial(prior_class, params, nullptr, Nparams, pp.a.data(), sw.data(), nullptr, status);
+}
+
 long double priors_asymptotic(const double *params, const std::vector<int> &pl, const Matrix &pp, const std::vector<int> &sw,
                               const std::vector<double> &extra, int *status) {
     return pr::prior_serial(4, params, pl.data(), nparams_of(pl), pp.a.data(), sw.data(), extra.data(), status);

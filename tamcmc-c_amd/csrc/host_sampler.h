@@ -89,6 +89,10 @@ long double priors_local(const double *params, const std::vector<int> &plength, 
 long double priors_asymptotic(const double *params, const std::vector<int> &plength, const Matrix &priors_params,
                          const std::vector<int> &priors_names_switch, const std::vector<double> &extra_priors, int *status);  // priors_calc.cpp:319-512
 
+// priors_Kallinger2014_Gaussian (prior_class 0) and priors_Harvey_Gaussian (1), priors_calc.cpp:631-703: no plength, no extra priors
+long double priors_envelope(int prior_class, const double *params, long Nparams, const Matrix &priors_params,
+                            const std::vector<int> &priors_names_switch, int *status);
+
 class Model_def {  // model_def.h:27-85
     std::vector<double> cons;
     long Ncons = 0, Nvars = 0, Nparams = 0, Nmodels = 0;

@@ -3,6 +3,7 @@
 //   apply_generic_priors tamcmc/sources/priors_calc.cpp:725-870
 //   priors_MS_Global     tamcmc/sources/priors_calc.cpp:27-317   (model_index 9 = aj family, default = Classic)
 //   priors_local         tamcmc/sources/priors_calc.cpp:514-629
+//   priors_Kallinger2014_Gaussian (class 0), priors_Harvey_Gaussian (class 1)   tamcmc/sources/priors_calc.cpp:631-703
 // Where the reference exits (unsupported prior ids, model classes flagged "needs checks") *status is set to
 // TAMCMC_ERR_BAD_MODEL and -inf is returned.
 // The priors are a SUM of independent terms; `term range` arguments let the device evaluate the terms in parallel
@@ -38,6 +39,13 @@ TM_HD xreal xpow2(xreal v) {  // pow(v, 2.)
 #endif
 }
 TM_HD xreal xfabs(xreal v) { return v < 0 ? -v : v; }
+TM_HD xreal xpow(xreal v, xreal e) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return pow(v, e);
+#else
+    return powl(v, e);
+#endif
+}
 #define TAMCMC_PIl ((xreal)3.141592653589793238462643383279502884L)
 
 TM_HD xreal logP_uniform(xreal b_min, xreal b_max, xreal x) {
@@ -238,11 +246,38 @@ TM_HD xreal local_constraints(const double *params, const int *pl, const int *sw
     return 0;
 }
 
+// ---- Gaussian-envelope fits: the Stello et al. (2009) width bound of priors_Harvey_Gaussian / priors_Kallinger2014_Gaussian ----
+// Dnu_expected = beta0 numax^beta1 with beta0 = 0.263, beta1 = 0.77 written as DOUBLE literals stored in long doubles (priors_calc.cpp:637-638,
+// :655-656), the power taken in long double (std::pow(double, long double)); the vector is rejected when sigma < Dnu_expected / 2.  Every
+// comparison is false for a NaN operand: a NaN numax or sigma passes the bound, as in the reference.
+TM_HD bool envelope_width_rejects(double numax, double sigma) {
+    const xreal beta0 = (xreal)0.263, beta1 = (xreal)0.77;
+    const xreal Dnu_expected = beta0 * xpow((xreal)numax, beta1);
+    return (xreal)sigma < Dnu_expected / 2;
+}
+
 // ---- serial evaluation in the reference's order (host; also usable on the device by one thread) ----
 // generic_terms (class 4): the Np generic prior terms already evaluated (the device spreads them over lanes; summed here in the same order)
 TM_HD xreal prior_serial(int prior_class, const double *params, const int *pl, long Np, const double *pp, const int *sw,
                          const double *extra, int *status, const xreal *generic_terms = nullptr) {
     xreal f = 0;
+    if (prior_class == 1) {  // priors_Harvey_Gaussian: [H1, tc1, p1, H2, tc2, p2, B0, Amax, numax, Gauss_sigma]
+        if (envelope_width_rejects(params[8], params[9])) return neg_inf();
+        xreal pena = 0;  // apply_generic_priors' own sum, then added to f (priors_calc.cpp:642)
+        for (long i = 0; i < Np; i++) pena = pena + generic_prior_term(params, Np, pp, sw, i, status);
+        return f + pena;
+    }
+    if (prior_class == 0) {  // priors_Kallinger2014_Gaussian: 14 noise parameters, Amax, numax, sigma, mu_numax, omega_numax
+        const double a1 = params[5], a2 = params[6];
+        if (a1 < 0 || a2 < 0) return neg_inf();
+        if (envelope_width_rejects(params[15], params[16])) return neg_inf();
+        const xreal numax = params[15], mu_numax = params[17], omega_numax = params[18];
+        if (numax + mu_numax < 0) return neg_inf();
+        f = f + logP_gaussian(0, xfabs(omega_numax), mu_numax);
+        xreal pena = 0;
+        for (long i = 0; i < Np; i++) pena = pena + generic_prior_term(params, Np, pp, sw, i, status);
+        return f + pena;
+    }
     if (prior_class == 2) {
         const xreal c = ms_global_constraints(params, pl, sw, extra, status);
         if (c != 0) return c;

@@ -31,6 +31,9 @@ EXTRA_ABI += [
     ("tamcmc_inputs_name", C.c_char_p, [_vp, C.c_int]),
     ("tamcmc_inputs_prior_name", C.c_char_p, [_vp, C.c_int]),
     ("tamcmc_inputs_model_name", C.c_char_p, [_vp]),
+    ("tamcmc_io_load_model_simple", C.c_int, [C.c_char_p, C.c_int, C.POINTER(_vp)]),
+    ("tamcmc_inputs_plength", C.c_int, [_vp, _ip, C.c_int]),
+    ("tamcmc_model_id_from_name", C.c_int, [C.c_char_p]),
 ]
 
 
@@ -127,6 +130,27 @@ class AsymptoticInputs(ModelInputs):
         super().__init__(h)
 
 
+class SimpleInputs(ModelInputs):
+    """Gaussian-envelope fit, the "simple matrix" `.model` dialect (Config::read_inputs_prior_Simple_Matrix): model_id 0
+    (model_Kallinger2014_Gaussian) or 1 (model_Harvey_Gaussian), which the file does not name -- it comes from the .cfg.
+    plength_simple: the dialect's own plength (count of each distinct name); plength: the fixed [11] form, {Nparams, 0, ...}."""
+
+    def __init__(self, model_path, model_id):
+        L = _L()
+        h = _vp()
+        _check(L.tamcmc_io_load_model_simple(str(model_path).encode(), int(model_id), C.byref(h)), "load_model_simple")
+        n = L.tamcmc_inputs_plength(h, None, 0)
+        pl = np.zeros(max(n, 1), dtype=np.int32)
+        L.tamcmc_inputs_plength(h, _p(pl, _ip), n)
+        self.plength_simple = pl[:n]
+        super().__init__(h)
+
+
+def model_id_from_name(name):
+    """Config/default/models_ctrl.list: a .cfg's model_fct_name -> model id (-1 when not listed)."""
+    return int(_L().tamcmc_model_id_from_name(str(name).encode()))
+
+
 def star_from_inputs(inp, x, y=None):
     star = Star(inp.model_id, inp.params, inp.plength, x, inp.relax, inp.priors, inp.priors_switch, inp.names, inp.prior_class,
                 inp.extra_priors)
@@ -220,3 +244,12 @@ def init_errors(errors_path, star):
     out = np.zeros(len(idx))
     _check(L.tamcmc_io_init_errors(str(errors_path).encode(), names, _p(vals), len(idx), _p(out)), "init_errors")
     return out
+
+
+def load_simple_star(model_path, data_path, model_id, x_col=0, y_col=1):
+    """`.model` (simple-matrix dialect) + `.data` of a Gaussian-envelope fit -> (Star with prior class 0 or 1 and x, y cut to the file's
+    range, SimpleInputs)."""
+    tab = read_data(data_path)
+    inp = SimpleInputs(model_path, model_id)
+    a, b = select_range(tab, inp.freq_range[0], inp.freq_range[1], x_col)
+    return star_from_inputs(inp, np.ascontiguousarray(tab[a:b, x_col]), np.ascontiguousarray(tab[a:b, y_col])), inp

@@ -273,3 +273,51 @@ def make_c5_star(seed=20240229, nx=200000, nmax=10, dnu=10.0, bias_type=1, model
     # extra_priors (io_asymptotic.cpp:422-431): [smooth switch, smooth coef, |a3/a1| limit, impose_normHnlm, model switch 3 = v4 models]
     extra = np.array([1.0, 2.0, 0.2, 0.0, 3.0, 0, 0, 0, 0, 0])
     return Star(MODEL_RGB_CTE_V4 if cte_width else MODEL_RGB_V4, params, plength, x, relax, pr, sw, names, prior_class=4, extra_priors=extra)
+
+
+# ---- Gaussian-envelope background fits (model ids 0 and 1) ----
+HARVEY_GAUSSIAN_NAMES = ["H1", "tc1", "p1", "H2", "tc2", "p2", "B0", "Amax", "numax", "Gauss_sigma"]
+KALLINGER_GAUSSIAN_NAMES = ["k_Agran", "s_Agran", "k_taugran", "s_taugran", "c_gran", "a1", "a2", "k1", "s1", "c1", "k2", "s2", "c2",
+                            "N0", "Amax", "numax", "Gauss_sigma", "mu_numax", "omega_numax"]
+P_GUG = 7
+
+
+def make_envelope_star(model_id, nx=5400, seed=1, fmax=256.0):
+    """Synthetic Gaussian-envelope star: model_Harvey_Gaussian (id 1, prior class 1; parameters close to the 1161491 fixture) or
+    model_Kallinger2014_Gaussian (id 0, prior class 0; the Kallinger et al. 2014 scaling coefficients at numax = 100 muHz).
+    nx bins of a regular grid over (0, fmax]; the spectrum y is left to the caller (set_spectrum_from_model)."""
+    rng = np.random.default_rng(seed)
+    x = np.arange(1, nx + 1, dtype=np.float64) * (fmax / nx)
+    if model_id == 1:
+        names = HARVEY_GAUSSIAN_NAMES
+        params = np.array([5154.9, 76.3, 4.0, 2796.4, 29.6, 2.5, 191.4, 3255.1, 52.0, 16.7])
+        params[[0, 3, 6, 7]] *= 1.0 + 0.02 * rng.standard_normal(4)
+        relax = np.array([1, 1, 0, 1, 1, 0, 1, 1, 1, 1], dtype=np.int32)
+        rules = {
+            "H1": (P_JEFF, lambda v: (0.1 * v, 100.0 * v)), "tc1": (P_UNIFORM, lambda v: (5.0, 500.0)),
+            "H2": (P_JEFF, lambda v: (0.1 * v, 100.0 * v)), "tc2": (P_UNIFORM, lambda v: (0.0, 100.0)),
+            "B0": (P_UNIFORM, lambda v: (0.0, 10.0 * v)), "Amax": (P_JEFF, lambda v: (0.1 * v, 100.0 * v)),
+            "numax": (P_UNIFORM, lambda v: (0.6 * v, 1.4 * v)), "Gauss_sigma": (P_UNIFORM, lambda v: (0.3 * v, 3.0 * v)),
+        }
+    elif model_id == 0:
+        names = KALLINGER_GAUSSIAN_NAMES
+        numax = 100.0
+        a = 3382.0 * numax ** -0.609
+        params = np.array([3382.0, -0.609, 0.1, 1.0, 4.0, a, 0.9 * a, 0.317, 0.970, 4.0, 0.948, 0.992, 4.0, 5.0, 400.0, numax, 12.0,
+                           0.0, 1.0])
+        params[[5, 6, 13, 14]] *= 1.0 + 0.02 * rng.standard_normal(4)
+        relax = np.zeros(params.size, dtype=np.int32)
+        relax[[5, 6, 13, 14, 15, 16]] = 1
+        rules = {
+            "a1": (P_UNIFORM, lambda v: (0.0, 5.0 * v)), "a2": (P_UNIFORM, lambda v: (0.0, 5.0 * v)),
+            "N0": (P_UNIFORM, lambda v: (0.0, 10.0 * v)), "Amax": (P_JEFF, lambda v: (0.1 * v, 100.0 * v)),
+            "numax": (P_UNIFORM, lambda v: (0.6 * v, 1.4 * v)), "Gauss_sigma": (P_UNIFORM, lambda v: (0.3 * v, 3.0 * v)),
+        }
+    else:
+        raise ValueError("model_id must be 0 (Kallinger2014_Gaussian) or 1 (Harvey_Gaussian)")
+    pr, sw = _prior_tables(names, params, relax, rules)
+    plength = np.zeros(11, dtype=np.int32)
+    plength[0] = params.size  # the fixed [11] form: one block (these models do not read plength)
+    star = Star(model_id, params, plength, x, relax, pr, sw, list(names), prior_class=model_id)
+    star.plength_simple = np.ones(params.size, dtype=np.int32)
+    return star
