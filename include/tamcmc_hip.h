@@ -82,6 +82,13 @@ extern "C" {
                                         longer fits the GPU's resident waves -- lockstep kernels elsewhere), 1 = lockstep kernels only,
                                         2 = fused with one launch per iteration, 3 = fused with two chain groups whenever there are
                                         8 chains or more.  Same chains bit for bit in every case (tests/test_gpu_sampler.py); default 0 */
+#define TAMCMC_OPT_QUICK_DECIDE 8    /* a test facility of the fused step.  Its likelihood tiles learn the outcome of the previous
+                                        iteration's Metropolis test and swap from a threshold comparison with a 1e-11 safety margin and
+                                        fall back to the exact evaluation when the comparison is too close (about once in 1e5 tests).
+                                        0 = that (default); 1 = the margin is +inf: every margin test answers "undecided" and every
+                                        test takes the fallback (records of proposals that cannot be accepted keep deciding without
+                                        sums).  Same chains bit for bit, several times slower; tamcmc_sampler_get_info counts the
+                                        fallbacks taken (TAMCMC_INFO_QUICK_FALLBACKS) */
 #define TAMCMC_OPT_ARMM_DENSE_SCAN 7 /* red-giant pre-step: 1 = walk the solver's whole grid like the reference (solver_mm.cpp:340-377)
                                         instead of the pole-structured scan that finds the same cells; default 0 */
 

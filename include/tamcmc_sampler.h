@@ -95,7 +95,14 @@ int64_t tamcmc_sampler_nvars(const tamcmc_sampler *s);
 #define TAMCMC_INFO_CHAIN_GROUPS 6
 #define TAMCMC_INFO_ITER_FUSED 7      /* iterations run as fused launches since creation */
 #define TAMCMC_INFO_ITER_LOCKSTEP 8   /* iterations run by the lockstep kernels (adaptation, long vectors, red giants, Langevin) */
-#define TAMCMC_SAMPLER_INFO_N 9
+#define TAMCMC_INFO_FUSED_STRETCHES 9  /* fused stretches since creation; the first launch of a stretch starts from settled chains, so
+                                          the likelihood tiles have decided Nchains * (ITER_FUSED - FUSED_STRETCHES) tests */
+#define TAMCMC_INFO_QUICK_FALLBACKS 10 /* of those, the tests for which the tiles' decision shortcut answered "undecided" and the exact
+                                          evaluation ran instead (counted by the chain's first tile) */
+#define TAMCMC_INFO_QUICK_SURE 11      /* of those, the tests of chains outside the swap pair whose record said "cannot be accepted"
+                                          (proposal outside a prior's support): decided without sums, also under
+                                          TAMCMC_OPT_QUICK_DECIDE = 1, where FALLBACKS + SURE = the number of tile tests */
+#define TAMCMC_SAMPLER_INFO_N 12
 int tamcmc_sampler_get_info(const tamcmc_sampler *s, int64_t *info, int32_t n);
 
 /* Advances all chains by n_iter iterations.  Optional outputs, one record per iteration after the swap step

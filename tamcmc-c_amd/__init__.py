@@ -24,6 +24,7 @@ MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4 = 27   # constant-width variant of 25, same path
 MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4 = 25  # batched device path only (tamcmc_hip_loglike_params_batch): needs the ARMM pre-step
 PRECISION_STRICT, PRECISION_FAST, PRECISION_FAST_DIRECT = 0, 1, 2
 OPT_PRECISION, OPT_TIMING, OPT_BINS_PER_THREAD, OPT_WORKGROUP, OPT_FD_WINDOWED, OPT_STEP_SCHEME, OPT_ARMM_DENSE_SCAN = 1, 2, 3, 4, 5, 6, 7
+OPT_QUICK_DECIDE = 8  # test facility: 1 = the fused step's decision shortcut always falls back to the exact evaluation
 
 
 class Multiplet(C.Structure):

@@ -67,6 +67,7 @@ struct tamcmc_hip_ctx {
     int fd_windowed = 1;  // FAST modes: finite differences through delta tables (changed multiplets on their windows only)
     int step_scheme = 0;  // device sampler: 0 = fused steps where possible (one or two launches per iteration: automatic), 1 = lockstep kernels only,
                           // 2 = fused, always one launch per iteration, 3 = fused, two chain groups whenever the chain count allows
+    int quick_decide = 0; // device sampler, fused step (a test facility): 1 = every margin test of the decision shortcut answers "undecided"
     int armm_dense = 0;   // red-giant pre-step: 1 = dense grid walk
     // resident spectrum
     int64_t Nx = 0;

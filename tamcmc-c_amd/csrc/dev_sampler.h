@@ -81,8 +81,9 @@ class DevSampler {
     int download_gradient(double *grad, double *grad_prior);
     int download_last_proposal(double *vars_prop, double *grad_prop);  // use_drift: what the last iteration tested  // use_drift: [C x Nv] gradient the engine holds for the chains' positions
     // [0] Nvars [1] Nparams [2] adaptation workspace in LDS (1) / global scratch (0) [3] fused step available [4] chain groups
-    // [5] iterations run fused [6] iterations run by the lockstep kernels [7] chains
-    void info(long out[8]) const;
+    // [5] iterations run fused [6] iterations run by the lockstep kernels [7] chains [8] fused stretches
+    // [9] quick_decide fallbacks taken by the likelihood tiles [10] tile tests decided from a kind-2 record (outside a swap pair)
+    void info(long out[11]) const;
     int run(long it0, long n_iter, const char *learn, double *samples, double *stats);
     int run_mala(long it0, long n_iter, const char *learn, double *samples, double *stats);  // use_drift = 1 (dev_mala_impl.h)
 };

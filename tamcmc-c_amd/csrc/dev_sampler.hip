@@ -783,6 +783,11 @@ struct FusedArgs {
     double *quick;                     // [2][C][QN] that iteration's MH and swap tests as thresholds on the sums of the partials (quick_decide)
     double *part;                      // [2][C][ntiles][2] the tiles' partial sums of that iteration
     double *lz;                        // [2][C][Nv] L z of chain m for the iteration of that parity, computed one launch ahead
+    // quick_decide's safety margin (1e-11; +inf under TAMCMC_OPT_QUICK_DECIDE = 1: every margin test answers "undecided") and what the
+    // tests read back (tamcmc_sampler_get_info): [0] fallbacks to decide() taken by the likelihood tiles, counted by each chain's tile 0;
+    // [1] tests of chains outside a swap pair that those tiles decided from a kind-2 record, counted by the chain's commit workgroup
+    double qmargin;
+    unsigned long long *qcount;
 };
 
 constexpr int QN = 8;  // doubles per quick record (quick_decide): S*, kind, -pl/T, logL held, [pair's first chain: log u_swap, TA/TB - 1, TB/TA - 1], slot
@@ -901,8 +906,9 @@ __device__ __attribute__((noinline)) int decide(const DevSamplerArgs *ga, const 
 // the record of iteration it-1 (update_buffer_params / update_buffer_stat_criteria, MALA.cpp:708-710), the move flags and counters -- and,
 // for the launch of iteration it+1, the slot, prior and status of the chain's proposal at iteration `it`.  With ST_COMMIT alone (after the
 // last iteration of a stretch) the launch holds nothing else.
+// (tiles: the launch holds the likelihood tiles of iteration `it`, which decided iteration it-1 themselves -- quick_decide)
 __device__ __attribute__((noinline)) void commit_chain(const DevSamplerArgs *ga, const FusedArgs *gf, int m, long it, int q, int settled, long rec,
-                                                       Decided *dec) {
+                                                       int tiles, Decided *dec) {
     const int slot = decide(ga, gf, m, it, q, settled, dec);
     __syncthreads();
     const ConstArgs &a = *(const ConstArgs *)uniform_ptr(ga);
@@ -928,6 +934,9 @@ __device__ __attribute__((noinline)) void commit_chain(const DevSamplerArgs *ga,
             Sstar = -((log(u) - lp + cur) * Tm) / (double)a.pl;
             if (isfinite(Sstar)) ok = 1;
         } else if (u > 0.0) ok = 2;  // r = 0 whatever the sums (mh_outcome): rejected
+        // (In practice kind 2 means "outside a prior's support".  A failed table cannot come from a proposal inside the priors for the
+        // models that run fused: set_imin_imax fails only on a NaN width or splitting, or on a non-positive truncation parameter -- a
+        // fixed input -- and a proposal is a finite sum of finite numbers.  tests/test_gpu_sampler.py counts the kind-2 tests it covers.)
         w[0] = Sstar; w[1] = ok; w[2] = -(double)a.pl / Tm; w[3] = settled ? a.logL_cur[q * C + m] : d.o.logL;
         double lus = 0, k1 = 0, k2 = 0;
         if (is_swap_iter(a, it)) {  // the swap test of iteration `it`, left by the pair's first chain: u <= exp(LA TA/TB + LB TB/TA - LA - LB)
@@ -971,6 +980,8 @@ __device__ __attribute__((noinline)) void commit_chain(const DevSamplerArgs *ga,
             double *r = a.stats + ((size_t)rec * C + m) * 3;
             r[0] = d.o.logL; r[1] = d.o.logPr; r[2] = d.o.logPost;
         }
+        // (diagnostic: the one kind of record that this chain's tiles decided without decide() whatever the margin)
+        if (tiles && d.swap_first < 0 && f.quick[((size_t)(q ^ 1) * C + m) * QN + 1] == 2.0) atomicAdd(f.qcount + 1, 1ull);
     }
 }
 
@@ -979,7 +990,7 @@ __device__ __attribute__((noinline)) void commit_chain(const DevSamplerArgs *ga,
 // comparison of S = the sum of launch it-1's partials with a threshold S* that the previous launch's commit workgroup has left
 // (commit_chain: everything in the test but S is known one launch earlier).  S is summed here in any order; when it is further from S*
 // than every rounding involved could explain (summation: n eps sum|v| ~ 2e-14 sum|v|; the threshold and the test's own exp / division:
-// a few eps of |S*|; the margin is 1e-11 of those magnitudes) the outcome is the exact test's.  The swap test of iteration it-1's pair
+// a few eps of |S*|; the margin, FusedArgs::qmargin, is 1e-11 of those magnitudes) the outcome is the exact test's.  The swap test of iteration it-1's pair
 // (pairA, named by the host: the same Philox draw) is taken the same way: log u against LA (TA/TB - 1) + LB (TB/TA - 1) with the
 // post-test likelihoods from the approximate sums.  Otherwise -- about once in 1e5 tests -- decide() evaluates everything as written.
 // A decide() of ~2000 dependent instructions costs a lone wave 5 us at the head of the launch's longest chains; this one ~0.5 us.
@@ -1015,11 +1026,12 @@ __device__ __attribute__((noinline)) int quick_decide_leaf(const DevSamplerArgs 
     }
     const double St0 = __shfl(rec, 0, 64), ok0 = __shfl(rec, 1, 64);
     const int ps0 = (int)__shfl(rec, 7, 64);
+    const double mg = f.qmargin;
     // kind 1: threshold test; kind 2: the proposal cannot be accepted (outside a prior's support, or its table failed: r = 0 and u > 0) --
     // its partial sums may be anything (an empty slot's tiles are skipped)
     int acc0 = 0;
     if (ok0 == 2.0) { s0 = 0; a0 = 0; }
-    else if (ok0 > 0 && fabs(s0 - St0) > 1e-11 * (a0 + fabs(St0))) acc0 = s0 < St0 ? 1 : 0;  // (a NaN sum fails the comparison)
+    else if (ok0 > 0 && fabs(s0 - St0) > mg * (a0 + fabs(St0))) acc0 = s0 < St0 ? 1 : 0;  // (a NaN sum fails the comparison)
     else return -1;
     Decided d;
     d.swap_first = -1; d.swapped = 0; d.src_par = p; d.r = 0;
@@ -1030,12 +1042,13 @@ __device__ __attribute__((noinline)) int quick_decide_leaf(const DevSamplerArgs 
         const int ps1 = (int)__shfl(rec, QN + 7, 64);
         int acc1 = 0;
         if (ok1 == 2.0) { s1 = 0; a1 = 0; }
-        else if (ok1 > 0 && fabs(s1 - St1) > 1e-11 * (a1 + fabs(St1))) acc1 = s1 < St1 ? 1 : 0;
+        else if (ok1 > 0 && fabs(s1 - St1) > mg * (a1 + fabs(St1))) acc1 = s1 < St1 ? 1 : 0;
         else return -1;
         const double c0 = __shfl(rec, 2, 64), c1 = __shfl(rec, QN + 2, 64);
         const double LA = acc0 ? c0 * s0 : __shfl(rec, 3, 64), LB = acc1 ? c1 * s1 : __shfl(rec, QN + 3, 64);
         const double lus = __shfl(rec, 4, 64), x = LA * __shfl(rec, 5, 64) + LB * __shfl(rec, 6, 64);
-        if (!(fabs(x - lus) > 1e-11 * (fabs(c0) * a0 + fabs(c1) * a1 + fabs(LA) + fabs(LB)))) return -1;
+        // (written as !(>): a NaN on either side -- a NaN sum, or inf * 0 under the forced margin -- is undecided)
+        if (!(fabs(x - lus) > mg * (fabs(c0) * a0 + fabs(c1) * a1 + fabs(LA) + fabs(LB)))) return -1;
         const int swapped = x > lus ? 1 : 0;
         const int A = pairA, B = pairA + 1;
         d.swap_first = A; d.swapped = swapped;
@@ -1058,6 +1071,18 @@ __device__ __forceinline__ int quick_decide(const DevSamplerArgs *ga, const Fuse
     return s >= 0 ? s : decide(ga, gf, m, it, q, 0, out);
 }
 
+// The same for a likelihood tile, which wants the slot alone.  Its fallback is counted (FusedArgs::qcount[0]) once per chain and
+// iteration, by the chain's tile 0, inside the cold branch: the decided path is quick_decide's, instruction for instruction.
+__device__ __attribute__((noinline)) int decide_counted(const DevSamplerArgs *ga, const FusedArgs *gf, int m, long it, int q, int tile) {
+    if (tile == 0 && (threadIdx.x & 63) == 0) atomicAdd(((const ConstFused *)uniform_ptr(gf))->qcount, 1ull);
+    return decide(ga, gf, m, it, q, 0, nullptr);
+}
+__device__ __forceinline__ int quick_slot(const DevSamplerArgs *ga, const FusedArgs *gf, int m, long it, int q, int settled, int pairA, int tile) {
+    if (settled) return decide(ga, gf, m, it, q, 1, nullptr);
+    const int s = quick_decide_leaf(ga, gf, m, q, pairA, nullptr);
+    return s >= 0 ? s : decide_counted(ga, gf, m, it, q, tile);
+}
+
 // Hook of the likelihood tiles of the fused step: evaluation b = chain first + b.
 struct StepTiles {
     const DevSamplerArgs *ga;
@@ -1065,7 +1090,7 @@ struct StepTiles {
     long it;
     int q, first, settled, pairA;
     static constexpr bool coherent_partials = false;
-    __device__ __forceinline__ int slot(const LoglikeArgs &, int b) const { return quick_decide(ga, gf, first + b, it, q, settled, pairA, nullptr); }
+    __device__ __forceinline__ int slot(const LoglikeArgs &, int b, int tile) const { return quick_slot(ga, gf, first + b, it, q, settled, pairA, tile); }
     __device__ __forceinline__ void operator()(int, int, int) const {}
 };
 
@@ -1304,7 +1329,7 @@ struct StepCtl {
     }                                                                                                                        \
     if (id < c.nbr + c.nlz) {                                                                                                \
         const int e = id - c.nbr, k = e - (c.nlz - c.cnt);                                                                   \
-        if (k >= 0 && (c.flags & ST_COMMIT)) commit_chain(c.ga, c.gf, c.first + k, c.it, c.q, settled, c.rec, &s_dec);       \
+        if (k >= 0 && (c.flags & ST_COMMIT)) commit_chain(c.ga, c.gf, c.first + k, c.it, c.q, settled, c.rec, c.flags & ST_L, &s_dec); \
         else if (e < c.n_lz_live)                                                                                            \
             lz_block(c.ga, c.gf, c.it_lz + e / c.cnt, (c.q_lz ^ (e / c.cnt)) & 1, c.first + e % c.cnt, (unsigned char *)&lds);  \
         return;                                                                                                              \
@@ -1385,6 +1410,7 @@ struct DevSampler::Impl {
     long armed_it = -1;
     int armed_q = 0;
     long it_fused = 0, it_lockstep = 0;  // iterations run by each scheme since creation (tamcmc_sampler_get_info)
+    long n_stretch = 0;                  // fused stretches since creation (the first launch of each has nothing to decide)
     int mala_chol_lds = -1;
 
     hipEvent_t gev[8][2];  // fused step with two chain groups: event pairs around sampled launches of the second group (on its stream)
@@ -1613,6 +1639,9 @@ int DevSampler::init(tamcmc_hip_ctx *c, const DevSamplerInit &in) {
         DCHK(I.dalloc(&f.mults, 3 * NS * (size_t)a.desc.per + 1)); DCHK(I.dalloc(&f.pairs, 6 * NS)); DCHK(I.dalloc(&f.nh, 3 * NS)); DCHK(I.dalloc(&f.nn, 3 * NS));
         DCHK(I.dalloc(&f.noise, 3 * NS * (size_t)a.desc.stride));
         DCHK(I.dalloc(&f.slot, 2 * C)); DCHK(I.dalloc(&f.prop_logPr, 2 * C)); DCHK(I.dalloc(&f.prop_st, 2 * C)); DCHK(I.dalloc(&f.quick, 2 * C * QN)); DCHK(I.dalloc(&f.lz, 2 * C * Nv));
+        DCHK(I.dalloc(&f.qcount, 2));
+        DCHK(hipMemsetAsync(f.qcount, 0, 2 * sizeof(unsigned long long), st));
+        f.qmargin = 1e-11;
         DCHK(hipMemsetAsync(f.nn, 0, 3 * NS * sizeof(int), st));
         DCHK(hipMemsetAsync(f.cand_stP, 0, 6 * NS * sizeof(int), st));
         DCHK(hipMemsetAsync(f.cand_rej, 0, 3 * NS * sizeof(int), st));
@@ -1651,8 +1680,11 @@ int DevSampler::download_last_proposal(double *vars_prop, double *grad_prop) {
     return TAMCMC_OK;
 }
 
-void DevSampler::info(long out[8]) const {
+void DevSampler::info(long out[11]) const {
     const Impl &I = *impl;
+    unsigned long long qc[2] = {0, 0};  // (every entry point returns with the sampler's streams idle)
+    if (I.f.qcount && hipSetDevice(I.ctx->device) == hipSuccess) (void)hipMemcpy(qc, I.f.qcount, sizeof qc, hipMemcpyDeviceToHost);
+    out[8] = I.n_stretch; out[9] = (long)qc[0]; out[10] = (long)qc[1];
     out[0] = I.a.Nv; out[1] = I.a.desc.Np;
     out[2] = I.use_drift ? I.mala_chol_lds : I.a.chol_in_lds;
     out[3] = (I.fused_ok && !I.use_drift) ? 1 : 0;
@@ -1820,6 +1852,7 @@ int DevSampler::run(long it0, long n_iter, const char *learn, double *samples, d
     a.tile_bins = tb;
     a.bg = nullptr;
     const bool use_fused = I.fused_ok && c->step_scheme != 1 && c->wgs == 64 && (c->K == 4 || c->K == 8 || c->K == 16);
+    I.f.qmargin = c->quick_decide == 1 ? (double)INFINITY : 1e-11;  // (TAMCMC_OPT_QUICK_DECIDE: a test facility)
     const size_t NS = (size_t)I.f.NS;
     I.f.bg = nullptr;
     if (c->precision == TAMCMC_PRECISION_FAST) {
@@ -2007,6 +2040,7 @@ int DevSampler::run(long it0, long n_iter, const char *learn, double *samples, d
         const int ntiles_pad = ((a.ntiles + 7) / 8) * 8;
         const long len = ib - ia;
         I.it_fused += len;
+        I.n_stretch += 1;
         int q = P;
         StepCtl sc{};
         {  // device-memory image of the two argument blocks (re-uploaded only when a pointer or size changed since the last run)

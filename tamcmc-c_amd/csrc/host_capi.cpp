@@ -169,13 +169,16 @@ int tamcmc_sampler_get_info(const tamcmc_sampler *s, int64_t *info, int32_t n) {
     v[TAMCMC_INFO_NCHAINS] = s->cfg.MALA.Nchains;
     v[TAMCMC_INFO_ADAPT_IN_LDS] = -1;
     if (s->dev) {
-        long d[8];
+        long d[11];
         s->dev->info(d);
         v[TAMCMC_INFO_ADAPT_IN_LDS] = d[2];
         v[TAMCMC_INFO_FUSED_AVAILABLE] = d[3];
         v[TAMCMC_INFO_CHAIN_GROUPS] = d[4];
         v[TAMCMC_INFO_ITER_FUSED] = d[5];
         v[TAMCMC_INFO_ITER_LOCKSTEP] = d[6];
+        v[TAMCMC_INFO_FUSED_STRETCHES] = d[8];
+        v[TAMCMC_INFO_QUICK_FALLBACKS] = d[9];
+        v[TAMCMC_INFO_QUICK_SURE] = d[10];
     }
     for (int32_t i = 0; i < n && i < TAMCMC_SAMPLER_INFO_N; i++) info[i] = v[i];
     return TAMCMC_OK;

@@ -690,7 +690,7 @@ __device__ __forceinline__ void tile_compute(const LoglikeArgs &a, const int til
 // after its partial sums are written.
 struct NoTail {
     static constexpr bool coherent_partials = false;
-    __device__ __forceinline__ int slot(const LoglikeArgs &, int b) const { return b; }  // evaluation b reads table slot b
+    __device__ __forceinline__ int slot(const LoglikeArgs &, int b, int /*tile*/) const { return b; }  // evaluation b reads table slot b
     __device__ __forceinline__ void operator()(int /*b*/, int /*tile*/, int /*slot*/) const {}
 };
 
@@ -723,7 +723,7 @@ __device__ __forceinline__ void loglike_tile(const LoglikeArgs &a, const int id,
     if (tile >= a.ntiles) return;  // padding workgroup: leaves before any barrier
     tile += a.tile_rot;
     if (tile >= a.ntiles) tile -= a.ntiles;
-    const int sb = tail.slot(a, b);
+    const int sb = tail.slot(a, b, tile);
     // everything the slot index leads to is requested at once (one memory round trip, not one per dependent step): the table's range,
     // the noise row's lengths; a.per > 0 (device-built tables in fixed-size slots): the range begins at (slot0 + sb) * per
     const int nn = a.nnoise[sb], nh = a.nharvey[sb];

@@ -27,6 +27,29 @@ def _constrained_star(pkg, oracle, synth, seed=5, nx=11000):
     return star
 
 
+def _check_scheme_counters(info, nchains, scheme, forced):
+    """What Sampler.info() must say after a run under TAMCMC_OPT_STEP_SCHEME = scheme (1: lockstep kernels only) and, forced,
+    TAMCMC_OPT_QUICK_DECIDE = 1.  Every launch of a fused stretch but the first decides the previous iteration's test for each chain in
+    its likelihood tiles: nchains * (iter_fused - fused_stretches) tile tests.  Forced, each of them takes the fallback to decide()
+    except the tests outside the swap pair whose record says "cannot be accepted" (kind 2: decided without sums in both settings), and
+    those are counted as well (quick_sure): the two counts add up exactly.  By default the fallback is rare: the margin is 1e-11 of
+    magnitudes ~1e5 around a threshold whose distance to the sum is spread over ~1 (log u), i.e. ~1e-5 per test --
+    asserted a hundred times above that, at 1e-3 of the tests plus one.  Returns the number of tile tests."""
+    if scheme == 1:
+        assert info["iter_fused"] == 0 and info["fused_stretches"] == 0 and info["quick_fallbacks"] == 0 and info["quick_sure"] == 0, info
+        return 0
+    assert info["fused_available"] == 1 and info["iter_fused"] > 0 and info["fused_stretches"] > 0, info
+    tests = nchains * (info["iter_fused"] - info["fused_stretches"])
+    assert tests > 0
+    if forced:
+        assert info["quick_fallbacks"] + info["quick_sure"] == tests, (info, tests)
+        assert info["quick_fallbacks"] > 0
+    else:
+        print("\ndefault margin: %d fallbacks in %d tile tests (%d of kind 2)" % (info["quick_fallbacks"], tests, info["quick_sure"]))
+        assert info["quick_fallbacks"] * 1000 <= tests + 1000, (info, tests)
+    return tests
+
+
 @pytest.fixture()
 def ctx(pkg):
     c = pkg.HipContext(0, precision=pkg.PRECISION_FAST)
@@ -75,34 +98,146 @@ def test_fused_steps_are_bitwise_the_lockstep_chain(pkg, oracle, synth, ctx, nch
     Same random numbers, same arithmetic, same summation orders: samples, statistics, swap counts and the final state must be
     IDENTICAL, whatever the mixing period and wherever the adaptation window falls.  From 8 chains on the fused iteration is TWO
     launches, one per chain group on its own stream (the groups drift apart and meet again at every swap whose pair straddles them):
-    still the same chains."""
+    still the same chains.
+    Third run: the fused steps with TAMCMC_OPT_QUICK_DECIDE = 1 -- every likelihood tile takes the shortcut's fallback, decide() called
+    from a tile workgroup with no output record, which by default runs about once in 1e5 tests.  Still the same chains, and the
+    counters prove which path each run took (_check_scheme_counters)."""
     star = _star_with_data(pkg, oracle, synth)
     ctx.set_spectrum(star.x, star.y)
     Nt = learn if learn else (10**9, 10**9 + 1)
     kw = dict(nchains=nchains, lambda_temp=1.4 if nchains < 10 else 1.2, seed=23, Nt_learn=Nt, periods_learn=(2,), dN_mixing=dN_mixing)
-    out = []
-    for scheme in (1, 0 if nchains < 8 else 3):   # 3: two chain groups even on this small star (automatic: only when a launch outgrows the GPU)
+    out, infos = [], []
+    fused_scheme = 0 if nchains < 8 else 3        # 3: two chain groups even on this small star (automatic: only when a launch outgrows the GPU)
+    n1 = 150 if nchains < 8 else 700
+    for scheme, forced in ((1, 0), (fused_scheme, 0), (fused_scheme, 1)):
         ctx.set_option(pkg.OPT_STEP_SCHEME, scheme)
+        ctx.set_option(pkg.OPT_QUICK_DECIDE, forced)
         d = pkg.Sampler(ctx, star, engine="device", **kw)
-        s1, t1 = d.run(150 if nchains < 8 else 700, stats=True)
+        s1, t1 = d.run(n1, stats=True)
         s2, t2 = d.run(61, stats=True)   # a second call continues the same chains
         s3, t3 = d.run(2, stats=True)    # shorter than a fused stretch: lockstep either way
         out.append((np.concatenate([s1, s2, s3]), np.concatenate([t1, t2, t3]), d.state()))
+        infos.append(d.info())
         d.close()
     ctx.set_option(pkg.OPT_STEP_SCHEME, 0)
+    ctx.set_option(pkg.OPT_QUICK_DECIDE, 0)
+    for k, (scheme, forced) in enumerate(((1, 0), (fused_scheme, 0), (fused_scheme, 1))):
+        _check_scheme_counters(infos[k], nchains, scheme, forced)
+        assert infos[k]["iter_fused"] + infos[k]["iter_lockstep"] == n1 + 63
+    assert infos[1]["iter_fused"] == infos[2]["iter_fused"] and infos[1]["fused_stretches"] == infos[2]["fused_stretches"]
+    assert infos[1]["quick_sure"] == infos[2]["quick_sure"]          # (the same records either way)
+    if not learn:    # no adaptation: each of the first two calls is one fused stretch
+        assert infos[1]["iter_fused"] == n1 + 61 and infos[1]["fused_stretches"] == 2 and infos[1]["iter_lockstep"] == 2
     smp, st, state = out[1]
     assert np.array_equal(smp, out[0][0])
     assert np.array_equal(st, out[0][1])
+    assert np.array_equal(out[2][0], out[0][0])
+    assert np.array_equal(out[2][1], out[0][1])
     for k in ("iteration", "swaps", "swap_attempts", "accepted0"):
         assert state[k] == out[0][2][k], k
+        assert out[2][2][k] == out[0][2][k], k
     for k in ("vars", "logL", "logPrior", "logPost", "Pmove", "sigma"):
         assert np.array_equal(state[k], out[0][2][k]), k
+        assert np.array_equal(out[2][2][k], out[0][2][k]), k
     assert (out[0][0][:, 0] != out[0][0][0, 0]).any()
     if dN_mixing:
         assert 0 < state["swaps"] <= state["swap_attempts"]
 
 
+def _star_with_close_prior_edges(pkg, oracle, synth):
+    """The C2 slice with the lower edge of two frequencies' uniform priors moved to 0.02 muHz below the start point: the proposal's
+    standard deviation on a frequency is ~0.026 muHz x T^0.1 (default_errors: 0.05; sigma = 2.38^2 T^0.2 / 21), so a fifth of the draws
+    of each of the two puts the proposal outside the prior's support (log-prior -inf, move probability 0) -- hot chains included."""
+    star = _star_with_data(pkg, oracle, synth)
+    fidx = [i for i, nm in enumerate(star.names) if nm == "Frequency_l"]
+    for i in (fidx[2], fidx[5]):                     # the two multiplets inside this cut of the spectrum (l = 1 and l = 2)
+        star.priors[0, i] = star.params[i] - 0.02
+    return star
+
+
+@pytest.mark.parametrize("nchains", [7, 9])
+def test_zero_probability_proposals_inside_fused_launches(pkg, oracle, synth, ctx, nchains):
+    """Proposals that cannot be accepted (outside a prior's support) leave a kind-2 record for the next launch's decision shortcut: the
+    tiles decide such a test without sums (quick_decide_leaf, ok = 2), alone or as either chain of the swap pair, the swap accepted or
+    refused.  First the events are COUNTED from an independent run -- the lockstep kernels one iteration at a time, Pmove == 0 with the
+    pair's entries put back where the swap took them from -- and the counts asserted, so that the comparison below is known to cover
+    them; then one fused call of N iterations (7 chains: one launch per iteration; 9: two chain groups) with the default margin and
+    with the forced fallback must be the lockstep chain bit for bit, and the device's own count of kind-2 tile decisions must be the
+    independent one."""
+    star = _star_with_close_prior_edges(pkg, oracle, synth)
+    ctx.set_spectrum(star.x, star.y)
+    N = 300
+    kw = dict(nchains=nchains, lambda_temp=1.4, seed=31, Nt_learn=(10**9, 10**9 + 1), periods_learn=(2,), dN_mixing=1, engine="device")
+    ctx.set_option(pkg.OPT_STEP_SCHEME, 1)
+    d = pkg.Sampler(ctx, star, **kw)
+    smp, stt, zero, pairA, swapped = [], [], np.zeros((N, nchains), dtype=bool), np.full(N, -1), np.zeros(N, dtype=bool)
+    swaps = 0
+    for k in range(N):
+        a, b = d.run(1, stats=True)
+        smp.append(a); stt.append(b)
+        st = d.state()
+        pm = st["Pmove"].copy()
+        if k > 0:                                    # dN_mixing = 1: a swap step at every iteration but the first
+            A = d.draws(k)[3]
+            pairA[k] = A
+            swapped[k] = st["swaps"] != swaps
+            swaps = st["swaps"]
+            if swapped[k]:
+                pm[[A, A + 1]] = pm[[A + 1, A]]      # Pmove travels with the rows (MALA.cpp:437, :447)
+        zero[k] = pm == 0.0
+    ref = (np.concatenate(smp), np.concatenate(stt), d.state())
+    assert d.info()["iter_fused"] == 0
+    d.close()
+    # the tests the tiles of a fused call of N iterations decide: iterations 0 .. N-2 (launch k+1 decides iteration k; the last one is the
+    # closing launch's, which has no tiles)
+    alone = a_cnt = b_cnt = both = acc = ref_ = 0
+    for k in range(N - 1):
+        A = pairA[k]
+        for m in range(nchains):
+            if zero[k, m] and not (A >= 0 and m in (A, A + 1)):
+                alone += 1
+        if A >= 0:
+            za, zb = zero[k, A], zero[k, A + 1]
+            a_cnt += int(za); b_cnt += int(zb); both += int(za and zb)
+            if za or zb:
+                acc += int(swapped[k]); ref_ += int(not swapped[k])
+    print("\nkind-2 events in %d iterations x %d chains: alone %d, as chain A %d, as chain B %d, both %d; swaps with one: accepted %d, refused %d"
+          % (N - 1, nchains, alone, a_cnt, b_cnt, both, acc, ref_))
+    assert alone >= 20 and a_cnt >= 5 and b_cnt >= 5 and both >= 1 and acc >= 1 and ref_ >= 1
+    assert (~zero).sum() > N and (ref[0][1:, 0] != ref[0][:-1, 0]).any()           # ... and the chains still move
+    scheme = 0 if nchains < 8 else 3
+    for forced in (0, 1):
+        ctx.set_option(pkg.OPT_STEP_SCHEME, scheme)
+        ctx.set_option(pkg.OPT_QUICK_DECIDE, forced)
+        d = pkg.Sampler(ctx, star, **kw)
+        a, b = d.run(N, stats=True)
+        info, state = d.info(), d.state()
+        d.close()
+        ctx.set_option(pkg.OPT_STEP_SCHEME, 0)
+        ctx.set_option(pkg.OPT_QUICK_DECIDE, 0)
+        assert info["iter_fused"] == N and info["fused_stretches"] == 1 and info["iter_lockstep"] == 0, info
+        tests = _check_scheme_counters(info, nchains, scheme, forced)
+        assert tests == nchains * (N - 1) and info["quick_sure"] == alone, (info, alone)
+        if forced:
+            assert info["quick_fallbacks"] == tests - alone
+        assert np.array_equal(a, ref[0]) and np.array_equal(b, ref[1]), forced
+        for key in ("iteration", "swaps", "swap_attempts", "accepted0"):
+            assert state[key] == ref[2][key], key
+        for key in ("vars", "logL", "logPrior", "logPost", "Pmove"):
+            assert np.array_equal(state[key], ref[2][key]), key
+
+
 def test_records_written_into_pinned_buffers_equal_the_copied_ones(pkg, oracle, synth, ctx):
+    _pinned_buffers_equal_the_copied_ones(pkg, oracle, synth, ctx, 0)
+
+
+def test_records_written_into_pinned_buffers_equal_the_copied_ones_with_forced_fallback(pkg, oracle, synth, ctx):
+    """The same with TAMCMC_OPT_QUICK_DECIDE = 1 (two samplers share the context whose option it is): every tile test of both samplers
+    takes the fallback of the decision shortcut."""
+    _pinned_buffers_equal_the_copied_ones(pkg, oracle, synth, ctx, 1)
+
+
+def _pinned_buffers_equal_the_copied_ones(pkg, oracle, synth, ctx, forced):
     """run(out=...) with page-locked arrays (pinned_empty / tamcmc_hip_host_alloc): the settle step writes every iteration's sample and
     statistics straight into the caller's memory; with ordinary arrays the records are kept on the device and copied at the end of the
     call.  Same records either way, through learning (lockstep kernels) and fused stretches, samples only / statistics only included.
@@ -110,6 +245,7 @@ def test_records_written_into_pinned_buffers_equal_the_copied_ones(pkg, oracle, 
     to the next (the prepared candidates of the next iteration) must not live in the context's scratch memory."""
     star = _star_with_data(pkg, oracle, synth)
     ctx.set_spectrum(star.x, star.y)
+    ctx.set_option(pkg.OPT_QUICK_DECIDE, forced)
     kw = dict(nchains=9, lambda_temp=1.4, seed=4, Nt_learn=(20, 60), periods_learn=(1,), dN_mixing=1, engine="device")
     a, b = pkg.Sampler(ctx, star, **kw), pkg.Sampler(ctx, star, **kw)
     for n in (100, 37, 5):
@@ -128,7 +264,10 @@ def test_records_written_into_pinned_buffers_equal_the_copied_ones(pkg, oracle, 
     _, t = b.run(50, record=False, stats=True)
     assert np.array_equal(pt, t)
     assert np.array_equal(a.state()["vars"], b.state()["vars"])
+    for s in (a, b):
+        _check_scheme_counters(s.info(), 9, 0, forced)
     a.close(); b.close()
+    ctx.set_option(pkg.OPT_QUICK_DECIDE, 0)
 
 
 def test_device_engine_learning_adapts(pkg, oracle, synth, ctx):
@@ -326,6 +465,15 @@ def test_checkpoint_and_resume(pkg, oracle, synth, ctx, tmp_path, engine):
 
 @pytest.mark.parametrize("engine,groups", [("device", 1), ("device", 2), ("host", 0)])
 def test_packed_stars_reproduce_their_solo_runs(pkg, oracle, synth, engine, groups):
+    _packed_stars_reproduce_their_solo_runs(pkg, oracle, synth, engine, groups, 0)
+
+
+def test_packed_stars_reproduce_their_solo_runs_with_forced_fallback(pkg, oracle, synth):
+    """The packed run with TAMCMC_OPT_QUICK_DECIDE = 1 on every star's context, against solo runs with the default margin."""
+    _packed_stars_reproduce_their_solo_runs(pkg, oracle, synth, "device", 2, 1)
+
+
+def _packed_stars_reproduce_their_solo_runs(pkg, oracle, synth, engine, groups, forced):
     """Several stars co-resident on one GPU (tamcmc_sampler_run_packed: one context and one host thread per star).  The stars share
     nothing, so each one's samples and statistics must be bit-identical to a run on its own -- with adaptation running, for both
     engines, and with the chains of a star in one or two stream groups."""
@@ -335,11 +483,12 @@ def test_packed_stars_reproduce_their_solo_runs(pkg, oracle, synth, engine, grou
         st = _star_with_data(pkg, oracle, synth, nx=nx, seed=seed)
         stars.append(st)
 
-    def build():
+    def build(quick=0):
         cs, ss = [], []
         for k, st in enumerate(stars):
             c = pkg.HipContext(0, precision=pkg.PRECISION_FAST)
             c.set_spectrum(st.x, st.y)
+            c.set_option(pkg.OPT_QUICK_DECIDE, quick)
             cs.append(c)
             ss.append(pkg.Sampler(c, st, engine=engine, nchains=4 + 2 * k, lambda_temp=1.5, seed=40 + k, Nt_learn=(20, 160), periods_learn=(1,),
                                   chain_groups=groups))
@@ -352,9 +501,11 @@ def test_packed_stars_reproduce_their_solo_runs(pkg, oracle, synth, engine, grou
         s.close()
     for c in cs:
         c.close()
-    cs, ss = build()
+    cs, ss = build(forced)
     smp, stt = S.run_packed(ss, n, stats=True)
     for k in range(len(stars)):
+        if engine == "device":
+            _check_scheme_counters(ss[k].info(), 4 + 2 * k, 0, forced)
         assert np.array_equal(smp[k], solo[k][0]) and np.array_equal(stt[k], solo[k][1]), k
         assert ss[k].state()["iteration"] == n and (smp[k][1:, 0] != smp[k][:-1, 0]).any()
     with pytest.raises(pkg.TamcmcError):

@@ -284,3 +284,57 @@ def test_langevin_at_the_headline_shape(pkg, oracle, c3):
     assert np.all(np.isfinite(stt)) and 0.1 < acc[0] < 0.9 and 0.1 < acc.mean() < 0.9, acc
     assert all((smp[1:, m] != smp[:-1, m]).any() for m in range(NCH))
     s.close()
+
+
+@pytest.mark.parametrize("forced", [0, 1])
+@pytest.mark.parametrize("nch,scheme", [(7, 0), (9, 3)])
+def test_fused_walk_equals_the_oracle_walk_on_a_local_slice(pkg, oracle, synth, nch, scheme, forced):
+    """The fused step against the oracle DIRECTLY: ONE run(N) of the device engine, executed as fused launches (info()), against N
+    iterations of oracle.sampler_iteration fed with the engine's draws and frozen proposal law, each iteration starting from the
+    oracle's OWN previous state (nothing of the device's run enters the walk but the start point).  C2 slice, 7 chains (one launch per
+    iteration) and 9 chains (two chain groups, scheme 3), default margin and forced fallback of the decision shortcut.  Every iteration
+    and every chain is compared, at this file's stated tolerances: positions 1e-11 relative / 1e-13 absolute, tempered logL and
+    logPost 2e-11, prior 1e-12.  (A comparator within rounding of its move probability would send the two walks apart: ~1e-6 per
+    test; the seeds are fixed and the walk is deterministic.)"""
+    N, lam = 60, 1.4
+    star = synth.make_c2_star(nx=4000)
+    _, m0 = oracle.call_model(star.model_id, star.params, star.plength, star.x)
+    star.set_spectrum_from_model(m0, 5)
+    ctx = pkg.HipContext(0, precision=pkg.PRECISION_FAST)
+    ctx.set_spectrum(star.x, star.y)
+    ctx.set_option(pkg.OPT_STEP_SCHEME, scheme)
+    ctx.set_option(pkg.OPT_QUICK_DECIDE, forced)
+    s = pkg.Sampler(ctx, star, nchains=nch, lambda_temp=lam, engine="device", seed=19, Nt_learn=(10**9, 10**9 + 1), periods_learn=(1,),
+                    dN_mixing=1, c0=2.0)
+    T = lam ** np.arange(nch)
+    st0 = s.state()
+    init_logL = st0["logL"].copy()
+    law = s.proposal_law()
+    params = np.tile(star.params, (nch, 1))
+    params[:, star.index_to_relax] = st0["vars"]
+    state = dict(params=params, vars=st0["vars"], logL=st0["logL"], logPrior=st0["logPrior"], logPost=st0["logPost"])
+    draws = [s.draws(k) for k in range(N)]
+    smp, stt = s.run(N, stats=True)
+    info = s.info()
+    s.close(); ctx.close()
+    assert info["iter_fused"] == N and info["iter_lockstep"] == 0 and info["fused_stretches"] == 1, info
+    assert info["chain_groups"] == (2 if nch >= 8 else 1)
+    tests = nch * (N - 1)
+    if forced:
+        assert info["quick_fallbacks"] + info["quick_sure"] == tests and info["quick_fallbacks"] > 0, info
+    else:
+        assert info["quick_fallbacks"] * 1000 <= tests + 1000, info
+    moved = swapped = 0
+    for k in range(N):
+        z, u, u_swap, ind_A = draws[k]
+        exp, _, rc = oracle.sampler_iteration(star, star.y, T, init_logL, state, law, i=k, z=z, u_mh=u, learn=False, do_swap=k != 0, ind_A=ind_A,
+                                              u_swap=u_swap, c0=2.0)
+        assert rc == 0
+        assert np.allclose(smp[k], exp["vars"], rtol=1e-11, atol=1e-13), (k, np.max(np.abs(smp[k] - exp["vars"])))
+        assert np.allclose(stt[k][:, 0], exp["logL"], rtol=2e-11, atol=0), k
+        assert np.allclose(stt[k][:, 1], exp["logPrior"], rtol=1e-12, atol=1e-12), k
+        assert np.allclose(stt[k][:, 2], exp["logPost"], rtol=2e-11, atol=0), k
+        moved += int(exp["moved"].sum())
+        swapped += int(exp["swapped"])
+        state = {key: exp[key] for key in ("params", "vars", "logL", "logPrior", "logPost")}
+    assert moved >= N and 0 < swapped < N - 1, (moved, swapped)      # the walk held accepted and refused moves and swaps
