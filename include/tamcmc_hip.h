@@ -54,6 +54,29 @@ extern "C" {
 #define TAMCMC_MODEL_HARVEY_GAUSSIAN 1        /* model_Harvey_Gaussian, models.cpp:5674; prior class 1 */
 #define TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC 3 /* model_MS_Global_a1etaa3_HarveyLike_Classic, models.cpp:1943 */
 #define TAMCMC_MODEL_MS_LOCAL_BASIC 11           /* model_MS_local_basic, models.cpp:3012 */
+/* Height-per-m models (ids 12, 13, 14): no stellar inclination; the heights of the 2l+1 components are read from the parameter
+ * vector, mirrored around m = 0.  Frequencies, widths and windows are those of id 3 (ids 12, 13) / of id 11 with a1 = |p[o_split]|
+ * and no sqrt(a1) cos/sin form (id 14).  With o_inc = the first index of the "inclination" block (after the noise block):
+ *   id 12  Ninc = 9 ratios shared by all orders: hv = H_l * |p[o_inc + {1,0,1}]|, |p[o_inc + {4,3,2,3,4}]|, |p[o_inc + {8,7,6,5,6,7,8}]|
+ *          for l = 1, 2, 3 with H_l exactly as in id 3 (visibilities included) -- with ratios = amplitude_ratio(l, i) the rows are
+ *          bit-identical to id 3's.  Prior: io_MS_Global with extra_priors[8] = 1 (the three sums of ratios in [0, 1 + 1e-10]).
+ *   id 13  one height per (n, l, |m|), no visibilities: hv = |p[o_inc + (l+1) n + |m|] / (pi W)| (|p[..]| without do_amp).
+ *   id 14  local: heights of l = 0 at p[n], of l >= 1 at p[off_l + (l+1) n + |m|] with off_l = Nfl0 + .. + Nfl(l-1);
+ *          plength[0] = Nfl0 + 2 Nfl1 + 3 Nfl2 + 4 Nfl3, Nharvey = 0.  Prior: io_local unchanged (no normalisation: the block of
+ *          priors_local that would apply one is commented out in the reference, priors_calc.cpp:575-613).
+ * Known quirk, kept from the reference (ids 13 and 14): the loaders lay the l >= 1 heights out l-major -- degree l starts after
+ * the 2 Nfl1 (+ 3 Nfl2) entries of the lower degrees -- but the model functions count every degree's offset (l+1) n from the START of
+ * the block (id 13, models.cpp:2427-2477) or from Nfl0 + Nfl1 (+ Nfl2) (id 14, models.cpp:3261-3316), so for l >= 2 they read inside the
+ * l = 1 heights.  The table builders read what the reference's model functions read; a star with l <= 1 is unaffected.
+ * For l >= 1 the amplitude conversion divides in double by the double-rounded product pi W (an Eigen vector divided by a scalar),
+ * where l = 0 and ids 3, 11 divide in long double.
+ * The reference's `params.model` side output (outparams = true) does not exist for these three: it exits there.  The row-writing
+ * entries are unaffected.  Id 13 has no prior the reference can run (its loader sets extra_priors[8] = 2, where priors_MS_Global
+ * exits): it is served at the model level only -- tables, likelihood, gradient -- and has no loader or sampler.
+ * A layout whose height block is shorter than what the model function reads is refused with TAMCMC_ERR_BAD_MODEL. */
+#define TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC_V2 12 /* model_MS_Global_a1etaa3_HarveyLike_Classic_v2, models.cpp:2128 */
+#define TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC_V3 13 /* model_MS_Global_a1etaa3_HarveyLike_Classic_v3, models.cpp:2338 */
+#define TAMCMC_MODEL_MS_LOCAL_HNLM 14                /* model_MS_local_Hnlm, models.cpp:3198 */
 #define TAMCMC_MODEL_MS_GLOBAL_AJ 23             /* model_MS_Global_aj_HarveyLike, models.cpp:1195 */
 #define TAMCMC_MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4 25 /* model_RGB_asympt_aj_AppWidth_HarveyLike_v4, models.cpp:4684: only through
                                                     tamcmc_hip_loglike_params_batch (its table needs the device pre-step:
@@ -140,7 +163,7 @@ int tamcmc_hip_loglike_batch(tamcmc_hip_ctx *ctx, int B, const tamcmc_multiplet 
 
 /* Table builders (Lorentzian models only; ids 0 and 1 have no multiplets: TAMCMC_ERR_BAD_MODEL): the host-side scalar part of the model functions
  *   VectorXd model_X(params, params_length, x, outparams)   tamcmc/headers/models.h:21-57
- * (parameter unpack, amplitude_ratio, lin_interpol, eta0, set_imin_imax) for ids 3, 11, 23.
+ * (parameter unpack, amplitude_ratio, lin_interpol, eta0, set_imin_imax) for ids 3, 11, 12, 13, 14, 23.
  * Writes at most max_mults rows; *n_mults = rows needed.  noise_abs receives |noise params| (plength[8] values). */
 int tamcmc_build_mode_table(int model_id, const double *params, const int32_t *plength, const double *x, int64_t Nx,
                             tamcmc_multiplet *mults, int max_mults, int *n_mults, double *noise_abs,

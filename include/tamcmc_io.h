@@ -13,8 +13,18 @@
  *   Config::convert_priors_names_to_switch config.cpp:725-752 (ids of Config/default/primepriors_ctrl.list)
  * Also read: the global (ids 3, 23), red-giant (ids 25, 27) and simple-matrix (Gaussian-envelope fits, ids 0 and 1) dialects and the
  * .cfg files (below).
- * Not covered yet (TAMCMC_IO_ERR_UNSUPPORTED): model_MS_local_Hnlm, the other global variants (a1n/a1l/a2a3/ajAlm/AppWidth/
- * Classic_v2,v3), the ajfit dialect.
+ * Height-per-m models: model_MS_local_Hnlm (id 14; io_local.cpp:387, :592-596, :768, :807, :1014-1054, :1076-1078) through the local
+ * loader -- one height per (n, l, m >= 0), start value h_l[n] * amplitude_ratio(l, Inclination)[l + m], the inclination slot emptied,
+ * extra_priors[3] = 2, plength[0] = Nfl0 + 2 Nfl1 + 3 Nfl2 + 4 Nfl3 -- and model_MS_Global_a1etaa3_HarveyLike_Classic_v2 (id 12;
+ * io_ms_global.cpp:429-433, :1234-1248) through the global loader: the Classic path with the inclination block replaced by nine
+ * ratios "Inc:H<l>,<m>", Uniform on [0, 1], start value amplitude_ratio(l, Inclination)[l + m], extra_priors[8] = 1.
+ * Kept from the reference for Hnlm: the height keyword's prior parameters are taken from its FIRST number (the basic model skips
+ * it), so such a file reads `Height  Jeffreys  <hmin>  <hmax>`; every height of l >= 1 is free whatever its mode line says.
+ * Deviation: the l = 0 heights are rewritten at position 0 of the height block; the reference uses a position variable left over from
+ * the keyword handled before (io_local.cpp:809), which is 0 for the keyword order of its own example files.
+ * Not covered (TAMCMC_IO_ERR_UNSUPPORTED): model_MS_Global_a1etaa3_HarveyLike_Classic_v3 (id 13) -- no prior the reference can run:
+ * its loader sets extra_priors[8] = 2, where priors_MS_Global exits -- the other global variants (a1n/a1l/a2a3/ajAlm/AppWidth),
+ * the ajfit dialect.
  * Parity: the reference cannot be run here and ships no expected Input_Data dump: "parity unpinned"; tests pin the
  * result against values derived by hand from the shipped file with the rules cited above.
  */

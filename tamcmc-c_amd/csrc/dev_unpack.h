@@ -286,7 +286,9 @@ __device__ inline void wg_unpack(const ModelDesc &d, const double *s_params, con
     if (live) {
         if (!vis_done) visibilities_stage(u, tid, WgSync());  // workgroup-uniform
         UPSTAMP(1);
-        if (rows_done) {  // rows already written with hv = H (wg_log_prior, early_rows): the visibilities are known now
+        const bool hnlm = mt::has_component_heights(d.model_id);  // heights per component, no visibility product (ids 13, 14)
+        if (rows_done && hnlm) {
+        } else if (rows_done) {  // rows already written with hv = H (wg_log_prior, early_rows): the visibilities are known now
             for (int e = tid; e < per * 7; e += nt) {
                 tamcmc_multiplet *r = &T.mults[(size_t)slot * per + e / 7];
                 const int k = e % 7, l = r->l;
@@ -298,6 +300,11 @@ __device__ inline void wg_unpack(const ModelDesc &d, const double *s_params, con
                                                    &T.mults[(size_t)slot * per + idx], false, pst);
                 if (st) *u.status = st;
             }
+        // (a row this lane wrote itself, or one written before the barrier that ended wg_log_prior.  A row whose window failed is
+        // passed too: the pass takes degree and position from the index, stays inside the row and the parameter vector, and the
+        // slot is discarded below through *u.status)
+        if (hnlm)
+            for (int idx = tid; idx < per; idx += nt) mt::component_heights(d.model_id, s_params, *S, idx, &T.mults[(size_t)slot * per + idx]);
         for (int i = tid; i < S->L.Nnoise; i += nt) T.noise[(size_t)slot * d.stride + i] = fabs(s_params[S->L.o_noise + i]);
         if (T.bg && !rows_done)  // (with early rows wg_log_prior's term lanes already did it)
             wg_bg_tiles(d, s_params, S, slot, T, (nt > 64) ? 64 : 0, (nt > 64) ? nt - 64 : nt);  // beside the first wave's multiplet rows

@@ -21,6 +21,7 @@
 
 #include "../../include/tamcmc_hip.h"
 #include "../../include/tamcmc_io.h"
+#include "mode_tables_impl.h"  // amplitude_ratio(), header-only: this file links without the table builders
 
 namespace {
 
@@ -304,7 +305,8 @@ int build_local(const ModelFile &mf, double resol, tamcmc_inputs &out) {
         }
     }
     if (model.empty()) return fail(TAMCMC_IO_ERR_SYNTAX, "the .model file has no model_fullname");
-    if (model != "model_MS_local_basic") return fail(TAMCMC_IO_ERR_UNSUPPORTED, "model not covered by this loader: " + model);
+    const bool hnlm = (model == "model_MS_local_Hnlm");  // one height per (n, l, m >= 0) instead of the inclination
+    if (model != "model_MS_local_basic" && !hnlm) return fail(TAMCMC_IO_ERR_UNSUPPORTED, "model not covered by this loader: " + model);
 
     // ---- per degree: the eigen-table rows of that degree, each matched to ONE mode line within 1e-2 (:416-502), then only
     //      the modes strictly inside the slice's range (:504-557)
@@ -337,9 +339,15 @@ int build_local(const ModelFile &mf, double resol, tamcmc_inputs &out) {
     const std::string hname = do_amp ? "Amplitude_l" : "Height_l";
 
     Block height, width, freq, snlm, inc, noise;
-    height.init(Ntot); width.init(Ntot); freq.init(Ntot); snlm.init(6); inc.init(1); noise.init(1);
+    const int Nheights = hnlm ? Nf[0] + 2 * Nf[1] + 3 * Nf[2] + 4 * Nf[3] : Ntot;  // (:592-593, :1076-1078)
+    height.init(Nheights); width.init(Ntot); freq.init(Ntot); snlm.init(6); inc.init(1); noise.init(1);
+    // Hnlm: only the l=0 heights are filled here; those of l >= 1 wait for the inclination (:592-596)
+    const std::vector<double> h0(h.begin(), h.begin() + Nf[0]);
+    const std::vector<int> rh0(rh.begin(), rh.begin() + Nf[0]);
+    int pos_prior_height = -1;  // Hnlm: index of the height keyword among the common parameters (:350, :769, :808)
     // ---- defaults (:586-673): Jeffreys on heights and widths, GUG on frequencies
-    height.fill_vect(h, rh, hname, "Jeffreys", {Hmin, Hmax, -9999., -9999.}, 0, 0);
+    if (hnlm) height.fill_vect(h0, rh0, hname, "Jeffreys", {Hmin, Hmax, -9999., -9999.}, 0, 0);
+    else height.fill_vect(h, rh, hname, "Jeffreys", {Hmin, Hmax, -9999., -9999.}, 0, 0);
     const std::vector<double> wdef = {resol, mf.dnu > 0 ? mf.dnu / 3. : 20., -9999., -9999.};
     width.fill_vect(w, rw, "Width_l", "Jeffreys", wdef, 0, 0);
     for (int i = 0; i < Ntot; i++) {
@@ -351,20 +359,23 @@ int build_local(const ModelFile &mf, double resol, tamcmc_inputs &out) {
     bool cosi = false, sini = false;
     auto no_auto = [&](const Common &c) { return c.prior == "Fix_Auto" ? fail(TAMCMC_IO_ERR_SYNTAX, c.name + " cannot be Fix_Auto") : 0; };
     // ---- the keywords of "# Controls and priors for common parameters" (:707-969)
-    for (const auto &c : mf.common) {
+    for (size_t ic = 0; ic < mf.common.size(); ic++) {
+        const Common &c = mf.common[ic];
         const std::string &n = c.name;
         if (n == "trunc_c") {
             if (c.prior != "Fix") return fail(TAMCMC_IO_ERR_SYNTAX, "trunc_c must be 'Fix'");
             trunc_c = c.v[0];
         } else if (n == "height" || n == "Height" || n == "amplitude" || n == "Amplitude") {
+            if (hnlm) pos_prior_height = (int)ic;
             if (c.prior == "Fix_Auto") {  // Jeffreys between input/Y and input*X per mode (:748-802)
                 const bool amp = (n == "amplitude" || n == "Amplitude");
-                for (int i = 0; i < Ntot; i++) {
+                for (int i = 0; i < (hnlm ? Nf[0] : Ntot); i++) {
                     const double s = amp ? (double)(pi * mf.dnu / 3.) : 1.0;
                     height.fill(hname, rh[(size_t)i] ? "Jeffreys" : "Fix", h[(size_t)i],
                                 {s * h[(size_t)i] / c.v[0], s * h[(size_t)i] * c.v[1], -9999., -9999.}, i, 0);
                 }
-            } else height.fill_vect(h, rh, hname, c.prior, c.v, 0, 1);
+            } else if (hnlm) height.fill_vect(h0, rh0, hname, c.prior, c.v, 0, 0);  // prior parameters from the FIRST number (:809)
+            else height.fill_vect(h, rh, hname, c.prior, c.v, 0, 1);
         } else if (n == "width" || n == "Width") {
             if (c.prior == "Fix_Auto") width.fill_vect(w, rw, "Width_l", "Jeffreys", wdef, 0, 0);
             else width.fill_vect(w, rw, "Width_l", c.prior, c.v, 0, 0);  // (i0 = 0 for free widths, :845-852)
@@ -399,7 +410,27 @@ int build_local(const ModelFile &mf, double resol, tamcmc_inputs &out) {
         // freq_smoothness, Visibility_l*: irrelevant for a local fit (:709-720); model_fullname etc. handled above
     }
     if (cosi != sini) return fail(TAMCMC_IO_ERR_SYNTAX, "sqrt(splitting_a1).cosi and .sini must both appear");
-    if (!cosi) {
+    if (hnlm) {
+        // the heights of l >= 1 (:1014-1054): h_l[n] * amplitude_ratio(l, inclination of the file)[l + m] for m = 0..l, l-major after
+        // the l=0 heights; the height keyword's prior (parameters from its first number) or Jeffreys [Hmin, Hmax]; free whatever
+        // the mode line's flag.  The inclination slot is emptied, Splitting_a1 keeps slot 0 of the splitting block.
+        if (cosi) return fail(TAMCMC_IO_ERR_UNSUPPORTED, "model_MS_local_Hnlm takes Splitting_a1 and Inclination (its heights are set from them, :978-1054)");
+        const double inc0 = inc.inputs[0];
+        std::vector<double> pv = {Hmin, Hmax, -9999., -9999.};
+        std::string pname = "Jeffreys";
+        if (pos_prior_height > 0) { pv = mf.common[(size_t)pos_prior_height].v; pname = mf.common[(size_t)pos_prior_height].prior; }
+        int ind = Nf[0], src = Nf[0];
+        for (int el = 1; el <= lmax; el++) {
+            double V[7];
+            tamcmc::mt::amplitude_ratio(el, inc0, V);
+            for (int en = 0; en < Nf[el]; en++, src++)
+                for (int em = 0; em <= el; em++)
+                    height.fill("H(" + std::to_string(en) + "," + std::to_string(el) + "," + std::to_string(em) + ")", pname,
+                                h[(size_t)src] * V[el + em], pv, ind++, 0);
+        }
+        extra[3] = 2;  // (:1052; priors_local's normalisation block is commented out: nothing reads it)
+        inc.fill("Empty", "Fix", 0, inc.prior_col(0), 0, 1);  // :1022
+    } else if (!cosi) {
         // Splitting_a1 + Inclination given: the model fits sqrt(a1) cos i and sqrt(a1) sin i (:978-1003)
         const double a1 = snlm.inputs[0], ang = (double)(inc.inputs[0] * pi / 180.);
         if (inc.prior_names[0] == "Fix" && snlm.prior_names[0] == "Fix") {
@@ -414,8 +445,10 @@ int build_local(const ModelFile &mf, double resol, tamcmc_inputs &out) {
         if (snlm.inputs[3] < 1e-2) snlm.inputs[3] = 1e-2;
         if (snlm.inputs[4] < 1e-2) snlm.inputs[4] = 1e-2;
     }
-    inc.fill("Empty", "Fix", 0, inc.prior_col(0), 0, 1);    // :1004 / :1057
-    snlm.fill("Empty", "Fix", 0, snlm.prior_col(0), 0, 1);  // :1005 / :1059
+    if (!hnlm) {
+        inc.fill("Empty", "Fix", 0, inc.prior_col(0), 0, 1);    // :1004 / :1057
+        snlm.fill("Empty", "Fix", 0, snlm.prior_col(0), 0, 1);  // :1005 / :1059
+    }
     // ---- local white-noise level (set_noise_params_local, :1178-1238): mean of the background at the two ends of the range
     {
         std::vector<double> np;
@@ -434,7 +467,7 @@ int build_local(const ModelFile &mf, double resol, tamcmc_inputs &out) {
     }
     // ---- assemble (:1067-1118): heights, frequencies, splitting block, widths, noise, inclination, trunc_c, do_amp
     int *pl = out.plength;
-    pl[0] = Ntot; pl[1] = 0; pl[2] = Nf[0]; pl[3] = Nf[1]; pl[4] = Nf[2]; pl[5] = Nf[3];
+    pl[0] = Nheights; pl[1] = 0; pl[2] = Nf[0]; pl[3] = Nf[1]; pl[4] = Nf[2]; pl[5] = Nf[3];
     pl[6] = 6; pl[7] = Ntot; pl[8] = 1; pl[9] = 1; pl[10] = 2;
     int N = 0;
     for (int k = 0; k < 11; k++) N += pl[k];
@@ -461,7 +494,7 @@ int build_local(const ModelFile &mf, double resol, tamcmc_inputs &out) {
     for (int k = 0; k < 10; k++) out.extra[k] = k < 4 ? extra[k] : 0.0;
     out.range[0] = mf.range[0]; out.range[1] = mf.range[1];
     out.dnu = mf.dnu; out.c_l = mf.c_l;
-    out.model_id = TAMCMC_MODEL_MS_LOCAL_BASIC;
+    out.model_id = hnlm ? TAMCMC_MODEL_MS_LOCAL_HNLM : TAMCMC_MODEL_MS_LOCAL_BASIC;
     out.prior_class = 3;  // io_local, Config/default/priors_ctrl.list
     out.model_name = model;
     for (int i = 0; i < N; i++)
@@ -513,7 +546,11 @@ int build_global(const ModelFile &mf, double resol, tamcmc_inputs &out) {
         }
     }
     if (model.empty()) return fail(TAMCMC_IO_ERR_SYNTAX, "the .model file has no model_fullname");
-    const bool aj = (model == "model_MS_Global_aj_HarveyLike"), classic = (model == "model_MS_Global_a1etaa3_HarveyLike_Classic");
+    const bool v2 = (model == "model_MS_Global_a1etaa3_HarveyLike_Classic_v2");  // the Classic path, nine height ratios for the inclination
+    const bool aj = (model == "model_MS_Global_aj_HarveyLike"), classic = (model == "model_MS_Global_a1etaa3_HarveyLike_Classic") || v2;
+    if (model == "model_MS_Global_a1etaa3_HarveyLike_Classic_v3")
+        return fail(TAMCMC_IO_ERR_UNSUPPORTED, "model_MS_Global_a1etaa3_HarveyLike_Classic_v3 has no prior the reference can run (its loader "
+                                               "sets extra_priors[8] = 2, where priors_MS_Global exits): use ..._Classic_v2");
     if (!aj && !classic) return fail(TAMCMC_IO_ERR_UNSUPPORTED, "model not covered by this loader: " + model);
     double extra[10] = {1, 2., 1e6, 0.50, 0.20, 0.15, 0.05, 0.05, 0, -1};  // :403-413
     if (aj) extra[9] = 9;                                                    // :494-499
@@ -626,11 +663,23 @@ int build_global(const ModelFile &mf, double resol, tamcmc_inputs &out) {
         inc.fill("Empty", "Fix", 0, inc.prior_col(0), 0, 1);
         snlm.fill("Empty", "Fix", 0, snlm.prior_col(0), 0, 1);
     }
+    if (v2) {  // :1234-1248: the inclination of the file only sets the start values of the nine ratios (slots above lmax stay empty)
+        const double inc0 = inc.inputs[0];
+        inc.init(9);
+        int ind = 0;
+        for (int el = 1; el <= lmax; el++) {
+            double V[7];
+            tamcmc::mt::amplitude_ratio(el, inc0, V);
+            for (int em = 0; em <= el; em++)
+                inc.fill("Inc:H" + std::to_string(el) + "," + std::to_string(em), "Uniform", V[el + em], {0, 1, -9999., -9999.}, ind++, 0);
+        }
+        extra[8] = 1;  // the three sums of ratios stay in [0, 1 + 1e-10] (priors_MS_Global, case 1)
+    }
     fill_noise_global(mf, noise);
     // ---- assemble (:1327-1376): heights, visibilities, frequencies, splitting block, widths, noise, inclination, trunc_c, do_amp
     int *pl = out.plength;
     pl[0] = Nh; pl[1] = lmax; pl[2] = Nf[0]; pl[3] = Nf[1]; pl[4] = Nf[2]; pl[5] = Nf[3];
-    pl[6] = snlm.n; pl[7] = Nh; pl[8] = 10; pl[9] = 1; pl[10] = 2;
+    pl[6] = snlm.n; pl[7] = Nh; pl[8] = 10; pl[9] = inc.n; pl[10] = 2;
     int N = 0;
     for (int k = 0; k < 11; k++) N += pl[k];
     Block &A = out.all;
@@ -657,7 +706,7 @@ int build_global(const ModelFile &mf, double resol, tamcmc_inputs &out) {
     for (int k = 0; k < 10; k++) out.extra[k] = extra[k];
     out.range[0] = mf.range[0]; out.range[1] = mf.range[1];
     out.dnu = mf.dnu; out.c_l = mf.c_l;
-    out.model_id = aj ? TAMCMC_MODEL_MS_GLOBAL_AJ : TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC;
+    out.model_id = aj ? TAMCMC_MODEL_MS_GLOBAL_AJ : (v2 ? TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC_V2 : TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC);
     out.prior_class = 2;  // io_MS_Global, Config/default/priors_ctrl.list
     out.model_name = model;
     for (int i = 0; i < N; i++)

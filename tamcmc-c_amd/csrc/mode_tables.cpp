@@ -71,6 +71,7 @@ int build_mode_table(int model_id, const double *params, const int32_t *plength,
         tamcmc_multiplet *r = (mults && n < max_mults) ? &mults[n] : &scratch;
         const int st = mt::build_multiplet(model_id, T, params, S, i, x[0], x[Nx - 1], Nx, step, r);
         if (st) { *n_mults = n; return st; }
+        if (mt::has_component_heights(model_id)) mt::component_heights(model_id, params, S, i, r);
         n++;
     }
     *n_mults = n;

@@ -11,6 +11,8 @@
 //   model_MS_Global_aj_HarveyLike               tamcmc/sources/models.cpp:1195-1408   (id 23)
 //   model_MS_Global_a1etaa3_HarveyLike_Classic  tamcmc/sources/models.cpp:1943-2121   (id 3)
 //   model_MS_local_basic                        tamcmc/sources/models.cpp:3012-3195   (id 11)
+//   model_MS_Global_a1etaa3_HarveyLike_Classic_v2 / _v3   models.cpp:2128-2330, :2338-2553   (ids 12, 13)
+//   model_MS_local_Hnlm                         tamcmc/sources/models.cpp:3198-3336   (id 14)
 #pragma once
 #include <math.h>
 #include <limits.h>
@@ -319,13 +321,31 @@ TM_HD Layout make_layout(const int32_t *pl) {
     return L;
 }
 
-// number of multiplets a parameter vector of this layout produces (-1: unknown model)
+// the model families by id: n-major global models with the Classic frequency/width rules (ids 3, 12, 13), and the models whose
+// l >= 1 heights are read per component from the parameter vector (ids 13, 14)
+TM_HD bool is_classic_family(int model_id) {
+    return model_id == TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC || model_id == TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC_V2 ||
+           model_id == TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC_V3;
+}
+TM_HD bool has_component_heights(int model_id) {
+    return model_id == TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC_V3 || model_id == TAMCMC_MODEL_MS_LOCAL_HNLM;
+}
+
+// number of multiplets a parameter vector of this layout produces (-1: unknown model, or a height block shorter than what the
+// model function of ids 12, 13, 14 reads)
 TM_HD int count_multiplets(int model_id, const int32_t *pl) {
     switch (model_id) {
+    case TAMCMC_MODEL_MS_LOCAL_HNLM:
+        if (pl[0] < pl[2] + 2 * pl[3] + 3 * pl[4] + 4 * pl[5]) return -1;
+        return pl[2] + pl[3] + pl[4] + pl[5];
     case TAMCMC_MODEL_MS_GLOBAL_AJ:
     case TAMCMC_MODEL_MS_LOCAL_BASIC: return pl[2] + pl[3] + pl[4] + pl[5];
+    case TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC_V2:
+    case TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC_V3:
     case TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC: {
         const int lm = pl[1] < 3 ? pl[1] : 3;
+        if (model_id == TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC_V2 && pl[9] < 9) return -1;
+        if (model_id == TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC_V3 && lm > 0 && pl[9] < (lm + 1) * pl[0]) return -1;
         return pl[0] * (1 + (lm > 0 ? lm : 0));
     }
     default: return -1;
@@ -357,6 +377,15 @@ TM_HD void shared_scalars_base(int model_id, const double *p, const int32_t *pl,
     S.ratios[0][0] = 1.0;
     S.a1 = 0; S.a3 = 0;
     for (int l = 0; l < 4; l++) { S.need_ratio[l] = 0; S.centre[l] = 0.0; }
+    if (model_id == TAMCMC_MODEL_MS_LOCAL_HNLM) {  // models.cpp:3243-3247, :3323
+        S.inc = 0.0;
+        S.a1 = fabs(p[L.o_split]);
+        S.eta0 = p[L.o_split + 1];
+        S.a3 = p[L.o_split + 2];
+        S.asym = p[L.o_split + 5];
+        S.nharvey = 0;
+        return;
+    }
     if (model_id == TAMCMC_MODEL_MS_LOCAL_BASIC) {  // models.cpp:3059-3088
         const xreal pi = 3.141592653589793238462643383279502884L;
         double inc = atan(p[L.o_split + 4] / p[L.o_split + 3]);
@@ -371,12 +400,18 @@ TM_HD void shared_scalars_base(int model_id, const double *p, const int32_t *pl,
         S.nharvey = 0;  // models.cpp:3167
         return;
     }
-    S.inc = p[L.o_inc];
+    const bool from_inc = (model_id == TAMCMC_MODEL_MS_GLOBAL_AJ || model_id == TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC);
+    S.inc = from_inc ? p[L.o_inc] : 0.0;
     for (int l = 1; l <= 3; l++)
         if (L.lmax >= l) {
             S.Vl[l] = fabs(p[L.o_vis + l - 1]);
-            S.need_ratio[l] = 1;
+            S.need_ratio[l] = from_inc ? 1 : 0;
         }
+    if (model_id == TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC_V2) {  // the nine ratios, mirrored around m = 0 (models.cpp:2197-2217)
+        const double *q = p + L.o_inc;
+        for (int l = 1, b = 0; l <= 3; b += l + 1, l++)
+            for (int k = 0; k <= 2 * l; k++) S.ratios[l][k] = fabs(q[b + (k < l ? l - k : k - l)]);
+    }
     S.nharvey = (L.Nnoise - 1) / 3;
     if (model_id == TAMCMC_MODEL_MS_GLOBAL_AJ) {  // models.cpp:1264-1276
         const double *sp = p + L.o_split;
@@ -400,8 +435,9 @@ TM_HD xreal xabs(xreal v) { return v < 0 ? -v : v; }
 
 // ---------- one multiplet by index (reference accumulation order) ----------
 // aj: l-major (all l=0, then l=1, ...) models.cpp:1288-1376; Classic: n-major (l=0..lmax per order) :2026-2085;
-// local: l-major :3096-3159.
+// local: l-major :3096-3159.  Ids 12, 13 follow Classic, id 14 follows local; ids 13, 14 read the heights of l >= 1 per component.
 // defer_ratio: leave hv[m] = H (the caller multiplies by the m-visibilities once they are known: same product, same bits)
+// Ids 13, 14: the caller follows a successful row with component_heights() (below), which writes the heights of its components.
 #if defined(TAMCMC_PROBE) && defined(__HIP_DEVICE_COMPILE__)
 #define BMSTAMP(k) do { if (pst && index == 20) pst[k] = (long)wall_clock64(); } while (0)
 #else
@@ -412,7 +448,8 @@ TM_HD int build_multiplet(int model_id, const PolyTab &T, const double *p, const
     const Layout &L = S.L;
     BMSTAMP(4);
     int l = 0, n = 0;
-    if (model_id == TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC) {
+    const bool classic = is_classic_family(model_id);
+    if (classic) {
         const int per_n = 1 + (L.lmax < 3 ? (L.lmax > 0 ? L.lmax : 0) : 3);
         n = index / per_n;
         l = index % per_n;
@@ -444,7 +481,7 @@ TM_HD int build_multiplet(int model_id, const PolyTab &T, const double *p, const
             for (int j = 1; j <= 6; j++) a[j] = (j <= 2 * l) ? sp[2 * (j - 1)] + sp[2 * (j - 1) + 1] * (f * 1e-3) : 0.0;
         }
         f_s = a[1];
-    } else if (model_id == TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC) {
+    } else if (classic) {
         const xreal pi = 3.141592653589793238462643383279502884L;
         const double *fl0 = p + L.o_f[0], *Wl0 = p + L.o_width;
         if (l == 0) {
@@ -459,7 +496,7 @@ TM_HD int build_multiplet(int model_id, const PolyTab &T, const double *p, const
             else H = fabs(p[n] * S.Vl[l]);
         }
         f_s = S.a1;
-    } else {  // local basic
+    } else {  // local basic, local Hnlm
         const xreal pi = 3.141592653589793238462643383279502884L;
         int off = 0;
         for (int k = 0; k < l; k++) off += L.Nfl[k];
@@ -496,6 +533,41 @@ TM_HD int build_multiplet(int model_id, const PolyTab &T, const double *p, const
     }
     BMSTAMP(7);
     return TAMCMC_OK;
+}
+
+// ids 13, 14, l >= 1: the heights of the components come from the parameter vector.  A pass of its own over the finished row (the width
+// is read back from it; degree and position in the block follow from the index alone), called by whoever called
+// build_multiplet() -- the host loop right after it, the device in a loop of its own after the rows (dev_unpack.h) -- so that the
+// rows of every other model are built by exactly the code above, within the same registers.  It overwrites every component of the
+// row (what build_multiplet left there, H times a ratio of 0, is not used); the device skips the deferred visibility product for
+// these ids (wg_unpack), so nothing touches the heights after this pass.
+// The amplitude conversion is an Eigen vector divided by the scalar pi*W: the long double product rounded to double, then a
+// double division.  Where the block starts: models.cpp:2427, :2445, :2465 (id 13: every degree from the START of the inclination
+// block) and :3275, :3288, :3303 (id 14: from Nfl0, Nfl0 + Nfl1, Nfl0 + Nfl1 + Nfl2) -- see tamcmc_hip.h.
+TM_HD void component_heights(int model_id, const double *p, const Shared &S, int index, tamcmc_multiplet *r) {
+    const Layout &L = S.L;
+    // degree and position from the index alone (a row whose window failed holds nothing to read back: l <= 3 keeps every access
+    // inside the row and, with the layout check of count_multiplets, inside the parameter vector)
+    int l = 0, hbase;
+    if (model_id == TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC_V3) {
+        const int per_n = 1 + (L.lmax < 3 ? (L.lmax > 0 ? L.lmax : 0) : 3);
+        l = index % per_n;
+        hbase = L.o_inc + (l + 1) * (index / per_n);
+    } else {
+        int rem = index, off = 0;
+        while (l < 3 && rem >= L.Nfl[l]) { rem -= L.Nfl[l]; off += L.Nfl[l]; l++; }
+        hbase = off + (l + 1) * rem;
+    }
+    if (l == 0) return;
+    const xreal pi = 3.141592653589793238462643383279502884L;
+    const double piW = (double)(pi * r->gamma);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+    for (int k = 0; k <= 2 * l; k++) {
+        const double v = p[hbase + (k < l ? l - k : k - l)];
+        r->hv[k] = S.do_amp ? fabs(v / piW) : fabs(v);
+    }
 }
 
 }  // namespace mt

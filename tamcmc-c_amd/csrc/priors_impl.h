@@ -121,6 +121,24 @@ TM_HD double second_difference(const double *y, long n, long i) {
     return y[i + 1] - 2. * y[i] + y[i - 1];
 }
 
+// ---- impose_normHnlm == 1 (extra_priors[8], model_MS_Global_a1etaa3_HarveyLike_Classic_v2; priors_calc.cpp:223-243) ----
+// Three logP_uniform(0, 1 + 1e-10, sum) terms on the ratio sums V(l,0) + 2 V(l,1) + .. + 2 V(l,l) of the nine parameters of the
+// inclination block, for ANY lmax: the slots of the degrees above lmax are "Empty"/"Fix" with value 0 (initialise_param,
+// io_models.cpp:253-274), their sum is 0, inside the support, so all three constants -ln(1 + 1e-10) are always added.  Split like the
+// rest of this prior: a sum outside the support is a hard constraint (-inf), the constant is an additive term.  (The reference adds
+// -inf to f and goes on; a vector it also rejects for another reason gives -inf either way.)  The 1e-10 is there because
+// amplitude_ratio() sums to 1 only to rounding.  Only the default (Classic) branch of the model_index switch applies it.
+TM_HD bool ms_global_norm_active(const double *extra) {
+    const int model_index = (int)extra[9];
+    return model_index < 0 || model_index > 9;
+}
+TM_HD double ms_global_norm_sum(const double *q, int l) {  // q = first parameter of the inclination block; double, as written there
+    if (l == 1) return q[0] + 2 * q[1];
+    if (l == 2) return q[2] + 2 * q[3] + 2 * q[4];
+    return q[5] + 2 * q[6] + 2 * q[7] + 2 * q[8];
+}
+TM_HD xreal ms_global_norm_term() { return xlog(xfabs((xreal)(1. + 1e-10) - (xreal)0)); }  // minus one term's value
+
 // ---- priors_MS_Global split into: hard constraints (-inf or 0) and a list of additive terms ----
 // hard constraints: visibilities >= 0, |aj/a1| limits (model_index 9), Harvey parameters >= 0.
 // The checks are independent: check number t0, t0+stride, ... are evaluated (host: t0=0, stride=1 = all of them in the
@@ -182,14 +200,21 @@ TM_HD xreal ms_global_constraints(const double *params, const int *pl, const int
     case 0: case 1: case 2: case 3: case 4: case 5: case 6: case 7: case 8:
         if (status) *status = TAMCMC_ERR_BAD_MODEL;  // families without a table builder in this build
         return neg_inf();
-    default:  // Classic models (priors_calc.cpp:230-262)
-        if (impose_normHnlm != 0) {
+    default:  // Classic models (priors_calc.cpp:223-249): 1 = the ratio sums of Classic_v2 (below), 2 = the reference exits
+        if ((impose_normHnlm != 0 && impose_normHnlm != 1) || (impose_normHnlm == 1 && pl[9] < 9)) {  // (1 reads nine ratios)
             if (status) *status = TAMCMC_ERR_BAD_MODEL;
             return neg_inf();
         }
         break;
     }
-    if (t0 != 0) return 0;  // the three noise checks belong to slice 0
+    if (t0 != 0) return 0;  // the ratio sums and the three noise checks belong to slice 0
+    if (impose_normHnlm == 1 && ms_global_norm_active(extra)) {  // priors_calc.cpp:226-243: a sum outside [0, 1 + 1e-10] is -inf
+        const double *q = params + Nmax + lmax + Nf + Nsplit + Nwidth + pl[8];
+        for (int l = 1; l <= 3; l++) {
+            const double sum = ms_global_norm_sum(q, l);
+            if (!(sum <= 1. + 1e-10 && sum >= 0)) return neg_inf();  // (a NaN sum fails logP_uniform's test as well)
+        }
+    }
     const int on = Nmax + lmax + Nf + Nsplit + Nwidth;  // noise block
     if (sw[on + 3] != 0)
         if ((params[on + 3] < 0) || (params[on + 4] < 0) || (params[on + 5] < 0)) return neg_inf();
@@ -199,7 +224,7 @@ TM_HD xreal ms_global_constraints(const double *params, const int *pl, const int
     return 0;
 }
 
-// number of additive terms after the Np generic ones: d02 terms then smoothness terms
+// number of additive terms after the Np generic ones: d02 terms, smoothness terms, then the three constants of the ratio sums
 TM_HD int ms_global_extra_terms(const int *pl, const double *extra) {
     const int Nfl[4] = {pl[2], pl[3], pl[4], pl[5]};
     int n = 0;
@@ -207,6 +232,7 @@ TM_HD int ms_global_extra_terms(const int *pl, const double *extra) {
     if ((int)extra[0] == 1) {
         for (int el = 0; el < pl[1] + 1 && el < 4; el++) n += Nfl[el];
     }
+    if ((int)extra[8] == 1 && ms_global_norm_active(extra)) n += 3;
     return n;
 }
 // extra term t (0-based) -- Dnu = slope of the l=0 frequencies (priors_calc.cpp:277-313)
@@ -222,11 +248,13 @@ TM_HD xreal ms_global_extra_term(const double *params, const int *pl, const doub
     }
     const double scoef = extra[1];
     int i0 = 0;
-    for (int el = 0; el < lmax + 1 && el < 4; el++) {
-        if (t < Nfl[el]) return logP_gaussian(0, scoef, second_difference(params + Nmax + lmax + i0, Nfl[el], t));
-        t -= Nfl[el];
-        i0 += Nfl[el];
-    }
+    if ((int)extra[0] == 1)
+        for (int el = 0; el < lmax + 1 && el < 4; el++) {
+            if (t < Nfl[el]) return logP_gaussian(0, scoef, second_difference(params + Nmax + lmax + i0, Nfl[el], t));
+            t -= Nfl[el];
+            i0 += Nfl[el];
+        }
+    if ((int)extra[8] == 1 && ms_global_norm_active(extra) && t < 3) return -ms_global_norm_term();  // (sums inside: see the constraints)
     return 0;
 }
 
@@ -281,10 +309,14 @@ TM_HD xreal prior_serial(int prior_class, const double *params, const int *pl, l
     if (prior_class == 2) {
         const xreal c = ms_global_constraints(params, pl, sw, extra, status);
         if (c != 0) return c;
-        for (long i = 0; i < Np; i++) f = f + generic_prior_term(params, Np, pp, sw, i, status);
+        const int nnorm = ((int)extra[8] == 1 && ms_global_norm_active(extra)) ? 3 : 0;
+        for (int t = 0; t < nnorm; t++) f = f - ms_global_norm_term();  // before everything else (priors_calc.cpp:228-241)
+        xreal pena = 0;  // apply_generic_priors' own sum, then added to f (priors_calc.cpp:276)
+        for (long i = 0; i < Np; i++) pena = pena + generic_prior_term(params, Np, pp, sw, i, status);
+        f = f + pena;
         double fit[2];
         mt::linfit_index(params + pl[0] + pl[1], pl[2], fit);
-        const int ne = ms_global_extra_terms(pl, extra);
+        const int ne = ms_global_extra_terms(pl, extra) - nnorm;
         for (int t = 0; t < ne; t++) f = f + ms_global_extra_term(params, pl, extra, fit[0], t);
         return f;
     }

@@ -9,6 +9,7 @@ y = M(theta_true) * Exp(1) with M supplied by the caller (GPU path in bench.py, 
 import numpy as np
 
 MODEL_CLASSIC, MODEL_LOCAL, MODEL_AJ, MODEL_RGB_V4, MODEL_RGB_CTE_V4 = 3, 11, 23, 25, 27
+MODEL_CLASSIC_V2, MODEL_CLASSIC_V3, MODEL_LOCAL_HNLM = 12, 13, 14  # heights per m-component instead of the inclination
 KEPLER_4YR_RESOL = 1e6 / (4.0 * 365.0 * 86400.0)  # test_build_l_mode.cpp:107
 
 
@@ -105,7 +106,7 @@ def make_c3_star(seed=20240229, nx=100000, nmax=14, lmax=3, step=0.02, fmin=1950
                                            noise=noise, eta_switch=0.0, n_first=15, dl_shift=(0, 0, -1, -1))
     o_inc = plength[:9].sum()
     params[o_inc] = 60.0 + rng.uniform(-15, 15)
-    names = (["Height_l0"] * nmax + ["Visibility_l%d" % (l + 1) for l in range(lmax)] + ["Frequency_l"] * (4 * nmax) +
+    names = (["Height_l0"] * nmax + ["Visibility_l%d" % (l + 1) for l in range(lmax)] + ["Frequency_l"] * ((lmax + 1) * nmax) +
              ["a1_0", "a1_1", "a2_0", "a2_1", "a3_0", "a3_1", "a4_0", "a4_1", "a5_0", "a5_1", "a6_0", "a6_1", "eta0_switch",
               "Lorentzian_asymetry"] + ["Width_l0"] * nmax +
              ["Harvey-Noise_H", "Harvey-Noise_tc", "Harvey-Noise_p", "Harvey-Noise_H", "Harvey-Noise_tc", "Harvey-Noise_p",
@@ -114,8 +115,8 @@ def make_c3_star(seed=20240229, nx=100000, nmax=14, lmax=3, step=0.02, fmin=1950
     relax = np.zeros(params.size, dtype=np.int32)
     relax[:nmax] = 1                                   # heights
     relax[nmax:nmax + lmax] = 1                        # visibilities
-    relax[nmax + lmax:nmax + lmax + 4 * nmax] = 1      # frequencies
-    o_split = nmax + lmax + 4 * nmax
+    relax[nmax + lmax:nmax + lmax + (lmax + 1) * nmax] = 1      # frequencies
+    o_split = nmax + lmax + (lmax + 1) * nmax
     relax[o_split] = 1                                 # a1_0
     o_w = o_split + 14
     relax[o_w:o_w + nmax] = 1                          # widths
@@ -194,6 +195,145 @@ def aj_to_classic(params, plength):
     pl = plength.copy()
     pl[6] = 6
     return out, pl
+
+
+# ---- height-per-m models (ids 12, 13, 14): conversions from the inclination models that give the same spectrum ----
+def amplitude_ratio(l, inc_deg):
+    """Relative heights of the 2l+1 components at inclination inc_deg (Gizon & Solanki 2003), closed forms for l <= 3.  Equal to the
+    library's amplitude_ratio() to rounding only: a test that needs the same bits passes the oracle's function to the converters."""
+    c, s = np.cos(np.radians(inc_deg)), np.sin(np.radians(inc_deg))
+    half = {0: [1.0],
+            1: [c * c, 0.5 * s * s],
+            2: [0.25 * (3 * c * c - 1) ** 2, 1.5 * c * c * s * s, 0.375 * s ** 4],
+            3: [0.25 * (5 * c ** 3 - 3 * c) ** 2, 0.1875 * s * s * (5 * c * c - 1) ** 2, 1.875 * c * c * s ** 4, 0.3125 * s ** 6]}[l]
+    return np.array(half[:0:-1] + half)
+
+
+def classic_to_v2(params, plength, amplitude_ratio=amplitude_ratio):
+    """Classic (id 3) vector -> Classic_v2 (id 12): the inclination is replaced by the nine ratios [V1(0), V1(1), V2(0..2), V3(0..3)]
+    = amplitude_ratio(l, inclination)[l + m] (0 above lmax, like the loader's empty slots).  Same operations as id 3: same rows."""
+    pl = np.asarray(plength, dtype=np.int32).copy()
+    lmax, o_inc = int(pl[1]), int(pl[:9].sum())
+    inc = params[o_inc]
+    ratios = []
+    for l in (1, 2, 3):
+        V = amplitude_ratio(l, inc) if l <= lmax else np.zeros(2 * l + 1)
+        ratios += [V[l + m] for m in range(l + 1)]
+    pl[9] = 9
+    return np.concatenate([params[:o_inc], ratios, params[o_inc + 1:]]), pl
+
+
+def classic_to_v3(params, plength, amplitude_ratio=amplitude_ratio):
+    """Classic (id 3) vector -> Classic_v3 (id 13): one height per (n, l, m >= 0), value H_n V_l amplitude_ratio(l, i)[l + m] (the
+    squared amplitude when do_amp is set), laid out l-major as the reference's loader does (io_ms_global.cpp:1269-1280).  The model
+    function counts every degree's offset from the start of the block (include/tamcmc_hip.h), so the spectrum equals the Classic
+    one for lmax <= 1 only -- to rounding: the heights are formed in a different order."""
+    pl = np.asarray(plength, dtype=np.int32).copy()
+    nmax, lmax, o_inc = int(pl[0]), int(pl[1]), int(pl[:9].sum())
+    inc = params[o_inc]
+    h = []
+    for l in range(1, lmax + 1):
+        V = amplitude_ratio(l, inc)
+        for n in range(int(pl[2 + l])):
+            h += [params[n] * abs(params[nmax + l - 1]) * V[l + m] for m in range(l + 1)]
+    pl[9] = len(h)
+    return np.concatenate([params[:o_inc], h, params[o_inc + 1:]]), pl
+
+
+def local_inclination(params, plength):
+    """Inclination (degrees) and a1 of a model_MS_local_basic vector, as the model function forms them (models.cpp:3059-3066)."""
+    o = int(plength[0] + plength[1] + plength[2:6].sum())
+    pi = np.longdouble("3.141592653589793238462643383279502884")
+    inc = float(np.longdouble(np.arctan(params[o + 4] / params[o + 3])) * np.longdouble(180.0) / pi)
+    return inc, params[o + 3] ** 2 + params[o + 4] ** 2
+
+
+def local_to_hnlm(params, plength, amplitude_ratio=amplitude_ratio):
+    """model_MS_local_basic (id 11) vector -> model_MS_local_Hnlm (id 14): Splitting_a1 in slot 0 of the splitting block instead of
+    sqrt(a1) cos i / sin i, heights of l >= 1 expanded to h amplitude_ratio(l, i)[l + m], l-major after the l = 0 heights
+    (io_local.cpp:1031-1051), plength[0] = Nfl0 + 2 Nfl1 + 3 Nfl2 + 4 Nfl3.  As for classic_to_v3, the model function's offsets make
+    the spectrum equal to the basic one only while no l = 2, 3 mode follows an l = 1 mode (include/tamcmc_hip.h)."""
+    pl = np.asarray(plength, dtype=np.int32).copy()
+    nfl = [int(v) for v in pl[2:6]]
+    ntot = int(pl[0])
+    inc, a1 = local_inclination(params, pl)
+    h = list(params[:nfl[0]])
+    src = nfl[0]
+    for l in (1, 2, 3):
+        V = amplitude_ratio(l, inc)
+        for n in range(nfl[l]):
+            h += [params[src] * V[l + m] for m in range(l + 1)]
+            src += 1
+    rest = params[ntot:].copy()
+    o = int(pl[1]) + sum(nfl)
+    rest[o], rest[o + 3], rest[o + 4] = a1, 0.0, 0.0
+    pl[0] = len(h)
+    return np.concatenate([h, rest]), pl
+
+
+def _splice(arr, lo, hi, new, axis=-1):
+    arr = np.asarray(arr)
+    idx = [slice(None)] * arr.ndim
+    idx[axis] = slice(0, lo)
+    head = arr[tuple(idx)]
+    idx[axis] = slice(hi, None)
+    return np.concatenate([head, np.asarray(new, dtype=arr.dtype), arr[tuple(idx)]], axis=axis)
+
+
+def make_classic_star(seed=20240229, nx=100000, nmax=14, lmax=3, step=0.02, fmin=1950.0):
+    """The C3 star in the Classic dialect (model_MS_Global_a1etaa3_HarveyLike_Classic, id 3): a1, a3 and the asymmetry of the aj
+    star, eta0 from the large separation; same free parameters."""
+    s = make_c3_star(seed=seed, nx=nx, nmax=nmax, lmax=lmax, step=step, fmin=fmin)
+    params, pl = aj_to_classic(s.params, s.plength)
+    o = int(pl[0] + pl[1] + pl[2:6].sum())
+    names = s.names[:o] + ["Splitting_a1", "Asphericity_eta", "Splitting_a3", "Empty", "Empty", "Lorentzian_asymetry"] + s.names[o + 14:]
+    keep = [0, 1, 4, 1, 1, 13]  # source slot of each Classic slot in the aj block (1: a fixed, unused one)
+    relax = _splice(s.relax, o, o + 14, s.relax[o:o + 14][keep] * np.array([1, 0, 0, 0, 0, 0]))
+    pr = _splice(s.priors, o, o + 14, s.priors[:, o:o + 14][:, keep], axis=1)
+    sw = _splice(s.priors_switch, o, o + 14, s.priors_switch[o:o + 14][keep] * np.array([1, 0, 0, 0, 0, 0]))
+    extra = s.extra_priors.copy()
+    extra[9] = -1.0  # the default (Classic) branch of priors_MS_Global
+    return Star(MODEL_CLASSIC, params, pl, s.x, relax, pr, sw, names, prior_class=2, extra_priors=extra)
+
+
+def make_v2_star(amplitude_ratio=amplitude_ratio, **kw):
+    """make_classic_star with the inclination replaced by the nine height ratios (id 12): Uniform on [0, 1], free up to lmax,
+    extra_priors[8] = 1 -- what the loader makes of a Classic_v2 .model file."""
+    s = make_classic_star(**kw)
+    params, pl = classic_to_v2(s.params, s.plength, amplitude_ratio)
+    o, lmax = int(s.plength[:9].sum()), int(pl[1])
+    used = np.array([1 if l <= lmax else 0 for l in (1, 1, 2, 2, 2, 3, 3, 3, 3)], dtype=np.int32)
+    names = s.names[:o] + [("Inc:H%d,%d" % lm if u else "Empty") for lm, u in
+                           zip([(1, 0), (1, 1), (2, 0), (2, 1), (2, 2), (3, 0), (3, 1), (3, 2), (3, 3)], used)] + s.names[o + 1:]
+    pr9 = np.full((4, 9), -9999.0)
+    pr9[0, used == 1], pr9[1, used == 1] = 0.0, 1.0
+    extra = s.extra_priors.copy()
+    extra[8] = 1.0
+    return Star(MODEL_CLASSIC_V2, params, pl, s.x, _splice(s.relax, o, o + 1, used), _splice(s.priors, o, o + 1, pr9, axis=1),
+                _splice(s.priors_switch, o, o + 1, used * P_UNIFORM), names, prior_class=2, extra_priors=extra)
+
+
+def make_hnlm_star(amplitude_ratio=amplitude_ratio, **kw):
+    """make_c2_star as model_MS_local_Hnlm (id 14): one free height per (n, l, m >= 0), Splitting_a1 free, no inclination."""
+    s = make_c2_star(**kw)
+    params, pl = local_to_hnlm(s.params, s.plength, amplitude_ratio)
+    nfl, ntot = [int(v) for v in pl[2:6]], int(s.plength[0])
+    hn = ["Height_l"] * nfl[0] + ["H(%d,%d,%d)" % (n, l, m) for l in (1, 2, 3) for n in range(nfl[l]) for m in range(l + 1)]
+    nh = len(hn)
+    names = hn + s.names[ntot:]
+    o = nh + int(pl[1]) + sum(nfl)
+    names[o], names[o + 3], names[o + 4] = "Splitting_a1", "Empty", "Empty"
+    relax = _splice(s.relax, 0, ntot, np.ones(nh))
+    relax[[o, o + 3, o + 4]] = 1, 0, 0
+    rules = {"Height_l": (P_JEFF, lambda v: (1.0e-3, 1.0e4)), "Frequency_l": (P_UNIFORM, lambda v: (v - 5.0, v + 5.0)),
+             "Splitting_a1": (P_UNIFORM, lambda v: (0.0, 6.0)), "Width_l": (P_JEFF, lambda v: (0.05, 40.0)),
+             "White_Noise_N0": (P_UNIFORM, lambda v: (0.0, 5.0))}
+    for nm in hn:
+        rules[nm] = rules["Height_l"]
+    pr, sw = _prior_tables(names, params, relax, rules)
+    extra = s.extra_priors.copy()
+    extra[3] = 2.0  # what the loader sets; priors_local applies no normalisation
+    return Star(MODEL_LOCAL_HNLM, params, pl, s.x, relax, pr, sw, names, prior_class=3, extra_priors=extra)
 
 
 def make_params_rgb_model(rng, nmax=6, dnu=20.0, epsilon=0.2, n_first=6, delta0l=-0.6, DPl=80.0, alpha_g=0.0, q=0.15, nferr=4,
