@@ -10,6 +10,7 @@
 #include "dev_sampler.h"
 #include "host_sampler.h"
 #include "rng.h"
+#include "step_schedule.h"
 
 using namespace tamcmc;
 
@@ -248,7 +249,7 @@ int tamcmc_sampler_draws(const tamcmc_sampler *s, int64_t iteration, double *z, 
     const uint64_t seed = s->mala->get_seed();
     for (long m = 0; m < Nc; m++) {
         if (z)
-            for (long k = 0; k < Nv; k += 2) {  // same addressing as MALA::new_prop_values / dev_sampler.hip::normals_into
+            for (long k = 0; k < Nv; k += 2) {  // same addressing as MALA::new_prop_values / dev_iterate_impl.h::normals_into
                 double z0, z1;
                 rng_normal2(seed, RNG_PROPOSAL, (uint32_t)m, (uint64_t)iteration, (uint32_t)(k / 2), z0, z1);
                 z[(size_t)(m * Nv + k)] = z0;
@@ -260,12 +261,8 @@ int tamcmc_sampler_draws(const tamcmc_sampler *s, int64_t iteration, double *z, 
             u_accept[m] = u;
         }
     }
-    double u, u2;
-    rng_uniform2(seed, RNG_SWAP, 0, (uint64_t)iteration, 0, u, u2);
-    int a = (int)(u2 * (double)(Nc - 1));
-    if (a > Nc - 2) a = (int)Nc - 2;
-    if (u_swap) *u_swap = u;
-    if (ind_A) *ind_A = Nc > 1 ? a : -1;
+    const int a = swap_draw(seed, (int)Nc, iteration, u_swap);  // (at any iteration; -1 for a single chain)
+    if (ind_A) *ind_A = a;
     return TAMCMC_OK;
 }
 

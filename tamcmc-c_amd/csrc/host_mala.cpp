@@ -13,6 +13,7 @@
 
 #include "host_sampler.h"
 #include "rng.h"
+#include "step_schedule.h"
 
 namespace tamcmc {
 
@@ -143,7 +144,7 @@ const Matrix &MALA::factor(int m) {
         for (long i = 0; i < Nvars; i++) T(i, i) += epsi2;
         for (double &v : T.a) v *= sigma[(size_t)m];
         // not positive definite (only while gamma = c0/(1+i) > 1): the previous factor stays -- same rule as the device engine
-        // (dev_sampler.hip::adapt_chain); the reference hands Eigen's partially computed factor on (MALA.cpp:348-350)
+        // (dev_iterate_impl.h::adapt_chain); the reference hands Eigen's partially computed factor on (MALA.cpp:348-350)
         if (cholesky_lower(T) || Lchol[(size_t)m].a.empty()) Lchol[(size_t)m] = T;
         Lchol_valid[(size_t)m] = 1;
     }
@@ -211,10 +212,8 @@ std::vector<double> MALA::new_prop_values(const double *vars, int m, const doubl
 
 // MALA.cpp:397-461 -- adjacent-pair swap on the TEMPERED log-likelihoods; returns ind_A
 int MALA::parallel_tempering(Model_def *model) {
-    double u, u2;
-    rng_uniform2(seed, RNG_SWAP, 0, (uint64_t)iteration, 0, u, u2);
-    int ind_A = (int)(u2 * (double)(Nchains - 1));
-    if (ind_A > Nchains - 2) ind_A = (int)Nchains - 2;
+    double u;
+    const int ind_A = swap_draw(seed, (int)Nchains, iteration, &u);  // (the caller tests the iteration: step_schedule.h)
     const int ind_B = ind_A + 1;
     const long double LA = model->logLikelihood[(size_t)ind_A], LB = model->logLikelihood[(size_t)ind_B];
     const long double logL_A_TB = LA * Tcoefs[(size_t)ind_A] / Tcoefs[(size_t)ind_B];
@@ -404,7 +403,7 @@ int MALA::step(Model_def *cur, Model_def *prop, Data *data, Config *) {
             update_proposal(cur->vars.row(m), cur->Pmove[(size_t)m], (int)m);  // position unchanged: gradient stays valid
     }
     // [3] parallel tempering (MALA.cpp:688-703)
-    if (dN_mixing > 0 && i % dN_mixing == 0 && i != 0 && Nchains > 1) parallel_tempering(cur);
+    if (is_swap_iteration((int)Nchains, dN_mixing, i)) parallel_tempering(cur);
     else { cur->swaped = false; cur->Pswap = 0; }
     iteration = i + 1;
     return TAMCMC_OK;

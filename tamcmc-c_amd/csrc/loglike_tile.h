@@ -223,8 +223,9 @@ struct __attribute__((aligned(16))) TileLds {
 };
 
 // One tile of one evaluation: table slot `sb` (its multiplets, noise row, background series), result row `b` (partials / model).
-// COH: the two partial sums are written through to memory (device-scope stores) because another workgroup of the SAME launch reads
-// them (the fused sampler step's settle tail); MI355X has one L2 per XCD and plain stores stay in the writer's.
+// COH: the two partial sums are written through to memory (device-scope stores) for a caller whose launch reads them in ANOTHER
+// workgroup; MI355X has one L2 per XCD and plain stores stay in the writer's.  No caller asks for it: the fused sampler step reads a
+// launch's sums in the NEXT launch (dev_step_impl.h).
 template <int MODE, int WGS, int K, bool WRITE_MODEL, bool DELTA, bool COH = false>
 __device__ __forceinline__ void tile_compute(const LoglikeArgs &a, const int tile, const int b, const int sb, TileLds<MODE, WGS> &S, const int mbeg,
                                              const int mend, const int nh, const int nn) {

@@ -189,7 +189,7 @@ __device__ inline void amplitude_ratios_lanes(const X &x, int lmax, double beta_
 // models.cpp:4727-4866 (id 25) / :4377-4470 (id 27, cte_width: one width parameter, Wl0 constant, :4407) + solver_mm.cpp:470-555 /
 // :624-705 (everything before the pair loop), then what the row builder needs besides the solver's output (:4867-5000), the bias spline
 // and the vector's noise row.  Written once: the host calls it per vector (batched C-ABI path, host-driven sampler), the device engine
-// runs it in its proposal kernel (dev_sampler.hip, propose_common) on the proposal it has just drawn.  Returns the vector's status (also left in P.status / ri.status).
+// runs it in its proposal kernel (dev_iterate_impl.h, propose_common) on the proposal it has just drawn.  Returns the vector's status (also left in P.status / ri.status).
 template <class X>
 __host__ __device__ inline int unpack_vector(const X &x, const double *p, const int32_t *pl, double step, bool cte_width, int dense, Prep &P, RowIn &ri,
                                              double *noise_row, int32_t *nh_out, int32_t *nn_out, double *fmin_out) {

@@ -1,0 +1,87 @@
+// step_schedule.h -- what the host engine, the device engine and the host-side launch planning of the device engine must agree on, bit
+// for bit, written once: the parallel-tempering swap pair of an iteration (one Philox draw) and the schedule of a run() call (which
+// iterations run as fused steps, which of those as one launch over all chains).  Integer logic and rng.h only: no HIP types, so a plain
+// C++ compiler can include it (tests/step_schedule_driver.cpp).
+#pragma once
+#include "rng.h"
+
+namespace tamcmc {
+
+// ---- the swap pair (MALA.cpp:397-405) ----
+
+// (inlined into every caller whatever its size: on the device, decide() and k_iterate keep the code they have with the draw in line)
+#define TAMCMC_HD_FLAT TAMCMC_HD __attribute__((always_inline))
+
+// Does iteration `it` end with a swap attempt?  (the reference mixes every dN_mixing iterations, never at iteration 0)
+TAMCMC_HD_FLAT bool is_swap_iteration(int C, long dN_mixing, long it) { return dN_mixing > 0 && (it % dN_mixing == 0) && it != 0 && C > 1; }
+
+// The draw itself, whatever the iteration: first chain A of the pair (A, A+1) -- -1 for a single chain -- and the uniform of the swap
+// test.
+TAMCMC_HD_FLAT int swap_draw(uint64_t seed, int C, long it, double *u_out) {
+    double u, u2;
+    rng_uniform2(seed, RNG_SWAP, 0, (uint64_t)it, 0, u, u2);
+    int A = (int)(u2 * (double)(C - 1));
+    if (A > C - 2) A = C - 2;
+    if (u_out) *u_out = u;
+    return A;
+}
+
+// First chain of iteration `it`'s swap pair, -1 when the iteration has none.
+TAMCMC_HD_FLAT int swap_pair(uint64_t seed, int C, long dN_mixing, long it, double *u_out) {
+    return is_swap_iteration(C, dN_mixing, it) ? swap_draw(seed, C, it, u_out) : -1;
+}
+
+// ---- chain groups ----
+
+// Group of `chain` among the G contiguous groups [goff[g], goff[g+1]).
+TAMCMC_HD int group_of(int chain, const int *goff, int G) {
+    int g = 0;
+    while (g + 1 < G && chain >= goff[g + 1]) g++;
+    return g;
+}
+
+// ---- stretches of a run() call ----
+
+constexpr long MIN_FUSED = 3;  // a fused stretch pays one entry launch: shorter quiet runs stay in lockstep
+
+// End of the run of iterations without adaptation that starts at `from` (learn == nullptr: nothing learns).
+TAMCMC_HD long quiet_end(const char *learn, long n_iter, long from) {
+    long q = from;
+    while (q < n_iter && !(learn && learn[q])) q++;
+    return q;
+}
+
+// The stretch [i, *end) that a call of n_iter iterations runs next (i < n_iter), and its scheme: a quiet run of at least MIN_FUSED
+// iterations is one fused stretch; everything up to the start of the next such run (or the end of the call) is one lockstep stretch.
+TAMCMC_HD void next_stretch(const char *learn, long n_iter, long i, bool use_fused, long *end, bool *is_fused) {
+    const long jn = quiet_end(learn, n_iter, i);
+    if (use_fused && jn - i >= MIN_FUSED) {
+        *end = jn;
+        *is_fused = true;
+        return;
+    }
+    long k = i;
+    for (;;) {
+        const long q = quiet_end(learn, n_iter, k);
+        if (use_fused && q - k >= MIN_FUSED && k > i) break;
+        k = q;
+        while (k < n_iter && learn && learn[k]) k++;
+        if (k >= n_iter) break;
+    }
+    *end = k;
+    *is_fused = false;
+}
+
+// ---- fused stretch with two chain groups [0, xsplit) and [xsplit, C) (split_ok; otherwise every iteration is one launch) ----
+
+// A swap pair (A, A+1) with one chain in each group.
+TAMCMC_HD bool straddles(bool split_ok, int xsplit, int A) { return split_ok && A == xsplit - 1; }
+
+// Is an iteration ONE launch over all chains?  A: its swap pair, A_prev: the previous iteration's (-1: none), first: the stretch's first
+// iteration (the chains are settled, the previous iteration's swap is not this stretch's business).  The launch of a straddling swap's
+// iteration builds the pair's cross candidates on both chains' vectors, the next one decides the swap from both chains' sums.
+TAMCMC_HD bool joint_launch(bool split_ok, int xsplit, int A, int A_prev, bool first) {
+    return !split_ok || straddles(split_ok, xsplit, A) || (!first && straddles(split_ok, xsplit, A_prev));
+}
+
+}  // namespace tamcmc
