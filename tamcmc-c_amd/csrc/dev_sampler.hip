@@ -93,7 +93,7 @@ struct DevSampler::Impl {
     FdBatch fd;
     DevBuf<unsigned char> fd_block;
     DevBuf<double> fd_part, fd_S, fd_model, fd_bg;
-    DevBuf<double> fused_bg, fused_part;  // (A): the candidates' background series, the tiles' partial sums by parity (see run())
+    DevBuf<double> fused_bg, fused_part, fused_psum;  // (A): the candidates' background series, the tiles' partial sums by parity and their per-tile sums (see run())
     MalaArgs mala{};
     bool grad_valid = false;
     int prior_class = 0, model_id = 0;
@@ -199,7 +199,7 @@ DevSampler::~DevSampler() {
     }
 #endif
     for (void *p : impl->allocs) (void)hipFree(p);
-    impl->fd_block.release(); impl->fd_part.release(); impl->fd_S.release(); impl->fd_model.release(); impl->fd_bg.release(); impl->fused_bg.release(); impl->fused_part.release();
+    impl->fd_block.release(); impl->fd_part.release(); impl->fd_S.release(); impl->fd_model.release(); impl->fd_bg.release(); impl->fused_bg.release(); impl->fused_part.release(); impl->fused_psum.release();
     if (impl->h_pack) (void)hipHostFree(impl->h_pack);
     for (int i = 0; i < impl->n_ev; i++) { (void)hipEventDestroy(impl->ev[i][0]); (void)hipEventDestroy(impl->ev[i][1]); }
     for (int i = 0; i < impl->n_gev; i++) { (void)hipEventDestroy(impl->gev[i][0]); (void)hipEventDestroy(impl->gev[i][1]); }
@@ -346,6 +346,7 @@ int DevSampler::init(tamcmc_hip_ctx *c, const DevSamplerInit &in) {
         DCHK(hipMemsetAsync(f.cand_rej, 0, 3 * NS * sizeof(int), st));
         DCHK(hipMemsetAsync(f.cand_stR, 0, 3 * NS * sizeof(int), st));
         f.part = nullptr;
+        f.psum = nullptr;
         f.bg = nullptr;
         // the candidate roles borrow the tile workgroup's LDS: a parameter vector too long for it keeps the lockstep scheme
         const size_t role_lds = (Np + 2 * Nv + 1) * sizeof(double) + unpack_lds_bytes() + 32;
@@ -681,6 +682,8 @@ struct DevSampler::Impl::RunCall {
         if (use_fused) {  // (A): the tiles' partial sums by iteration parity (launch i writes one half and reads the other)
             DCHK(I.fused_part.reserve(2 * C * (size_t)a.ntiles * 2));
             I.f.part = I.fused_part.p;
+            DCHK(I.fused_psum.reserve(2 * C * (size_t)a.ntiles));  // (written and read with `part`, tile by tile: valid wherever it is)
+            I.f.psum = I.fused_psum.p;
         }
         // (two groups pay once one launch no longer fits the GPU's resident waves -- 20 chains x 196 tiles: 27.7 -> 23.9 us, x 782 tiles:
         // 59.8 -> 49.6 us -- and cost below that: 8 chains x 196 tiles 20.5 -> 23.7 us, 20 chains x 20 tiles 33.5 -> 35.6 us;

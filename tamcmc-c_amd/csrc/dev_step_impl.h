@@ -27,6 +27,7 @@ struct FusedArgs {
     int *prop_st;                      // [2][C]   ... and status (prior role's, else rows role's)
     double *quick;                     // [2][C][QN] that iteration's MH and swap tests as thresholds on the sums of the partials (quick_decide)
     double *part;                      // [2][C][ntiles][2] the tiles' partial sums of that iteration
+    double *psum;                      // [2][C][ntiles]    part[..][0] + part[..][1], stored by the same lane beside them (quick_decide)
     double *lz;                        // [2][C][Nv] L z of chain m for the iteration of that parity, computed one launch ahead
     // quick_decide's safety margin (1e-11; +inf under TAMCMC_OPT_QUICK_DECIDE = 1: every margin test answers "undecided") and what the
     // tests read back (tamcmc_sampler_get_info): [0] fallbacks to decide() taken by the likelihood tiles, counted by each chain's tile 0;
@@ -239,35 +240,59 @@ __device__ __attribute__((noinline)) void commit_chain(const DevSamplerArgs *ga,
 // (pairA, named by the host: the same Philox draw) is taken the same way: log u against LA (TA/TB - 1) + LB (TB/TA - 1) with the
 // post-test likelihoods from the approximate sums.  Otherwise -- about once in 1e5 tests -- decide() evaluates everything as written.
 // A decide() of ~2000 dependent instructions costs a lone wave 5 us at the head of the launch's longest chains; this one ~0.5 us.
-// (the shortcut itself, a leaf function: -1 = undecided)
-__device__ __attribute__((noinline)) int quick_decide_leaf(const DevSamplerArgs *ga, const FusedArgs *gf, int m, int q, int pairA, Decided *out) {
+//
+// The sums come from FusedArgs::psum, ONE value per tile, c_t = fl(p_t[0] + p_t[1]), instead of the two of FusedArgs::part: half the loads,
+// and the magnitude is sum|c_t|.  Why the margin still covers it: the pre-addition adds one rounding of relative size eps to each term,
+// |c_t - (p_t[0] + p_t[1])| <= eps (|p_t[0]| + |p_t[1]|), which is one more unit in the n of "n eps sum|v|" above; and sum|c_t| <= sum|p_t[0]| +
+// sum|p_t[1]|, so the margin can only be the smaller of the two -- by the factor to which the two partials of a tile cancel.  They do not
+// cancel to speak of: p_t[0] = sum y/M is ~ the tile's bin count with a chi-square scatter of its square root, p_t[1] = sum ln M moves
+// with the units of the spectrum; even where ln M ~ -1 on every bin, |c_t| stays ~ sqrt(bins) = 1/50 of the magnitude.  1e-11 sum|c_t|
+// against ~2e-14 (sum|p_t[0]| + sum|p_t[1]|) leaves three orders of magnitude, one and a half in that worst case.  (The exact decide(), the
+// commit workgroups and the records keep reading `part`, in k_finalize's order.)
+
+// The lane's share of the per-tile values of chain j0 (PAIR: and of chain j0 + 1, both chains' loads in flight together), summed in any
+// order: four loads per lane and round (C3's 196 tiles: one round), then a butterfly.  A chain outside the swap pair pays for one chain.
+template <bool PAIR>
+__device__ __forceinline__ void quick_sums(const double *c0, int n, int lane, double &s0, double &a0, double &s1, double &a1) {
+    for (int t0 = 0; t0 < n; t0 += 256) {
+        double v[4], w[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int t = t0 + k * 64 + lane;
+            v[k] = t < n ? c0[t] : 0.0;
+            if (PAIR) w[k] = t < n ? c0[n + t] : 0.0;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            s0 += v[k]; a0 += fabs(v[k]);
+            if (PAIR) { s1 += w[k]; a1 += fabs(w[k]); }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        s0 += __shfl_xor(s0, off, 64); a0 += __shfl_xor(a0, off, 64);
+        if (PAIR) { s1 += __shfl_xor(s1, off, 64); a1 += __shfl_xor(a1, off, 64); }
+    }
+}
+// (the shortcut itself: -1 = undecided.  Inlined at the head of a likelihood tile, whose own first loads are in flight beside these --
+// StepTiles::head; a leaf function for the candidate roles)
+__device__ __forceinline__ int quick_decide_core(const DevSamplerArgs *ga, const FusedArgs *gf, int m, int q, int pairA, Decided *out) {
     const ConstArgs &a = *(const ConstArgs *)uniform_ptr(ga);
     const ConstFused &f = *(const ConstFused *)uniform_ptr(gf);
     const int lane = threadIdx.x & 63, C = a.C;
-    const int p = q ^ 1, n2 = 2 * a.ntiles;
+    const int p = q ^ 1, n = a.ntiles;
     const bool in_pair = pairA >= 0 && (m == pairA || m == pairA + 1);
     const int j0 = in_pair ? pairA : m;
-    const double *b0 = f.part + ((size_t)p * C + j0) * n2;
+    const double *c0 = f.psum + ((size_t)p * C + j0) * n;
     const double *r0 = f.quick + ((size_t)p * C + j0) * QN;
-    // every load first: the records (lane k < QN: field k of chain j0, lane QN + k: of chain j0 + 1), the partial sums
-    const double rec = (lane < (in_pair ? 2 * QN : QN)) ? r0[lane] : 0.0;
-    double s0 = 0, a0 = 0, s1 = 0, a1 = 0;
-    for (int t0 = 0; t0 < n2; t0 += 512) {
-        double v[8], w[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const int t = t0 + k * 64 + lane;
-            v[k] = t < n2 ? b0[t] : 0.0;
-            w[k] = (in_pair && t < n2) ? b0[n2 + t] : 0.0;
-        }
-#pragma unroll
-        for (int k = 0; k < 8; k++) { s0 += v[k]; a0 += fabs(v[k]); s1 += w[k]; a1 += fabs(w[k]); }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) { s0 += __shfl_xor(s0, off, 64); a0 += __shfl_xor(a0, off, 64); }
-    if (in_pair) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) { s1 += __shfl_xor(s1, off, 64); a1 += __shfl_xor(a1, off, 64); }
+    // every load first: the records (lane k < QN: field k of chain j0, lane QN + k: of chain j0 + 1), the tiles' sums
+    double rec, s0 = 0, a0 = 0, s1 = 0, a1 = 0;
+    if (in_pair) {  // (wave-uniform)
+        rec = lane < 2 * QN ? r0[lane] : 0.0;
+        quick_sums<true>(c0, n, lane, s0, a0, s1, a1);
+    } else {
+        rec = lane < QN ? r0[lane] : 0.0;
+        quick_sums<false>(c0, n, lane, s0, a0, s1, a1);
     }
     const double St0 = __shfl(rec, 0, 64), ok0 = __shfl(rec, 1, 64);
     const int ps0 = (int)__shfl(rec, 7, 64);
@@ -308,6 +333,9 @@ __device__ __attribute__((noinline)) int quick_decide_leaf(const DevSamplerArgs 
     if (out && lane == 0) *out = d;
     return d.slot;
 }
+__device__ __attribute__((noinline)) int quick_decide_leaf(const DevSamplerArgs *ga, const FusedArgs *gf, int m, int q, int pairA, Decided *out) {
+    return quick_decide_core(ga, gf, m, q, pairA, out);
+}
 
 __device__ __forceinline__ int quick_decide(const DevSamplerArgs *ga, const FusedArgs *gf, int m, long it, int q, int settled, int pairA,
                                             Decided *out) {
@@ -316,16 +344,11 @@ __device__ __forceinline__ int quick_decide(const DevSamplerArgs *ga, const Fuse
     return s >= 0 ? s : decide(ga, gf, m, it, q, 0, out);
 }
 
-// The same for a likelihood tile, which wants the slot alone.  Its fallback is counted (FusedArgs::qcount[0]) once per chain and
-// iteration, by the chain's tile 0, inside the cold branch: the decided path is quick_decide's, instruction for instruction.
+// The fallback of a likelihood tile, which wants the slot alone (StepTiles::head).  It is counted (FusedArgs::qcount[0]) once per chain and
+// iteration, by the chain's tile 0, inside the cold branch: the decided path has no instruction for it.
 __device__ __attribute__((noinline)) int decide_counted(const DevSamplerArgs *ga, const FusedArgs *gf, int m, long it, int q, int tile) {
     if (tile == 0 && (threadIdx.x & 63) == 0) atomicAdd(((const ConstFused *)uniform_ptr(gf))->qcount, 1ull);
     return decide(ga, gf, m, it, q, 0, nullptr);
-}
-__device__ __forceinline__ int quick_slot(const DevSamplerArgs *ga, const FusedArgs *gf, int m, long it, int q, int settled, int pairA, int tile) {
-    if (settled) return decide(ga, gf, m, it, q, 1, nullptr);
-    const int s = quick_decide_leaf(ga, gf, m, q, pairA, nullptr);
-    return s >= 0 ? s : decide_counted(ga, gf, m, it, q, tile);
 }
 
 // Hook of the likelihood tiles of the fused step: evaluation b = chain first + b.
@@ -335,7 +358,29 @@ struct StepTiles {
     long it;
     int q, first, settled, pairA;
     static constexpr bool coherent_partials = false;
-    __device__ __forceinline__ int slot(const LoglikeArgs &, int b, int tile) const { return quick_slot(ga, gf, first + b, it, q, settled, pairA, tile); }
+    static constexpr bool early_loads = true;
+    // The chain's slot and what it leads to.  A chain outside iteration it-1's swap pair proposes from slot 2m (that iteration rejected)
+    // or 2m + 1 (accepted): both slots' words are requested before the decision's own loads and selected after it -- one memory round
+    // trip less at the head of every tile.  (Not their 152-byte rows: two of them would have to stay in registers across the decision.)
+    __device__ __forceinline__ tile::SlotWords head(const LoglikeArgs &a, int b, int tile) const {
+        const int m = first + b;
+        if (settled) return tile::slot_words(a, decide(ga, gf, m, it, q, 1, nullptr));
+        // (a.per > 0, the candidates' fixed-size table slots: no word is loaded under a condition -- a register that one branch loads and
+        // the other computes is waited for, with every load in flight, where it is computed)
+        const bool lone = a.per > 0 && !(pairA >= 0 && (m == pairA || m == pairA + 1));
+        tile::SlotWords w0{}, w1{};
+        if (lone) { w0 = tile::slot_words(a, 2 * m); w1 = tile::slot_words(a, 2 * m + 1); }
+        int s = quick_decide_core(ga, gf, m, q, pairA, nullptr);
+        if (s < 0) s = decide_counted(ga, gf, m, it, q, tile);
+        if (lone && (s >> 1) == m) return (s & 1) ? w1 : w0;
+        return tile::slot_words(a, s);
+    }
+    // (lane 0, beside the stores of the two sums: the one value quick_decide reads of this tile)
+    __device__ __forceinline__ void store_sums(int b, int tile, double s0, double s1) const {
+        const ConstArgs &a = *(const ConstArgs *)uniform_ptr(ga);
+        const ConstFused &f = *(const ConstFused *)uniform_ptr(gf);
+        f.psum[((size_t)q * a.C + first + b) * a.ntiles + tile] = s0 + s1;
+    }
     __device__ __forceinline__ void operator()(int, int, int) const {}
 };
 
@@ -549,7 +594,7 @@ struct StepCtl {
     int n_lz_live, q_lz;   // L z blocks that have work (chain first + e % cnt of iteration it_lz + e / cnt); parity of it_lz
     int first, cnt;        // the chains of this launch: [first, first + cnt) -- all of them, or one chain group (see run(): fused)
     int extra;             // 1: the launch also builds the four extra candidates of its iteration's swap pair (slots 2C..2C+3)
-    int pairA;             // first chain of iteration it-1's swap pair, -1: none (quick_slot)
+    int pairA;             // first chain of iteration it-1's swap pair, -1: none (quick_decide)
     const DevSamplerArgs *ga;  // device-memory copies of the first two kernel arguments (for the function calls)
     const struct FusedArgs *gf;
 };

@@ -223,13 +223,15 @@ struct __attribute__((aligned(16))) TileLds {
 };
 
 // One tile of one evaluation: table slot `sb` (its multiplets, noise row, background series), result row `b` (partials / model).
-// COH: the two partial sums are written through to memory (device-scope stores) for a caller whose launch reads them in ANOTHER
-// workgroup; MI355X has one L2 per XCD and plain stores stay in the writer's.  No caller asks for it: the fused sampler step reads a
-// launch's sums in the NEXT launch (dev_step_impl.h).
-template <int MODE, int WGS, int K, bool WRITE_MODEL, bool DELTA, bool COH = false>
+// Tail::coherent_partials: the two partial sums are written through to memory (device-scope stores) for a caller whose launch reads them
+// in ANOTHER workgroup; MI355X has one L2 per XCD and plain stores stay in the writer's.  No caller asks for it: the fused sampler step
+// reads a launch's sums in the NEXT launch (dev_step_impl.h).
+// xpre (may be null): the lane's K values of x, requested by a caller that had something to wait for first (loglike_tile).
+template <int MODE, int WGS, int K, bool WRITE_MODEL, bool DELTA, class Tail>
 __device__ __forceinline__ void tile_compute(const LoglikeArgs &a, const int tile, const int b, const int sb, TileLds<MODE, WGS> &S, const int mbeg,
-                                             const int mend, const int nh, const int nn) {
+                                             const int mend, const int nh, const int nn, const Tail &tail, const double *xpre) {
     constexpr bool FAST = (MODE != M_STRICT);
+    constexpr bool COH = Tail::coherent_partials;
     static_assert(!DELTA || (FAST && !WRITE_MODEL), "DELTA launches are FAST-mode, logL-only");
     constexpr bool FARFIELD = (MODE == M_FAST);
     LdsMult *s_m = (LdsMult *)S.buf;
@@ -287,7 +289,7 @@ __device__ __forceinline__ void tile_compute(const LoglikeArgs &a, const int til
     for (int k = 0; k < K; k++) {
         bin[k] = t0 + k * WGS + tid;
         const int bi = min(bin[k], a.Nx - 1);
-        xv[k] = a.x[bi];
+        xv[k] = xpre ? xpre[k] : a.x[bi];
         acc[k] = 0.0;
     }
 
@@ -674,6 +676,7 @@ __device__ __forceinline__ void tile_compute(const LoglikeArgs &a, const int til
             p[0] = out[0];
             p[1] = out[1];
         }
+        tail.store_sums(b, tile, out[0], out[1]);
     }
     KSTAMP(6);
 #ifdef TAMCMC_PROBE
@@ -687,11 +690,28 @@ __device__ __forceinline__ void tile_compute(const LoglikeArgs &a, const int til
 #undef PROBE_SKIP
 }
 
-// Hook of loglike_tile: which table slot evaluation b reads, and a tail called by every lane of every workgroup that owns a real tile
-// after its partial sums are written.
+// What a table slot leads to: its multiplet range and the lengths of its noise row.
+struct SlotWords { int sb, nn, nh, mbeg, mend; };
+// everything the slot index leads to is requested at once (one memory round trip, not one per dependent step): the table's range,
+// the noise row's lengths; a.per > 0 (device-built tables in fixed-size slots): the range begins at (slot0 + sb) * per
+__device__ __forceinline__ SlotWords slot_words(const LoglikeArgs &a, int sb) {
+    SlotWords w;
+    w.sb = sb; w.nn = a.nnoise[sb]; w.nh = a.nharvey[sb];
+    w.mend = a.offsets[2 * sb + 1];
+    w.mbeg = a.per > 0 ? (a.slot0 + sb) * a.per : a.offsets[2 * sb];
+    return w;
+}
+
+// Hook of loglike_tile: which table slot evaluation b reads, what lane 0 does with the tile's two sums beside storing them, and a tail
+// called by every lane of every workgroup that owns a real tile after its partial sums are written.
+// early_loads: the slot takes the hook a memory round trip or more to name (head(), in place of slot(): the slot AND its words) -- the
+// tile's x, which depends on the tile alone, is requested before it and consumed after it.  (Not y: held from here to the likelihood terms,
+// its K values per lane would not fit the 168 registers of the fused step's three waves per SIMD.)
 struct NoTail {
     static constexpr bool coherent_partials = false;
+    static constexpr bool early_loads = false;
     __device__ __forceinline__ int slot(const LoglikeArgs &, int b, int /*tile*/) const { return b; }  // evaluation b reads table slot b
+    __device__ __forceinline__ void store_sums(int /*b*/, int /*tile*/, double, double) const {}
     __device__ __forceinline__ void operator()(int /*b*/, int /*tile*/, int /*slot*/) const {}
 };
 
@@ -724,15 +744,16 @@ __device__ __forceinline__ void loglike_tile(const LoglikeArgs &a, const int id,
     if (tile >= a.ntiles) return;  // padding workgroup: leaves before any barrier
     tile += a.tile_rot;
     if (tile >= a.ntiles) tile -= a.ntiles;
-    const int sb = tail.slot(a, b, tile);
-    // everything the slot index leads to is requested at once (one memory round trip, not one per dependent step): the table's range,
-    // the noise row's lengths; a.per > 0 (device-built tables in fixed-size slots): the range begins at (slot0 + sb) * per
-    const int nn = a.nnoise[sb], nh = a.nharvey[sb];
-    const int mend = a.offsets[2 * sb + 1];
-    const int mbeg = a.per > 0 ? (a.slot0 + sb) * a.per : a.offsets[2 * sb];
-    if (nn > 0)  // else: empty evaluation slot (a candidate that was not built, or whose table failed)
-        tile_compute<MODE, WGS, K, WRITE_MODEL, DELTA, Tail::coherent_partials>(a, tile, b, sb, S, mbeg, mend, nh, nn);
-    tail(b, tile, sb);
+    SlotWords w;
+    double xpre[Tail::early_loads ? K : 1];
+    if constexpr (Tail::early_loads) {
+#pragma unroll
+        for (int k = 0; k < K; k++) xpre[k] = a.x[min(tile * (WGS * K) + k * WGS + (int)threadIdx.x, a.Nx - 1)];
+        w = tail.head(a, b, tile);
+    } else w = slot_words(a, tail.slot(a, b, tile));
+    if (w.nn > 0)  // else: empty evaluation slot (a candidate that was not built, or whose table failed)
+        tile_compute<MODE, WGS, K, WRITE_MODEL, DELTA, Tail>(a, tile, b, w.sb, S, w.mbeg, w.mend, w.nh, w.nn, tail, Tail::early_loads ? xpre : nullptr);
+    tail(b, tile, w.sb);
 }
 
 }  // namespace tile
