@@ -357,7 +357,6 @@ struct StepTiles {
     const FusedArgs *gf;
     long it;
     int q, first, settled, pairA;
-    static constexpr bool coherent_partials = false;
     static constexpr bool early_loads = true;
     // The chain's slot and what it leads to.  A chain outside iteration it-1's swap pair proposes from slot 2m (that iteration rejected)
     // or 2m + 1 (accepted): both slots' words are requested before the decision's own loads and selected after it -- one memory round
@@ -381,7 +380,6 @@ struct StepTiles {
         const ConstFused &f = *(const ConstFused *)uniform_ptr(gf);
         f.psum[((size_t)q * a.C + first + b) * a.ntiles + tile] = s0 + s1;
     }
-    __device__ __forceinline__ void operator()(int, int, int) const {}
 };
 
 // The three kinds of work on one candidate (see candidate_role); the proposal vector is in LDS.

@@ -22,7 +22,6 @@ struct LoglikeArgs {
     long *dbg = nullptr;  // phase stamps of one workgroup / per-workgroup timeline
 #endif
     int tile_rot = 0;     // tile dispatched first (launch order wraps around); any value in [0, ntiles) gives the same results
-    int prio_b = -1;      // >= 0: evaluations prio_b and prio_b+1 are dispatched first (B >= 3); results do not depend on it
     const tamcmc_multiplet *mults;  // concatenated multiplet tables
     int per = 0, slot0 = 0;         // per > 0: evaluation b's table begins at row (slot0 + slot) * per (fixed-size slots, device-built tables)
     const int32_t *offsets;         // [2B] (begin,end) multiplet range per evaluation
@@ -72,7 +71,7 @@ inline int pick_tile_rot(const tamcmc_multiplet *m, int n, double x0, double ste
 
 int tile_bins(int wgs, int K);       // bins per workgroup = workgroup size x bins per thread
 bool valid_geometry(int wgs, int K);  // (256; 1,2,4) or (64; 4,8,16)
-bool delta_geometry(int wgs, int K);  // geometries the DELTA variant is instantiated for: (256,4), (64,8)
+bool delta_geometry(int wgs, int K);  // geometries the DELTA variant is instantiated for: (256,4), (64,8), (64,4)
 // mode = TAMCMC_PRECISION_* (0 strict, 1 fast = far-field expansion + direct near field, 2 fast without the far field)
 hipError_t launch_loglike(LoglikeArgs a, int mode, int wgs, int K, bool write_model, hipStream_t st);
 // DELTA variant (FAST modes only): a.d_* / a.model0 must be set

@@ -41,7 +41,7 @@ constexpr int WG = 256;  // k_finalize / k_bg_poly; k_loglike's workgroup size i
 template <int MODE, int WGS, int K, bool WRITE_MODEL, bool DELTA = false>
 __global__ void __launch_bounds__(WGS) k_loglike(const LoglikeArgs a) {
     __shared__ TileLds<MODE, WGS> lds;
-    loglike_tile<MODE, WGS, K, WRITE_MODEL, DELTA>(a, (int)blockIdx.x, lds, NoTail());
+    loglike_tile<MODE, WGS, K, WRITE_MODEL, DELTA>(a, (int)blockIdx.x, lds, DirectSlots());
 }
 
 // Background series of every (evaluation, tile) of a launch: one thread each (bg_series.h).
@@ -87,7 +87,9 @@ __global__ void __launch_bounds__(64) k_fd_moments(const double *x, const double
     __shared__ double s_m[64][FD_MOM + 1];
     const int tile = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
     const int t0 = tile * tile_bins_;
-    const double h = 0.5 * (double)tile_bins_ * step, xc = x0 + ((double)t0 + 0.5 * (double)tile_bins_ - 0.5) * step, inv_h = 1.0 / h;
+    double xc, h;
+    bg::tile_geometry(tile, tile_bins_, x0, step, xc, h);
+    const double inv_h = 1.0 / h;
     double m1[NC], m2[2 * NC - 1], rmax = 0.0;
 #pragma unroll
     for (int k = 0; k < NC; k++) m1[k] = 0.0;
@@ -118,14 +120,14 @@ __global__ void __launch_bounds__(64) k_fd_moments(const double *x, const double
         }
     }
 #pragma unroll
-    for (int k = 0; k < NC; k++) s_m[lane][k] = m1[k];
+    for (int k = 0; k < NC; k++) s_m[lane][FD_W1 + k] = m1[k];
 #pragma unroll
-    for (int k = 0; k < 2 * NC - 1; k++) s_m[lane][NC + k] = m2[k];
-    s_m[lane][FD_MOM - 1] = rmax;
+    for (int k = 0; k < 2 * NC - 1; k++) s_m[lane][FD_W2 + k] = m2[k];
+    s_m[lane][FD_RMAX] = rmax;
     __syncthreads();
     if (lane < FD_MOM) {  // lanes in order: deterministic
         double v = s_m[0][lane];
-        if (lane == FD_MOM - 1) {
+        if (lane == FD_RMAX) {
             for (int r = 1; r < 64; r++) v = fmax(v, s_m[r][lane]);
         } else
             for (int r = 1; r < 64; r++) v = v + s_m[r][lane];
@@ -135,9 +137,10 @@ __global__ void __launch_bounds__(64) k_fd_moments(const double *x, const double
 }
 
 // The far-only tiles of the light evaluations of a DELTA launch, one LANE per tile (see launch_fd_far, kernels.h).  A tile is taken when
-// every row of the evaluation's delta table that overlaps it covers it and lies in its far field -- the staging pass's own criteria
-// (loglike_tile.h) -- and its polynomial is small enough for the moment form (sum|c_k| max(1/M0) <= 1e-5); its 16 coefficients are the
-// far-field recurrences of tile_compute, summed over the rows in table order, then the dot products with the tile's moments.
+// every row of the evaluation's delta table that overlaps it covers it and lies in its far field -- the staging pass's criteria, by the
+// staging pass's functions (loglike_tile.h) -- and its polynomial is small enough for the moment form (moment_form_holds); its 16
+// coefficients are the far-field recurrences of the tile (far_coefs, full length here), summed over the rows in table order, then the dot
+// products with the tile's moments.
 constexpr int FAR_ROWS = 16, FAR_WAVES = 4, FAR_WG = 64 * FAR_WAVES;
 // grid (evaluations, chunks of 64 tiles); the four waves of a workgroup share the rows of the delta table (row r on wave r mod 4: the
 // longest evaluation's chain of 16 rows x 7 components was the kernel's duration), wave 0 adds their coefficient vectors in wave order
@@ -162,13 +165,13 @@ __global__ void __launch_bounds__(FAR_WG) k_fd_far(const LoglikeArgs a, const in
         for (int i = tid; i < nrows * (int)(sizeof(tamcmc_multiplet) / 8); i += FAR_WG) dst[i] = src[i];
     }
     __syncthreads();
-    const double h = 0.5 * (double)tile_bins_ * a.step;
     const int t0 = tile * tile_bins_, t1 = min(t0 + tile_bins_, a.Nx);
+    double xc, h;
+    bg::tile_geometry(tile, tile_bins_, a.x0, a.step, xc, h);
     bool take = tile < a.ntiles && !(t1 <= lo || t0 >= hi);
     double fc[NC];
 #pragma unroll
     for (int k = 0; k < NC; k++) fc[k] = 0.0;
-    const double xc = a.x0 + ((double)t0 + 0.5 * (double)tile_bins_ - 0.5) * a.step;
     for (int r = wave; r < nrows; r += FAR_WAVES) {
         if (!__any(take)) break;  // (wave-uniform)
         const tamcmc_multiplet &g = s_rows[r];  // the same row in every lane (LDS broadcast): degree and asymmetry are wave-uniform
@@ -176,47 +179,27 @@ __global__ void __launch_bounds__(FAR_WG) k_fd_far(const LoglikeArgs a, const in
         const bool asym = __builtin_amdgcn_readfirstlane(g.asym != 0.0 ? 1 : 0) != 0;
         bool act = take && (g.i0 < t1) && (g.i1 > t0);        // no overlap: contributes nothing to this tile
         if (act && !(g.i0 <= t0 && g.i1 >= t1)) { take = false; act = false; }  // a window edge inside the tile: near field
-        const double ig = 2.0 * rcp_nr2(g.gamma), beta = ig * h, beta2 = beta * beta;
-        const double r2 = asym ? RHO_MAX2_ASYM : RHO_MAX2;
+        const double ig = far_ig(g), beta = ig * h, beta2 = beta * beta;
+        const double r2 = far_rho2_max(asym);
         double Am[7];
 #pragma unroll
         for (int m = 0; m < 7; m++) {
-            Am[m] = ig * (g.nu[m] - xc);
-            if (act && m < nm && !(beta2 <= r2 * fma(Am[m], Am[m], 1.0))) { take = false; act = false; }
+            Am[m] = far_arg(ig, g.nu[m], xc);
+            bool far = true;
+            far_component(far, act && m < nm, beta2, r2, Am[m]);
+            if (!far) { take = false; act = false; }
         }
         if (!__any(act)) continue;
-        const double ifc = rcp_nr2(g.fc), c2 = 0.5 * g.gamma * g.asym * ifc, c2sq = c2 * c2, fcx = g.asym * ifc;
-        const double p0 = fma(fcx, xc, 1.0 - g.asym), p1 = fcx * h;
-        const double A0 = fma(p0, p0, c2sq), A1 = 2.0 * p0 * p1, A2 = p1 * p1;
+        double c2sq, fcx;
+        fast_asym_scalars(g, c2sq, fcx);
+        const AsymPoly P = asym_poly(fcx, g.asym, c2sq, xc, h);
 #pragma unroll
         for (int m = 0; m < 7; m++) {
             if (m >= nm) break;  // (uniform)
-            const double A = Am[m];
-            const double inv = rcp_nr2(fma(A, A, 1.0));
-            const double two_req = 2.0 * beta * A * inv, q2 = beta * beta * inv;
-            double cm = act ? g.hv[m] * inv : 0.0, cc = cm * two_req;  // (a lane that does not take this row adds zeros)
-            if (!asym) {
-                fc[0] = fc[0] + cm;
-                fc[1] = fc[1] + cc;
-#pragma unroll
-                for (int k = 2; k < NC; k++) {
-                    const double cn = fma(two_req, cc, -q2 * cm);
-                    fc[k] = fc[k] + cn;
-                    cm = cc;
-                    cc = cn;
-                }
-            } else {
-                double c2k = 0.0, c1 = 0.0, c0k = cm;
-                const double nxt = cc;
-#pragma unroll
-                for (int k = 0; k < NC; k++) {
-                    fc[k] = fc[k] + fma(A0, c0k, fma(A1, c1, A2 * c2k));
-                    const double cn = (k == 0) ? nxt : fma(two_req, c0k, -q2 * c1);
-                    c2k = c1;
-                    c1 = c0k;
-                    c0k = cn;
-                }
-            }
+            FarSeed f = far_seed(g.hv[m], Am[m], beta);
+            if (!act) f.c0 = 0.0;  // (a lane that does not take this row adds zeros)
+            if (!asym) far_coefs<false>(f, fc);
+            else far_coefs_asym(f, P, fc);
         }
     }
 #pragma unroll
@@ -238,16 +221,16 @@ __global__ void __launch_bounds__(FAR_WG) k_fd_far(const LoglikeArgs a, const in
         double ab = 0.0;
 #pragma unroll
         for (int k = 0; k < NC; k++) ab = ab + fabs(fc[k]);
-        if (ab * mm[(FD_MOM - 1) * ms] <= 1e-5) {
+        if (moment_form_holds(ab, mm[FD_RMAX * ms])) {
 #pragma unroll
-            for (int k = 0; k < NC; k++) tot = fma(fc[k], mm[k * ms], tot);
+            for (int k = 0; k < NC; k++) tot = fma(fc[k], mm[(FD_W1 + k) * ms], tot);
 #pragma unroll
             for (int m = 0; m < 2 * NC - 1; m++) {
                 double cv = 0.0;
 #pragma unroll
                 for (int j = 0; j < NC; j++)
                     if (m - j >= 0 && m - j < NC) cv = fma(fc[j], fc[m - j], cv);
-                tot = fma(cv, mm[(NC + m) * ms], tot);
+                tot = fma(cv, mm[(FD_W2 + m) * ms], tot);
             }
         } else take = false;
     }
@@ -281,6 +264,20 @@ bool launch_geom(const LoglikeArgs &a, int wgs, int K, bool write_model, int gri
     return true;
 }
 
+// Launch geometry of (Nx, wgs, K, B): bins per tile, tiles, and the workgroups of a tile launch -- the tiles padded to a multiple of 8
+// (the XCD mapping of loglike_tile) times the evaluations.
+struct TileGrid {
+    int tile_bins, ntiles;
+    long long grid;
+    TileGrid(int Nx, int wgs, int K, int B) : tile_bins(wgs * K), ntiles((Nx + tile_bins - 1) / tile_bins), grid((long long)((ntiles + 7) / 8 * 8) * B) {}
+    // fills the launch's part of the argument block; false: the grid is beyond 2^31 - 1 workgroups
+    bool prepare(LoglikeArgs &a) const {
+        a.ntiles = ntiles;
+        if (a.tile_rot < 0 || a.tile_rot >= ntiles) a.tile_rot = 0;
+        return grid <= 0x7fffffffLL;
+    }
+};
+
 }  // namespace
 
 int tile_bins(int wgs, int K) { return wgs * K; }
@@ -291,16 +288,12 @@ bool valid_geometry(int wgs, int K) {
 hipError_t launch_loglike(LoglikeArgs a, int mode, int wgs, int K, bool write_model, hipStream_t st) {
     if (a.B <= 0) return hipSuccess;
     if (!valid_geometry(wgs, K)) return hipErrorInvalidValue;
-    const int tb = wgs * K;
-    a.ntiles = (a.Nx + tb - 1) / tb;
-    const int ntiles_pad = ((a.ntiles + 7) / 8) * 8;
-    const long long grid = (long long)ntiles_pad * a.B;
-    if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-    if (a.tile_rot < 0 || a.tile_rot >= a.ntiles) a.tile_rot = 0;
+    const TileGrid g(a.Nx, wgs, K, a.B);
+    if (!g.prepare(a)) return hipErrorInvalidValue;
     bool ok;
-    if (mode == M_FAST) ok = launch_geom<M_FAST>(a, wgs, K, write_model, (int)grid, st);
-    else if (mode == M_FAST_DIRECT) ok = launch_geom<M_FAST_DIRECT>(a, wgs, K, write_model, (int)grid, st);
-    else ok = launch_geom<M_STRICT>(a, wgs, K, write_model, (int)grid, st);
+    if (mode == M_FAST) ok = launch_geom<M_FAST>(a, wgs, K, write_model, (int)g.grid, st);
+    else if (mode == M_FAST_DIRECT) ok = launch_geom<M_FAST_DIRECT>(a, wgs, K, write_model, (int)g.grid, st);
+    else ok = launch_geom<M_STRICT>(a, wgs, K, write_model, (int)g.grid, st);
     if (!ok) return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -319,13 +312,9 @@ bool delta_geometry(int wgs, int K) { return (wgs == 256 && K == 4) || (wgs == 6
 hipError_t launch_loglike_delta(LoglikeArgs a, int mode, int wgs, int K, hipStream_t st) {
     if (a.B <= 0) return hipSuccess;
     if (!delta_geometry(wgs, K) || mode == M_STRICT || !a.d_range || !a.d_flags || !a.d_noise_old || !a.d_row || !a.model0) return hipErrorInvalidValue;
-    const int tb = wgs * K;
-    a.ntiles = (a.Nx + tb - 1) / tb;
-    const int ntiles_pad = ((a.ntiles + 7) / 8) * 8;
-    const long long grid = (long long)ntiles_pad * a.B;
-    if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-    if (a.tile_rot < 0 || a.tile_rot >= a.ntiles) a.tile_rot = 0;
-    const bool ok = (mode == M_FAST) ? launch_geom_delta<M_FAST>(a, wgs, K, (int)grid, st) : launch_geom_delta<M_FAST_DIRECT>(a, wgs, K, (int)grid, st);
+    const TileGrid g(a.Nx, wgs, K, a.B);
+    if (!g.prepare(a)) return hipErrorInvalidValue;
+    const bool ok = (mode == M_FAST) ? launch_geom_delta<M_FAST>(a, wgs, K, (int)g.grid, st) : launch_geom_delta<M_FAST_DIRECT>(a, wgs, K, (int)g.grid, st);
     if (!ok) return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -333,20 +322,18 @@ hipError_t launch_loglike_delta(LoglikeArgs a, int mode, int wgs, int K, hipStre
 hipError_t launch_bg_poly(const LoglikeArgs &a, int wgs, int K, double *bg, hipStream_t st) {
     if (a.B <= 0) return hipSuccess;
     if (!valid_geometry(wgs, K) || !bg) return hipErrorInvalidValue;
-    const int tb = wgs * K;
-    const int ntiles = (a.Nx + tb - 1) / tb;
-    const long n = (long)a.B * ntiles;
-    hipLaunchKernelGGL(k_bg_poly, dim3((unsigned)((n + WG - 1) / WG)), dim3(WG), 0, st, a.noise, a.noise_stride, a.nharvey, a.nnoise, a.B, ntiles, tb,
-                       a.x0, a.step, bg);
+    const TileGrid g(a.Nx, wgs, K, a.B);
+    const long n = (long)a.B * g.ntiles;
+    hipLaunchKernelGGL(k_bg_poly, dim3((unsigned)((n + WG - 1) / WG)), dim3(WG), 0, st, a.noise, a.noise_stride, a.nharvey, a.nnoise, a.B, g.ntiles,
+                       g.tile_bins, a.x0, a.step, bg);
     return hipGetLastError();
 }
 
 hipError_t launch_fd_moments(const LoglikeArgs &a, int wgs, int K, double *mom, double *momT, hipStream_t st) {
     if (a.B <= 0) return hipSuccess;
     if (!valid_geometry(wgs, K) || !mom || !momT || !a.fd_rows) return hipErrorInvalidValue;
-    const int tb = wgs * K;
-    const int ntiles = (a.Nx + tb - 1) / tb;
-    static_assert(FD_MOM == NC + (2 * NC - 1) + 1, "moment layout");
+    const TileGrid g(a.Nx, wgs, K, a.B);
+    const int tb = g.tile_bins, ntiles = g.ntiles;
     if (tb == 256) hipLaunchKernelGGL(k_fd_moments<4>, dim3(ntiles, a.B), dim3(64), 0, st, a.x, a.fd_rows, a.fd_plane, a.Nx, ntiles, tb, a.x0, a.step, mom, momT);
     else if (tb == 512) hipLaunchKernelGGL(k_fd_moments<8>, dim3(ntiles, a.B), dim3(64), 0, st, a.x, a.fd_rows, a.fd_plane, a.Nx, ntiles, tb, a.x0, a.step, mom, momT);
     else if (tb == 1024) hipLaunchKernelGGL(k_fd_moments<16>, dim3(ntiles, a.B), dim3(64), 0, st, a.x, a.fd_rows, a.fd_plane, a.Nx, ntiles, tb, a.x0, a.step, mom, momT);
@@ -358,9 +345,9 @@ hipError_t launch_fd_far(const LoglikeArgs &d, int wgs, int K, unsigned char *do
     if (d.B <= 0) return hipSuccess;
     if (!delta_geometry(wgs, K) || !done || !d.fd_momT || !d.d_range || !d.d_flags || !d.d_row) return hipErrorInvalidValue;
     LoglikeArgs a = d;
-    const int tb = wgs * K;
-    a.ntiles = (a.Nx + tb - 1) / tb;
-    hipLaunchKernelGGL(k_fd_far, dim3(a.B, (a.ntiles + 63) / 64), dim3(FAR_WG), 0, st, a, tb, done);
+    const TileGrid g(a.Nx, wgs, K, a.B);
+    a.ntiles = g.ntiles;
+    hipLaunchKernelGGL(k_fd_far, dim3(a.B, (g.ntiles + 63) / 64), dim3(FAR_WG), 0, st, a, g.tile_bins, done);
     return hipGetLastError();
 }
 
