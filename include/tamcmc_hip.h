@@ -78,9 +78,10 @@ extern "C" {
 #define TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC_V3 13 /* model_MS_Global_a1etaa3_HarveyLike_Classic_v3, models.cpp:2338 */
 #define TAMCMC_MODEL_MS_LOCAL_HNLM 14                /* model_MS_local_Hnlm, models.cpp:3198 */
 #define TAMCMC_MODEL_MS_GLOBAL_AJ 23             /* model_MS_Global_aj_HarveyLike, models.cpp:1195 */
-#define TAMCMC_MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4 25 /* model_RGB_asympt_aj_AppWidth_HarveyLike_v4, models.cpp:4684: only through
-                                                    tamcmc_hip_loglike_params_batch (its table needs the device pre-step:
-                                                    ARMM mixed-mode solver + zeta function, csrc/rgb_prestep.hip) */
+#define TAMCMC_MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4 25 /* model_RGB_asympt_aj_AppWidth_HarveyLike_v4, models.cpp:4684: through
+                                                    tamcmc_hip_loglike_params_batch and the tamcmc_hip_fd_gradient* entry points
+                                                    (its table needs the device pre-step: ARMM mixed-mode solver + zeta function,
+                                                    csrc/rgb_prestep.hip; tamcmc_build_mode_table: TAMCMC_ERR_BAD_MODEL) */
 #define TAMCMC_MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4 27 /* model_RGB_asympt_aj_CteWidth_HarveyLike_v4, models.cpp:4334: same path, one
                                                     constant width for the l=0,2,3 modes */
 
@@ -204,14 +205,29 @@ int tamcmc_hip_rgb_mixed_modes(tamcmc_hip_ctx *ctx, int model_id, const double *
  * omitted is below 1e-10 of the leading term).  Against the brute-force difference of two full evaluations it agrees to that
  * difference's own cancellation noise (~5e-15 Nx / h) + 1e-6 of the gradient's scale (tests/test_gpu_parity.py).
  * Ids 0 and 1: every parameter moves every bin, so the batch is brute force -- C x (Nvars+1) full evaluations in one batched launch
- * (C x (Nvars+1) <= 65535), grad = (logL(theta + h e_k) - logL(theta)) / h_applied; plength is not read. */
+ * (C x (Nvars+1) <= 65535), grad = (logL(theta + h e_k) - logL(theta)) / h_applied; plength is not read.
+ * Ids 25 and 27 (red giants): each of the C x (Nvars+1) <= 65535 vectors goes through the device pre-step (scalar unpack beside the prior in
+ * the batch's first kernel, then mixed-mode solver, zeta and rows), in chunks when their workspace (~28 KB per vector) would pass 256 MiB;
+ * one likelihood launch over all tables (brute force: STRICT always, FAST with TAMCMC_OPT_FD_WINDOWED = 0) or the windowed pipeline above
+ * (FAST, the default: at the C5 shape, 2e5 bins x 40 chains x 62 vectors, 8.2 ms against 10.4 ms brute force and 19.3 ms for the same vectors
+ * through 62 tamcmc_hip_loglike_params_batch calls), where a perturbation that moves the mixed modes (period spacing, coupling, large separation, rotation, ...) is a
+ * "full table" evaluation.  A perturbation may change the NUMBER of mixed modes; the tables are then compared row against absent row.
+ * A vector the pre-step refuses (a negative large separation, more than 400 mixed modes, ...) makes the call return that status with
+ * grad = NaN for this component (logL0 = NaN when it is the base point); the other components are unaffected.
+ * Tolerance: the red-giant tolerance above carries into the differences -- each of the two log-likelihoods is within tol of the oracle's, so
+ * |d grad| <= 2 tol |logL| / h with tol = 1e-11 (STRICT) / the FAST tolerance; windowed against brute force as for the other models.
+ * STRICT: the scalar unpack of the vectors is the host's, in long double like the reference's, so logL0 and every difference are the very
+ * bits of tamcmc_hip_loglike_params_batch on the same vectors.  FAST modes: the unpack runs on the device in double and agrees with that
+ * entry to rounding (a few ulp of logL), not bit for bit (tests/test_gpu_rgb_gradient.py). */
 int tamcmc_hip_fd_gradient(tamcmc_hip_ctx *ctx, int model_id, int C, const double *params, int64_t Nparams,
                            const int32_t *plength, const int32_t *index_to_relax, int Nvars, const double *hstep,
                            const double *Tcoefs, double p, double *logL0, double *grad);
 
 /* Same batch, gradient of the tempered log-POSTERIOR: each of the C*(Nvars+1) workgroups also evaluates the log-prior of
- * its perturbed vector on the device (prior_class 2 = io_MS_Global, 3 = io_local, 0 = priors_Kallinger2014_Gaussian with model id 0,
- * 1 = priors_Harvey_Gaussian with model id 1 -- these two on the device in double, one thread per point, extra_priors not read;
+ * its perturbed vector on the device (prior_class 2 = io_MS_Global, 3 = io_local, 4 = io_asymptotic with model ids 25 / 27 and only
+ * with them -- generic terms one per lane, constraints and the ordered sum by one lane, in double --, 0 = priors_Kallinger2014_Gaussian
+ * with model id 0, 1 = priors_Harvey_Gaussian with model id 1 -- these two on the device in double, one thread per point, extra_priors
+ * not read; any other pairing: TAMCMC_ERR_BAD_MODEL;
  * priors = 4 x Nparams row-major table,
  * priors_switch = primitive ids, extra_priors[10]: Input_Data of tamcmc/headers/data.h:51-62).  Where the forward point
  * leaves a prior's support the backward difference of the prior is used, else that prior term is flat.

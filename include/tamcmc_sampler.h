@@ -81,7 +81,8 @@ int64_t tamcmc_sampler_nvars(const tamcmc_sampler *s);
  *   Nparams + 2 Nvars, device      <= 971                the fused one-launch iteration borrows the likelihood tile's 12 KB of LDS for its
  *     engine, fused step                                 candidate roles; longer vectors run every iteration on the lockstep kernels
  *                                                        (TAMCMC_INFO_FUSED_AVAILABLE = 0) -- same chains bit for bit
- *   red-giant models (ids 25/27)   lockstep kernels only; no Langevin step (use_drift = 1 -> TAMCMC_ERR_BAD_MODEL)
+ *   red-giant models (ids 25/27)   device engine: lockstep kernels only, no Langevin step (engine = 1 with use_drift = 1 ->
+ *                                  TAMCMC_ERR_BAD_MODEL); host-driven engine: random walk or Langevin (tamcmc_hip_fd_gradient_posterior)
  *   Gaussian-envelope models       host-driven engine only (random walk or Langevin); engine = 1 -> TAMCMC_ERR_BAD_MODEL at
  *     (ids 0/1)                    tamcmc_sampler_create
  * The host-driven engine has no size-dependent branches (host memory, column Cholesky).

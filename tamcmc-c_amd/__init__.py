@@ -24,7 +24,7 @@ MODEL_MS_GLOBAL_A1ETAA3_CLASSIC, MODEL_MS_LOCAL_BASIC, MODEL_MS_GLOBAL_AJ = 3, 1
 # (model level only) / the same for a local fit
 MODEL_MS_GLOBAL_A1ETAA3_CLASSIC_V2, MODEL_MS_GLOBAL_A1ETAA3_CLASSIC_V3, MODEL_MS_LOCAL_HNLM = 12, 13, 14
 MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4 = 27   # constant-width variant of 25, same path
-MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4 = 25  # batched device path only (tamcmc_hip_loglike_params_batch): needs the ARMM pre-step
+MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4 = 25  # batched device paths only (loglike_params_batch, fd_gradient*): needs the ARMM pre-step
 PRECISION_STRICT, PRECISION_FAST, PRECISION_FAST_DIRECT = 0, 1, 2
 OPT_PRECISION, OPT_TIMING, OPT_BINS_PER_THREAD, OPT_WORKGROUP, OPT_FD_WINDOWED, OPT_STEP_SCHEME, OPT_ARMM_DENSE_SCAN = 1, 2, 3, 4, 5, 6, 7
 OPT_QUICK_DECIDE = 8  # test facility: 1 = the fused step's decision shortcut always falls back to the exact evaluation
@@ -212,6 +212,8 @@ class HipContext:
         return logL, model, status
 
     def fd_gradient(self, model_id, params, plength, index_to_relax, hstep, Tcoefs=None, p=1.0):
+        """(logL0 [C], grad [C x Nvars]) of the tempered log-likelihood by forward differences, one device-built batch.  Every Lorentzian
+        model id with a device table builder, the red giants (25, 27: tables through the device pre-step) and the envelope fits (0, 1)."""
         params = _f64(params)
         if params.ndim == 1:
             params = params[None, :]
@@ -226,7 +228,8 @@ class HipContext:
         return l0, g
 
     def fd_gradient_posterior(self, star, params, hstep, Tcoefs=None, p=1.0):
-        """Gradient of the tempered log-posterior of `star`'s model at each row of params (device-built FD batch)."""
+        """Gradient of the tempered log-posterior of `star`'s model at each row of params (device-built FD batch); the prior class must
+        be the model's own (red giants, ids 25 / 27: class 4).  The prior's share is left in self.last_grad_prior."""
         params = _f64(params)
         if params.ndim == 1:
             params = params[None, :]

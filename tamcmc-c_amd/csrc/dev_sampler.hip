@@ -257,7 +257,9 @@ int DevSampler::init(tamcmc_hip_ctx *c, const DevSamplerInit &in) {
         I.G = G;
     }
     if (I.rgb) {
-        if (I.use_drift) return TAMCMC_ERR_BAD_MODEL;  // the finite-difference builder has no red-giant pre-step
+        // the finite-difference batch builds red-giant tables now (fd_batch.hip); what this engine's Langevin step still lacks is its
+        // candidate tables through the pre-step (k_mala_settle's proposals are unpacked by wg_unpack, which knows no mixed modes)
+        if (I.use_drift) return TAMCMC_ERR_BAD_MODEL;
         I.rgb_bmax = (in.C + I.G - 1) / I.G;
         int rc = rgb_device_prepare(c, I.rgb_bmax, I.G, in.plength, &a.desc.per, &a.desc.stride);  // one workspace slice per chain group
         if (rc) return rc;

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "ctx.h"
+#include "fd_rgb_chunk.h"
 
 namespace tamcmc {
 
@@ -13,6 +14,13 @@ struct FdBatch {
     int model_id = 0, prior_class = 0, C = 0, E = 0, B = 0, Nvars = 0, per = 0, stride = 1, ntiles = 0;
     int64_t Np = 0;
     bool windowed = false;
+    bool rgb = false;  // red-giant models (ids 25 / 27): tables through the device pre-step, `chunk` vectors at a time
+    int chunk = 0;
+    // red giants: the host's long-double scalar unpack of the B vectors (rgb::Prep[B], rgb::RowIn[B], the table block's header with counts
+    // and noise rows; pinned memory that outlives the launches), uploaded by enqueue instead of the device unpack; nullptr: the device
+    // unpacks, in double.  STRICT promises the reference's long-double unpack, so under STRICT enqueue() REQUIRES these (it returns
+    // TAMCMC_ERR_BAD_ARG without them): a caller whose vectors live on the device only cannot run a STRICT red-giant batch.
+    const void *h_prep = nullptr, *h_rows = nullptr, *h_header = nullptr;
     // offsets inside the device block: host-filled constants [0, in_bytes), results [in_bytes, in_bytes + out_bytes), tables after
     size_t o_params = 0, o_h = 0, o_pr = 0, o_ex = 0, o_pl = 0, o_idx = 0, o_sw = 0, in_bytes = 0;
     size_t o_lpp = 0, o_lpm = 0, o_st = 0, out_bytes = 0;

@@ -7,8 +7,12 @@
 // edge of a prior's support) and writes its multiplet table straight into the likelihood kernel's input block:
 //   k_fd_unpack (C*(Nvars+1) workgroups) -> k_loglike (one launch, B = C*(Nvars+1)) -> k_finalize,
 // or, windowed (FAST arithmetic: the default):
-//   k_fd_unpack (tables + delta tables) -> k_loglike on the C base points (planes 1/M0, y/M0, M0 kept) -> k_fd_moments (tile moments of the
-//   base points) -> k_fd_far (far-only tiles of the light evaluations from the moments) -> k_loglike<DELTA> (everything else) -> k_finalize.
+//   k_fd_unpack (tables) -> k_fd_compare (delta tables) -> k_loglike on the C base points (planes 1/M0, y/M0, M0 kept) -> k_fd_moments (tile
+//   moments of the base points) -> k_fd_far (far-only tiles of the light evaluations from the moments) -> k_loglike<DELTA> (everything else)
+//   -> k_finalize.
+// Red-giant models (ids 25 / 27): the table of a vector needs the mixed-mode solver, so k_fd_unpack's place is taken by
+//   k_fd_rgb_perturb (perturbed vector, class-4 log-prior, scalar unpack into the pre-step workspace) -> rgb_device_stage (solver, rows),
+// in chunks of vectors through ONE workspace slice; everything after the tables is the same.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -20,6 +24,7 @@
 #include "dev_unpack.h"
 #include "kernels.h"
 #include "fd_batch.h"
+#include "rgb_prestep.h"
 
 namespace tamcmc {
 namespace {
@@ -40,9 +45,10 @@ struct FdArgs {
     double *logPr_plus;    // [C x E] log-prior at the evaluation point (e=0: the base point)
     double *logPr_minus;   // [C x E] log-prior at theta - h e_k (e>=1)
     int *status;           // [C x E]
-    // windowed mode (delta tables): rows [B*per, 2B*per) of T.mults hold each block's copy of the BASE table,
+    // windowed mode (delta tables): rows [B*per, 2B*per) of T.mults hold each block's copy of the BASE table (red giants: no copies,
+    // the base table of chain c is slot c*E itself: base_copies = 0),
     // D is the delta launch's input block (2*per rows per evaluation: +new / -old of the changed multiplets)
-    int windowed;
+    int windowed, base_copies;
     TablePtrs D;
     int *d_range, *d_flags, *d_row;
     double *d_noise_old;
@@ -56,17 +62,16 @@ __global__ void __launch_bounds__(FB) k_fd_unpack(const FdArgs a) {
     double *s_params = (double *)s_raw;
     const UnpackLds U = carve_unpack_lds((unsigned char *)(s_params + Np));
     const int slot = blockIdx.x, c = slot / a.E, e = slot - c * a.E, tid = threadIdx.x;
-    const int B = a.C * a.E, per = a.desc.per;
-    __shared__ int s_lo, s_hi, s_nchg, s_noise_chg, s_base_status;
+    const int B = a.C * a.E;
     for (int i = tid; i < Np; i += FB) s_params[i] = a.params[(size_t)c * Np + i];
     unpack_begin(a.desc, U);
     if (a.windowed && e > 0) {
-        // this block's own copy of the BASE table (slot B+slot): the changed rows are found by comparing with it
+        // this block's own copy of the BASE table (slot B+slot): k_fd_compare finds the changed rows by comparing with it
         if (tid == FB - 1) mt::shared_scalars_base(a.desc.model_id, s_params, a.desc.plength, *U.S);
         __syncthreads();
         wg_unpack(a.desc, s_params, U, B + slot, a.T, true);
         __syncthreads();
-        if (tid == 0) { s_base_status = *U.status; *U.status = TAMCMC_OK; *U.reject = 0; }
+        if (tid == 0) { *U.status = TAMCMC_OK; *U.reject = 0; }
         __syncthreads();
     }
     const bool with_prior = a.desc.prior_class != 0;
@@ -100,9 +105,104 @@ __global__ void __launch_bounds__(FB) k_fd_unpack(const FdArgs a) {
         lp_minus = wg_log_prior(a.desc, s_params, U, false);
     }
     if (tid == 0) a.logPr_minus[slot] = lp_minus;
-    if (!a.windowed) return;
+}
+
+// Red-giant models (ids 25 / 27), the counterpart of k_fd_unpack up to the table: one workgroup per slot of the chunk [slot0, slot0 + gridDim.x).
+// The perturbed vector is staged in LDS; its class-4 log-prior is evaluated as the device sampler's proposal kernel does (generic terms one
+// per lane of the first wave, then pr::prior_serial's constraints, ordered sum and smoothness tail by lane 0) while the second wave runs the scalar unpack
+// (rgb_unpack.h) of the same vector into entry blockIdx.x of the pre-step workspace slice; rgb_device_stage builds the table from there.
+// The likelihood is evaluated whatever the prior says (the caller combines the parts), so an infinite prior does not empty the entry.
+// host_unpack (STRICT, host entry): the workspace entries, noise rows and counts were filled by the host's long-double unpack and uploaded
+// (fd_run); the kernel then only evaluates the prior and resets the solver's counters.
+__global__ void __launch_bounds__(FB) k_fd_rgb_perturb(const FdArgs a, const rgb::Slice rs, const int slot0, const int host_unpack) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+    const int Np = a.desc.Np;
+    double *s_params = (double *)s_raw;
+    mt::xreal *terms = (mt::xreal *)(s_params + Np);  // [Np] generic prior terms (xreal = double on the device)
+    __shared__ rgb::Prep sP;
+    __shared__ rgb::RowIn sR;
+    __shared__ double s_w[40], s_noise[3 * TAMCMC_MAX_HARVEY + 4], s_lp;
+    __shared__ int32_t s_hn[2];
+    __shared__ int s_stp;
+    const int rb = blockIdx.x, slot = slot0 + rb, c = slot / a.E, e = slot - c * a.E, tid = threadIdx.x;
+    const bool with_prior = a.desc.prior_class != 0;
+    for (int i = tid; i < Np; i += FB) s_params[i] = a.params[(size_t)c * Np + i];
+    const int ip = e > 0 ? a.idx[e - 1] : 0;
+    const double x0 = e > 0 ? a.params[(size_t)c * Np + ip] : 0.0, hh = e > 0 ? a.h[e - 1] : 0.0;
+    if (tid == 0) { s_stp = TAMCMC_OK; s_lp = 0.0; }
     __syncthreads();
-    const int stride = a.desc.stride;
+    if (e > 0 && tid == 0) s_params[ip] = x0 + hh;
+    __syncthreads();
+    // log-prior of the vector in LDS: the same value in every lane.  All of it is wave 0's -- the generic terms one per lane, a wavefront
+    // barrier, the serial tail on lane 0 -- so that it runs beside wave 1's scalar unpack; the workgroup meets at the one barrier at the end
+    auto log_prior = [&]() -> double {
+        if (tid < 64) {
+            for (int i = tid; i < Np; i += 64) {
+                int st = TAMCMC_OK;
+                terms[i] = pr::generic_prior_term(s_params, Np, a.desc.priors, a.desc.priors_switch, i, &st);
+                if (st != TAMCMC_OK) s_stp = st;
+            }
+            WaveSync()();
+            if (tid == 0) {
+                int st = s_stp;
+                s_lp = (double)pr::prior_serial(a.desc.prior_class, s_params, a.desc.plength, Np, a.desc.priors, a.desc.priors_switch, a.desc.extra, &st, terms);
+                s_stp = st;
+            }
+        }
+        __syncthreads();
+        return s_lp;
+    };
+    if ((tid >> 6) == 1 && !host_unpack) {  // wave 1: the scalar unpack (it reads s_params only), while wave 0 is in log_prior() below
+        rgb::WaveLanes x;
+        x.w = s_w;
+        double fmin;
+        rgb::unpack_vector(x, s_params, a.desc.plength, rs.step, a.desc.model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4_ID, rs.dense, sP, sR, s_noise,
+                           &s_hn[0], &s_hn[1], &fmin);
+    }
+    const double lp = with_prior ? log_prior() : 0.0;
+    __syncthreads();
+    if (host_unpack) {
+        if (tid == 0 && s_stp != TAMCMC_OK) { rs.preps[rb].status = s_stp; rs.rows[rb].status = s_stp; }
+    } else {
+        if (tid == 0 && s_stp != TAMCMC_OK) { sP.status = s_stp; sR.status = s_stp; }  // a prior the device cannot evaluate: the slot fails (status, NaN)
+        __syncthreads();
+        static_assert(sizeof(rgb::Prep) % 8 == 0 && sizeof(rgb::RowIn) % 8 == 0, "copied as doubles");
+        const double *src = (const double *)&sP;
+        double *dst = (double *)&rs.preps[rb];
+        for (int i = tid; i < (int)(sizeof(rgb::Prep) / 8); i += FB) dst[i] = src[i];
+        src = (const double *)&sR;
+        dst = (double *)&rs.rows[rb];
+        for (int i = tid; i < (int)(sizeof(rgb::RowIn) / 8); i += FB) dst[i] = src[i];
+        for (int i = tid; i < s_hn[1] && i < a.desc.stride; i += FB) a.T.noise[(size_t)slot * a.desc.stride + i] = s_noise[i];
+        if (tid == 0) {
+            a.T.nh[slot] = s_hn[0];
+            a.T.nn[slot] = s_hn[1];
+        }
+    }
+    if (tid == 0) {
+        rs.norm_bits[rb] = 0ull;
+        rs.nsol[rb] = 0;
+        a.logPr_plus[slot] = lp;
+    }
+    // the log-prior at theta - h e_k: only where the forward point lies outside a prior's support (as k_fd_unpack; workgroup-uniform)
+    double lp_minus = 0.0;
+    if (e > 0 && with_prior && !isfinite(lp)) {
+        __syncthreads();
+        if (tid == 0) s_params[ip] = x0 - hh;
+        __syncthreads();
+        lp_minus = log_prior();
+    }
+    if (tid == 0) a.logPr_minus[slot] = lp_minus;
+}
+
+// Windowed mode, after the tables: one workgroup per slot compares slot e's finished table with the chain's base table row by row and writes
+// the delta launch's input -- it reads two tables and does not care which builder made them.  The tables may differ in length (a red-giant
+// perturbation can change the number of mixed modes: every row after the first difference then differs, and the rows beyond the end of the
+// shorter table count as changed against an absent row).
+__global__ void __launch_bounds__(FB) k_fd_compare(const FdArgs a) {
+    const int slot = blockIdx.x, c = slot / a.E, e = slot - c * a.E, tid = threadIdx.x;
+    const int B = a.C * a.E, per = a.desc.per, stride = a.desc.stride;
+    __shared__ int s_lo, s_hi, s_noise_chg, s_nrows, s_wtot[FB / 64];
     if (e == 0) {
         // base evaluation of chain c: the base launch (B = C, model rows written) reads the SAME table rows
         if (tid == 0) {
@@ -118,64 +218,93 @@ __global__ void __launch_bounds__(FB) k_fd_unpack(const FdArgs a) {
         return;
     }
     // ---- delta table: the multiplets whose row differs from the base row, +new / -old, and the affected bin range ----
-    __shared__ int s_namp, s_nshape;
-    if (tid == 0) { s_lo = a.desc.Nx; s_hi = 0; s_nchg = 0; s_noise_chg = 0; s_namp = 0; s_nshape = 0; }
+    const int bs = a.base_copies ? B + slot : c * a.E;  // the slot holding the base table
+    const int n_new = a.T.pairs[2 * slot + 1] - a.T.pairs[2 * slot], n_old = a.T.pairs[2 * bs + 1] - a.T.pairs[2 * bs];
+    if (tid == 0) { s_lo = a.desc.Nx; s_hi = 0; s_noise_chg = 0; s_nrows = 0; }
     __syncthreads();
-    const bool ok = (a.status[slot] == TAMCMC_OK) && (s_base_status == TAMCMC_OK);
+    const bool ok = (a.status[slot] == TAMCMC_OK) && (n_old > 0);  // (a base table that failed is empty)
     tamcmc_multiplet *drows = a.D.mults + (size_t)slot * 2 * per;
     for (int i = tid; i < stride; i += FB) {
-        const double vn = a.T.noise[(size_t)slot * stride + i], vo = a.T.noise[(size_t)(B + slot) * stride + i];
+        const double vn = a.T.noise[(size_t)slot * stride + i], vo = a.T.noise[(size_t)bs * stride + i];
         a.D.noise[(size_t)slot * stride + i] = vn;
         a.d_noise_old[(size_t)slot * stride + i] = vo;
         if (ok && i < a.T.nn[slot] && vn != vo) s_noise_chg = 1;
     }
     // how row jdx changed: 0 not at all, 1 heights only (a parameter that only rescales heights -- inclination, visibilities, heights --
-    // leaves frequencies, width, asymmetry and window untouched: +new and -old are then ONE row with the height differences), 2 otherwise
+    // leaves frequencies, width, asymmetry and window untouched: +new and -old are then ONE row with the height differences), 2 otherwise;
+    // 3 / 4: the row exists in the perturbed / the base table only
     auto change_of = [&](int jdx) -> int {
         if (!ok || jdx >= per) return 0;
+        const bool has_n = jdx < n_new, has_o = jdx < n_old;
+        if (!has_n || !has_o) return has_n ? 3 : (has_o ? 4 : 0);
         const unsigned long long *pn = (const unsigned long long *)&a.T.mults[(size_t)slot * per + jdx];
-        const unsigned long long *po = (const unsigned long long *)&a.T.mults[(size_t)(B + slot) * per + jdx];
+        const unsigned long long *po = (const unsigned long long *)&a.T.mults[(size_t)bs * per + jdx];
         bool chg = false;
         for (int w = 0; w < (int)(sizeof(tamcmc_multiplet) / 8); w++) chg = chg || (pn[w] != po[w]);
         if (!chg) return 0;
-        const tamcmc_multiplet &rn = a.T.mults[(size_t)slot * per + jdx], &ro = a.T.mults[(size_t)(B + slot) * per + jdx];
+        const tamcmc_multiplet &rn = a.T.mults[(size_t)slot * per + jdx], &ro = a.T.mults[(size_t)bs * per + jdx];
         bool amp_only = (rn.l == ro.l) && (rn.i0 == ro.i0) && (rn.i1 == ro.i1) && (rn.fc == ro.fc) && (rn.gamma == ro.gamma) && (rn.asym == ro.asym);
         for (int m = 0; m < 7; m++) amp_only = amp_only && (rn.nu[m] == ro.nu[m]);
         return amp_only ? 1 : 2;
     };
     for (int j0 = 0; j0 < per; j0 += FB) {
         const int k = change_of(j0 + tid);
-        if (k == 1) atomicAdd(&s_namp, 1);
-        else if (k == 2) atomicAdd(&s_nshape, 1);
+        if (k) atomicAdd(&s_nrows, k == 2 ? 2 : 1);  // rows the pair table would take
     }
     __syncthreads();
     // "full table": the pairs would be longer than the perturbed point's whole table (a parameter that moves most multiplets: a splitting
-    // coefficient, the asymmetry) -- the delta launch then evaluates that table and subtracts the base model row (loglike_tile.h)
-    const bool full = ok && !s_noise_chg && a.full_tables && (s_namp + 2 * s_nshape > per);
+    // coefficient, the asymmetry, a red giant's period spacing) -- the delta launch then evaluates that table and subtracts the base model
+    // row (loglike_tile.h)
+    const bool full = ok && !s_noise_chg && a.full_tables && (s_nrows > n_new);
+    int nchg = 0;
     if (full) {
-        for (int jdx = tid; jdx < per; jdx += FB) drows[jdx] = a.T.mults[(size_t)slot * per + jdx];
+        for (int jdx = tid; jdx < n_new; jdx += FB) drows[jdx] = a.T.mults[(size_t)slot * per + jdx];
     } else
+        // the changed rows in table order (an ordered compaction: the delta launch sums the rows in the order they are stored, so the
+        // result is the same from call to call): rows per lane -> scan over the wave -> wave totals in LDS
         for (int j0 = 0; j0 < per; j0 += FB) {
-            const int jdx = j0 + tid, k = change_of(jdx);
-            if (k) {
-                const tamcmc_multiplet &rn = a.T.mults[(size_t)slot * per + jdx];
-                tamcmc_multiplet ro = a.T.mults[(size_t)(B + slot) * per + jdx];
-                const int pos = atomicAdd(&s_nchg, k);   // order of the changed rows is irrelevant (a sum)
-                if (k == 1) {
-                    for (int m = 0; m < 7; m++) ro.hv[m] = rn.hv[m] - ro.hv[m];
-                    drows[pos] = ro;
-                } else {
-                    for (int m = 0; m < 7; m++) ro.hv[m] = -ro.hv[m];
-                    drows[pos] = rn;
-                    drows[pos + 1] = ro;
-                }
-                atomicMin(&s_lo, min(rn.i0, ro.i0));
-                atomicMax(&s_hi, max(rn.i1, ro.i1));
+            const int jdx = j0 + tid, k = change_of(jdx), nr = (k == 2) ? 2 : (k ? 1 : 0);
+            int inc = nr;
+            for (int off = 1; off < 64; off <<= 1) {
+                const int up = __shfl_up(inc, off, 64);
+                if ((tid & 63) >= off) inc += up;
             }
+            if ((tid & 63) == 63) s_wtot[tid >> 6] = inc;
+            __syncthreads();
+            int pos = nchg + inc - nr;
+            for (int w = 0; w < FB / 64; w++) {
+                if (w < (tid >> 6)) pos += s_wtot[w];
+                nchg += s_wtot[w];
+            }
+            if (k) {
+                // rows move as 8-byte words, global to global (no private copy of a row): 12 words of degree, window, centre, width,
+                // asymmetry and frequencies, then the 7 heights -- differences (k = 1), as they are (+new) or negated (-old)
+                constexpr int NW = (int)(sizeof(tamcmc_multiplet) / 8), HV = NW - 7;
+                const tamcmc_multiplet *rn = &a.T.mults[(size_t)slot * per + jdx], *ro = &a.T.mults[(size_t)bs * per + jdx];
+                const unsigned long long *wn = (const unsigned long long *)rn, *wo = (const unsigned long long *)ro;
+                int lo = a.desc.Nx, hi = 0;
+                if (k != 4) {
+                    lo = rn->i0; hi = rn->i1;
+                    if (k != 1) {
+                        unsigned long long *d = (unsigned long long *)&drows[pos];
+                        for (int w = 0; w < NW; w++) d[w] = wn[w];
+                    }
+                }
+                if (k != 3) {
+                    lo = min(lo, ro->i0); hi = max(hi, ro->i1);
+                    tamcmc_multiplet *dr = &drows[pos + (k == 2 ? 1 : 0)];
+                    unsigned long long *d = (unsigned long long *)dr;
+                    for (int w = 0; w < HV; w++) d[w] = wo[w];
+                    for (int m = 0; m < 7; m++) dr->hv[m] = (k == 1) ? rn->hv[m] - ro->hv[m] : -ro->hv[m];
+                }
+                atomicMin(&s_lo, lo);
+                atomicMax(&s_hi, hi);
+            }
+            __syncthreads();  // (s_wtot is rewritten by the next pass)
         }
     __syncthreads();
     if (tid == 0) {
-        const int n = full ? per : s_nchg;
+        const int n = full ? n_new : nchg;
         const bool all_bins = s_noise_chg || full;
         a.D.pairs[2 * slot] = slot * 2 * per;
         a.D.pairs[2 * slot + 1] = slot * 2 * per + n;  // n = rows written (one or two per changed multiplet, or the whole table)
@@ -187,7 +316,6 @@ __global__ void __launch_bounds__(FB) k_fd_unpack(const FdArgs a) {
         a.d_range[2 * slot + 1] = all_bins ? a.desc.Nx : (n ? s_hi : 0);
     }
 }
-
 }  // namespace
 }  // namespace tamcmc
 
@@ -204,11 +332,23 @@ static size_t al16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 int FdBatch::layout(tamcmc_hip_ctx *c, int model_id_, int prior_class_, int C_, int64_t Nparams, const int32_t *plength, int Nvars_) {
     model_id = model_id_; prior_class = prior_class_; C = C_; Np = Nparams; Nvars = Nvars_;
-    per = mt::count_multiplets(model_id, plength);
-    if (per < 0) return TAMCMC_ERR_BAD_MODEL;
-    stride = plength[8] > 0 ? plength[8] : 1;
-    if ((stride - 1) / 3 > TAMCMC_MAX_HARVEY) return TAMCMC_ERR_BAD_ARG;
+    rgb = (model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4_ID || model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4_ID);
     E = Nvars + 1; B = C * E;
+    if (rgb) {
+        // red giants: the tables come from the device pre-step, whose workspace is ~28 KB per vector (Prep, RowIn, three arrays of
+        // rgb::MAXSOL doubles).  Chunk rule: the batch goes through ONE workspace slice of at most FD_RGB_WORKSPACE bytes, in chunks of
+        // fd_rgb_chunk() vectors (all of them at once while they fit: ~9500); sized here, once per layout
+        if ((long)C * E > 65535) return TAMCMC_ERR_BAD_ARG;  // (the limit of the batched red-giant entry)
+        if (plength[10] < 6) return TAMCMC_ERR_BAD_ARG;       // (the unpack reads six configuration values behind the inclination)
+        chunk = fd_rgb_chunk(B, rgb_device_workspace_bytes(1), FD_RGB_WORKSPACE);
+        const int rc = rgb_device_prepare(c, chunk, 1, plength, &per, &stride);
+        if (rc) return rc;
+    } else {
+        per = mt::count_multiplets(model_id, plength);
+        if (per < 0) return TAMCMC_ERR_BAD_MODEL;
+        stride = plength[8] > 0 ? plength[8] : 1;
+        if ((stride - 1) / 3 > TAMCMC_MAX_HARVEY) return TAMCMC_ERR_BAD_ARG;
+    }
     const size_t Nv = (size_t)Nvars;
     size_t o = 0;
     o_params = o; o = al16(o + (size_t)C * Np * 8);
@@ -226,7 +366,7 @@ int FdBatch::layout(tamcmc_hip_ctx *c, int model_id_, int prior_class_, int C_, 
     // windowed finite differences (FAST modes): only the multiplets a perturbation changes are re-evaluated, on their
     // windows, against the stored base model row ("the main algorithmic lever")
     windowed = c->fd_windowed && c->precision != TAMCMC_PRECISION_STRICT && delta_geometry(c->wgs, c->K) && Nvars > 0;
-    const int nslots = windowed ? 2 * B : B;                   // windowed: slots [B, 2B) = per-block copies of the base table
+    const int nslots = (windowed && !rgb) ? 2 * B : B;         // windowed: slots [B, 2B) = per-block copies of the base table (not for red giants)
     const StageLayout L(nslots, stride, (size_t)nslots * per);
     o_tab = o; o = al16(o + L.bytes);
     o_dtab = o_btab = o_drange = o_dflags = o_drow = o_dnold = 0;
@@ -258,7 +398,7 @@ int FdBatch::enqueue(tamcmc_hip_ctx *c, unsigned char *db, const double *d_param
         T.nh = (int *)(base + Lx.off_nh); T.nn = (int *)(base + Lx.off_nn); T.noise = (double *)(base + Lx.off_noise);
         return T;
     };
-    const int nslots = windowed ? 2 * B : B;
+    const int nslots = (windowed && !rgb) ? 2 * B : B;
     const StageLayout L(nslots, stride, (size_t)nslots * per), LD(B, stride, (size_t)B * 2 * per), LB(C, stride, 0);
     FdArgs fa;
     fa.desc.model_id = model_id; fa.desc.prior_class = prior_class; fa.desc.Np = (int)Np; fa.desc.per = per;
@@ -272,6 +412,7 @@ int FdBatch::enqueue(tamcmc_hip_ctx *c, unsigned char *db, const double *d_param
     fa.idx = (const int *)(db + o_idx); fa.h = (const double *)(db + o_h);
     fa.logPr_plus = (double *)(db + o_lpp); fa.logPr_minus = (double *)(db + o_lpm); fa.status = (int *)(db + o_st);
     fa.windowed = windowed ? 1 : 0;
+    fa.base_copies = rgb ? 0 : 1;
     fa.full_tables = (windowed && c->precision == TAMCMC_PRECISION_FAST && bgbuf) ? 1 : 0;
     fa.D = fa.T; fa.Bs = fa.T;
     fa.d_range = nullptr; fa.d_flags = nullptr; fa.d_row = nullptr; fa.d_noise_old = nullptr;
@@ -281,9 +422,32 @@ int FdBatch::enqueue(tamcmc_hip_ctx *c, unsigned char *db, const double *d_param
         fa.d_range = (int *)(db + o_drange); fa.d_flags = (int *)(db + o_dflags); fa.d_row = (int *)(db + o_drow);
         fa.d_noise_old = (double *)(db + o_dnold);
     }
-    const size_t lds = (size_t)Np * 8 + unpack_lds_bytes() + 32;
-    hipLaunchKernelGGL(k_fd_unpack, dim3(B), dim3(FB), lds, st, fa);
-    HIPCHK(c, hipGetLastError());
+    if (rgb && c->precision == TAMCMC_PRECISION_STRICT && !h_prep) return TAMCMC_ERR_BAD_ARG;  // (fd_batch.h: STRICT needs the host unpack)
+    if (rgb) {
+        RgbDeviceTables R;
+        R.mults = fa.T.mults; R.pairs = fa.T.pairs; R.nh = fa.T.nh; R.nn = fa.T.nn; R.noise = fa.T.noise; R.status = fa.status; R.stride = stride;
+        const rgb::Slice rs = rgb_device_slice(c, chunk, 0);
+        if (h_prep) HIPCHK(c, hipMemcpyAsync(db + o_tab, h_header, L.off_mults, hipMemcpyHostToDevice, st));  // counts and noise rows of the host unpack
+        for (int b0 = 0; b0 < B; b0 += chunk) {  // (one stream: a chunk's solver and row kernels are done with the slice before the next chunk's unpack)
+            const int n = B - b0 < chunk ? B - b0 : chunk;
+            if (h_prep) {
+                HIPCHK(c, hipMemcpyAsync(rs.preps, (const rgb::Prep *)h_prep + b0, (size_t)n * sizeof(rgb::Prep), hipMemcpyHostToDevice, st));
+                HIPCHK(c, hipMemcpyAsync(rs.rows, (const rgb::RowIn *)h_rows + b0, (size_t)n * sizeof(rgb::RowIn), hipMemcpyHostToDevice, st));
+            }
+            hipLaunchKernelGGL(k_fd_rgb_perturb, dim3(n), dim3(FB), (size_t)Np * 16, st, fa, rs, b0, h_prep ? 1 : 0);
+            HIPCHK(c, hipGetLastError());
+            const int rc = rgb_device_stage(c, b0, n, chunk, 0, per, R, st);
+            if (rc) return rc;
+        }
+    } else {
+        const size_t lds = (size_t)Np * 8 + unpack_lds_bytes() + 32;
+        hipLaunchKernelGGL(k_fd_unpack, dim3(B), dim3(FB), lds, st, fa);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (windowed) {
+        hipLaunchKernelGGL(k_fd_compare, dim3(B), dim3(FB), 0, st, fa);
+        HIPCHK(c, hipGetLastError());
+    }
 
     const int Nx = (int)c->Nx;
     LoglikeArgs a;
@@ -398,6 +562,37 @@ static int fd_run(tamcmc_hip_ctx *c, int model_id, int prior_class, int C, const
     std::memcpy(hb + fb.o_pl, plength, 11 * 4);
     std::memcpy(hb + fb.o_idx, index_to_relax, Nv * 4);
     HIPCHK(c, hipMemcpyAsync(db, hb, in_bytes, hipMemcpyHostToDevice, st));
+    if (fb.rgb && c->precision == TAMCMC_PRECISION_STRICT) {
+        // STRICT keeps the reference's arithmetic for the scalar unpack too: long double on the host, exactly what
+        // tamcmc_hip_loglike_params_batch does with the same vector -- a vector's STRICT logL is the same bits from either entry
+        const size_t bytes_prep = ((size_t)B * sizeof(rgb::Prep) + 15) & ~(size_t)15;
+        const StageLayout L(B, fb.stride, (size_t)B * fb.per);
+        HIPCHK(c, c->h_rgb.reserve(bytes_prep + (size_t)B * sizeof(rgb::RowIn)));
+        HIPCHK(c, c->h_stage.reserve(L.off_mults));
+        rgb::Prep *hp = (rgb::Prep *)c->h_rgb.p;
+        rgb::RowIn *hr = (rgb::RowIn *)(c->h_rgb.p + bytes_prep);
+        unsigned char *hh = c->h_stage.p;
+        std::memset(hh, 0, L.off_mults);
+        int32_t *h_nh = (int32_t *)(hh + L.off_nh), *h_nn = (int32_t *)(hh + L.off_nn);
+        double *h_noise = (double *)(hh + L.off_noise);
+        const bool cte = model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4_ID;
+        const double ustep = c->hx[2] - c->hx[1];
+        int nthr = B / 4 > 0 ? (B / 4 < 8 ? B / 4 : 8) : 1;
+        (void)nthr;  // (only the host pass sees the OpenMP pragma)
+#pragma omp parallel for schedule(static) num_threads(nthr)
+        for (int s = 0; s < B; s++) {
+            const int ch = s / E, e = s - ch * E;
+            std::vector<double> v(params + (size_t)ch * Np, params + (size_t)(ch + 1) * Np);
+            if (e > 0) {
+                volatile double xp = v[(size_t)index_to_relax[e - 1]] + hstep[e - 1];
+                v[(size_t)index_to_relax[e - 1]] = xp;
+            }
+            double fmin;
+            rgb::unpack_vector(rgb::OneThread(), v.data(), plength, ustep, cte, c->armm_dense ? 1 : 0, hp[s], hr[s], h_noise + (size_t)s * fb.stride, h_nh + s,
+                               h_nn + s, &fmin);
+        }
+        fb.h_prep = hp; fb.h_rows = hr; fb.h_header = hh;
+    }
     const size_t nS = fb.nS;
     HIPCHK(c, c->d_part.reserve(nS * fb.ntiles * 2));
     HIPCHK(c, c->d_S.reserve(nS));
@@ -510,7 +705,8 @@ int tamcmc_hip_fd_gradient_posterior(tamcmc_hip_ctx *c, int model_id, int prior_
         return tamcmc::envelope_fd_run(c, model_id, true, prior_class, C, params, Nparams, index_to_relax, Nvars, hstep, Tcoefs, p, priors,
                                        priors_switch, logL0, logPr0, grad, grad_prior);
     }
-    if (prior_class != 2 && prior_class != 3) return TAMCMC_ERR_BAD_MODEL;
+    const bool rgb = (model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4_ID || model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4_ID);
+    if (rgb ? prior_class != 4 : (prior_class != 2 && prior_class != 3)) return TAMCMC_ERR_BAD_MODEL;  // io_asymptotic is the red giants' prior, and theirs only
     return fd_run(c, model_id, prior_class, C, params, Nparams, plength, index_to_relax, Nvars, hstep, Tcoefs, p, priors,
                   priors_switch, extra_priors, logL0, logPr0, grad, grad_prior);
 }

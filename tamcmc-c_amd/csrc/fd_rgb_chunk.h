@@ -1,0 +1,20 @@
+// fd_rgb_chunk.h -- the chunk rule of a red-giant finite-difference batch (fd_batch.hip), plain C++ so that a host test can compile it
+// (tests/fd_rgb_chunk_driver.cpp).
+#pragma once
+#include <stddef.h>
+
+namespace tamcmc {
+
+// Vectors per pass through the ONE pre-step workspace slice: as many as fit `budget` bytes at `per_vector` bytes each, at least one
+// (a single vector larger than the budget still has to run), at most the batch; an empty batch gets 1 so that the chunk loop's step
+// is never zero.
+constexpr size_t FD_RGB_WORKSPACE = (size_t)256 << 20;
+inline int fd_rgb_chunk(int B, size_t per_vector, size_t budget) {
+    size_t n = per_vector ? budget / per_vector : (size_t)(B > 0 ? B : 1);
+    if (n < 1) n = 1;
+    return n < (size_t)(B > 0 ? B : 1) ? (int)n : (B > 0 ? B : 1);
+}
+// Chunks a batch of B vectors takes.
+inline int fd_rgb_chunks(int B, int chunk) { return B > 0 ? (B + chunk - 1) / chunk : 0; }
+
+}  // namespace tamcmc

@@ -32,8 +32,10 @@ struct RgbDeviceTables {
     int ntiles = 0, tile_bins = 0;
 };
 // prepare: workspace for `slices` chain groups of at most Bmax vectors each (once, outside the iteration loop).
+// workspace_bytes: what one slice of Bmax vectors takes (never more than Bmax times the size for one vector).
 // slice:   what the proposal kernel needs to run the scalar unpack of its chain into workspace slice `slice` (rgb_unpack.h).
 // stage:   chains [b0, b0 + B) through workspace slice `slice`: solver + zeta normalisation, then sort / zeta / rows / background, on st.
+size_t rgb_device_workspace_bytes(int Bmax);
 int rgb_device_prepare(tamcmc_hip_ctx *c, int Bmax, int slices, const int32_t *plength, int *per_out, int *stride_out);
 rgb::Slice rgb_device_slice(tamcmc_hip_ctx *c, int Bmax, int slice);
 int rgb_device_stage(tamcmc_hip_ctx *c, int b0, int B, int Bmax, int slice, int per, const RgbDeviceTables &T, hipStream_t st);

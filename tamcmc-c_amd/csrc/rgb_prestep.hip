@@ -599,6 +599,8 @@ static size_t rgb_slice_bytes(int B) {
     return (bytes_prep + bytes_rows + (size_t)B * MAXSOL * 3 * sizeof(double) + (size_t)B * (3 * sizeof(int) + sizeof(unsigned long long)) + 255) & ~(size_t)255;
 }
 
+size_t rgb_device_workspace_bytes(int Bmax) { return rgb_slice_bytes(Bmax); }
+
 int rgb_device_prepare(tamcmc_hip_ctx *c, int Bmax, int slices, const int32_t *plength, int *per_out, int *stride_out) {
     using namespace rgb;
     const int stride = plength[8] > 0 ? plength[8] : 1;
