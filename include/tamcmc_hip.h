@@ -116,6 +116,11 @@ extern "C" {
 #define TAMCMC_OPT_ARMM_DENSE_SCAN 7 /* red-giant pre-step: 1 = walk the solver's whole grid like the reference (solver_mm.cpp:340-377)
                                         instead of the pole-structured scan that finds the same cells; default 0 */
 
+#define TAMCMC_OPT_GRADIENT 9        /* value: TAMCMC_GRADIENT_* -- how the gradient batches (tamcmc_hip_fd_gradient*, both samplers' Langevin
+                                        step) obtain the likelihood's share; see tamcmc_hip_adjoint_table.  Default TAMCMC_GRADIENT_FD */
+#define TAMCMC_GRADIENT_FD 0         /* finite differences: Nvars perturbed likelihoods per chain (windowed or brute force) */
+#define TAMCMC_GRADIENT_ADJOINT 1    /* table-space adjoint with frozen windows: one pass over the bins per chain, whatever Nvars is */
+
 /* One (n,l) multiplet: <=7 Lorentzian m-components on its truncation window.
  * This is the flat "mode table" row every Lorentzian model of the dispatch table reduces to
  * (build_lorentzian.cpp:131-161, :208-246).  152 bytes, no padding. */
@@ -238,6 +243,34 @@ int tamcmc_hip_fd_gradient_posterior(tamcmc_hip_ctx *ctx, int model_id, int prio
                                      const double *hstep, const double *Tcoefs, double p, const double *priors,
                                      const int32_t *priors_switch, const double *extra_priors, double *logL0, double *logPr0,
                                      double *grad, double *grad_prior);
+
+/* Adjoint gradient (TAMCMC_OPT_GRADIENT = TAMCMC_GRADIENT_ADJOINT).  Every parameter of a Lorentzian model reaches the sum
+ * S = sum_i (y_i / M_i + ln M_i) only through the mode table and the noise row, so the likelihood's share of the gradient is
+ *   dS/dtheta_k = sum_rows sum_f G[row][f] dT[row].f/dtheta_k + sum_j Gn[j] d|noise_j|/dtheta_k,   f in {nu[7], hv[7], gamma, asym, fc}.
+ * G and Gn (the "table-space adjoint") are taken in ONE pass over the bins of the base point: G[row][f] = sum_i r_i dM_i/df over the row's
+ * own window [i0, i1), Gn[j] = sum_i r_i dN_i/d|noise_j| over all bins, r_i = (1/M_i)(1 - y_i/M_i).  The table Jacobian is the forward
+ * difference of the tables the batch's first kernel builds at theta + hstep[k] e_k anyway; hstep also still serves the prior's forward and
+ * backward differences, which are untouched.  No perturbed likelihood is evaluated.
+ * "Frozen window": the reference truncates each multiplet to a window of bins that depends on its frequency and width; a step that carries
+ * a window edge across a bin makes a finite difference jump by that bin's whole term.  The adjoint differentiates with every window held at
+ * the base point's [i0, i1) -- the windows of the perturbed tables are not read -- which is the exact derivative of the truncated model
+ * wherever that derivative exists: no jumps, no cancellation noise.
+ * With the option set, tamcmc_hip_fd_gradient, tamcmc_hip_fd_gradient_posterior, the host engine's Langevin step and the device engine's all
+ * take this route (same signatures, same outputs; logL0 is the windowed route's bit for bit, the prior's share the finite-difference
+ * route's bit for bit).  Models: the fixed-length table models, ids 3, 11, 12, 13, 14, 23; ids 0, 1 (no table) and 25, 27 (tables of
+ * variable length) return TAMCMC_ERR_BAD_MODEL.  Arithmetic: FAST or FAST_DIRECT (the pass reads the planes 1/M0 and y/M0 that the FAST
+ * base launch leaves), any workgroup geometry; STRICT returns TAMCMC_ERR_BAD_ARG.
+ * Tolerance: each G[row][f] / Gn[j] within 1e-11 sum_i |r_i dM_i/df| of a long-double evaluation of the same sum (the FAST tolerance,
+ * applied to this sum); the gradient within 3 R of the central difference with frozen windows, R that reference's own uncertainty
+ * |g(h) - g(h/2)| (tests/test_gpu_adjoint.py).  Every sum has one fixed order: two calls give the same bits, and a chain's gradient does
+ * not depend on the number of chains or on its place in the batch.
+ *
+ * The audit entry: G [C x *nrows x 17] and Gn [C x max(plength[8], 1)] of the C parameter vectors, for the UN-tempered S (Tcoefs and p are
+ * accepted for symmetry and not read: logL = -p S / T).  *nrows = rows per table.  Runs under the adjoint route whatever the option says;
+ * entries of rows a table does not have, of components m >= 2l+1 and, where asym = 0, of asym and fc are 0.  A vector whose table fails
+ * makes the call return that status; its G and Gn are 0.  G, Gn, nrows may be NULL. */
+int tamcmc_hip_adjoint_table(tamcmc_hip_ctx *ctx, int model_id, int C, const double *params, int64_t Nparams, const int32_t *plength,
+                             const double *Tcoefs, double p, double *G, double *Gn, int *nrows);
 
 /* Timing of the likelihood kernel measured with HIP events on the context's own stream
  * (enabled by TAMCMC_OPT_TIMING): totals since the last reset. */

@@ -27,6 +27,7 @@ MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4 = 27   # constant-width variant of 25, same path
 MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4 = 25  # batched device paths only (loglike_params_batch, fd_gradient*): needs the ARMM pre-step
 PRECISION_STRICT, PRECISION_FAST, PRECISION_FAST_DIRECT = 0, 1, 2
 OPT_PRECISION, OPT_TIMING, OPT_BINS_PER_THREAD, OPT_WORKGROUP, OPT_FD_WINDOWED, OPT_STEP_SCHEME, OPT_ARMM_DENSE_SCAN = 1, 2, 3, 4, 5, 6, 7
+OPT_GRADIENT, GRADIENT_FD, GRADIENT_ADJOINT = 9, 0, 1  # gradient batches: finite differences (default) / table-space adjoint, frozen windows
 OPT_QUICK_DECIDE = 8  # test facility: 1 = the fused step's decision shortcut always falls back to the exact evaluation
 
 
@@ -62,6 +63,7 @@ ABI = [
     ("tamcmc_hip_fd_gradient", C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int64, _ip, _ip, C.c_int, _dp, _dp, C.c_double, _dp, _dp]),
     ("tamcmc_hip_fd_gradient_posterior", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, C.c_int64, _ip, _ip, C.c_int, _dp, _dp, C.c_double,
                                                   _dp, _ip, _dp, _dp, _dp, _dp, _dp]),
+    ("tamcmc_hip_adjoint_table", C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int64, _ip, _dp, C.c_double, _dp, _dp, C.POINTER(C.c_int)]),
     ("tamcmc_hip_rgb_mixed_modes", C.c_int, [_vp, C.c_int, _dp, C.c_int64, _ip, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int)]),
     ("tamcmc_hip_get_kernel_stats", C.c_int, [_vp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("tamcmc_hip_reset_kernel_stats", C.c_int, [_vp]),
@@ -244,6 +246,24 @@ class HipContext:
         self._chk(st, tolerate=(ERR_EMPTY_WINDOW, ERR_NAN_WINDOW))
         self.last_grad_prior = gp
         return l0, pr0, g
+
+    def adjoint_table(self, model_id, params, plength, Tcoefs=None, p=1.0):
+        """Table-space adjoint of the un-tempered sum S at each row of params (tamcmc_hip_adjoint_table): (G [C x rows x 17], Gn [C x nnoise]),
+        fields of G in the order nu[7], hv[7], gamma, asym, fc."""
+        params = _f64(params)
+        if params.ndim == 1:
+            params = params[None, :]
+        Cn, Np = params.shape
+        plength = _i32(plength)
+        T = _f64(Tcoefs) if Tcoefs is not None else None
+        n = C.c_int(0)
+        self._chk(self._L.tamcmc_hip_adjoint_table(self._h, int(model_id), 0, _p(params), Np, _p(plength, _ip), _p(T), float(p), None, None,
+                                                   C.byref(n)))
+        G = np.zeros((Cn, n.value, 17))
+        Gn = np.zeros((Cn, max(int(plength[8]), 1)))
+        self._chk(self._L.tamcmc_hip_adjoint_table(self._h, int(model_id), Cn, _p(params), Np, _p(plength, _ip), _p(T), float(p), _p(G), _p(Gn),
+                                                   C.byref(n)))
+        return G, Gn
 
     def rgb_mixed_modes(self, model_id, params, plength, max_modes=1024):
         """l=1 mixed modes of one red-giant vector from the device pre-step: (nu_m, zeta, H1/H0) -- what ARMM's do_solve prints."""

@@ -102,6 +102,10 @@ int tamcmc_hip_set_option(tamcmc_hip_ctx *c, int option, int64_t value) {
         c->quick_decide = (int)value;
         return TAMCMC_OK;
     case TAMCMC_OPT_ARMM_DENSE_SCAN: c->armm_dense = value ? 1 : 0; return TAMCMC_OK;
+    case TAMCMC_OPT_GRADIENT:
+        if (value != TAMCMC_GRADIENT_FD && value != TAMCMC_GRADIENT_ADJOINT) return TAMCMC_ERR_BAD_ARG;
+        c->gradient = (int)value;
+        return TAMCMC_OK;
     case TAMCMC_OPT_WORKGROUP:  // sets the workgroup size AND its default bins per thread
         if (value != 64 && value != 256) return TAMCMC_ERR_BAD_ARG;
         c->wgs = (int)value;

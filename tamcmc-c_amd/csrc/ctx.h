@@ -69,6 +69,7 @@ struct tamcmc_hip_ctx {
                           // 2 = fused, always one launch per iteration, 3 = fused, two chain groups whenever the chain count allows
     int quick_decide = 0; // device sampler, fused step (a test facility): 1 = every margin test of the decision shortcut answers "undecided"
     int armm_dense = 0;   // red-giant pre-step: 1 = dense grid walk
+    int gradient = TAMCMC_GRADIENT_FD;  // gradient batches: finite differences, or the table-space adjoint with frozen windows (adjoint.h)
     // resident spectrum
     int64_t Nx = 0;
     std::vector<double> hx;  // host copy of x (table builders need x[0], x[Nx-1], step)

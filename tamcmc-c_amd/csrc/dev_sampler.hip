@@ -1023,7 +1023,7 @@ int DevSampler::run_mala(long it0, long n_iter, const char *learn, double *sampl
         int rc = nb.layout(c, I.model_id, I.prior_class, a.C, (int64_t)Np, I.h_plength.data(), a.Nv);
         if (rc) return rc;
         const bool need_bg = c->precision == TAMCMC_PRECISION_FAST && !I.fd_bg.p;  // (a switch to FAST between two calls keeps every size)
-        if (nb.total_bytes != I.fd.total_bytes || nb.windowed != I.fd.windowed || nb.ntiles != I.fd.ntiles || !I.fd_block.p || need_bg) {
+        if (nb.total_bytes != I.fd.total_bytes || nb.windowed != I.fd.windowed || nb.adjoint != I.fd.adjoint || nb.ntiles != I.fd.ntiles || !I.fd_block.p || need_bg) {
             I.fd = nb;
             rc = fd_ensure_poly(c);
             if (rc) return rc;
@@ -1038,8 +1038,8 @@ int DevSampler::run_mala(long it0, long n_iter, const char *learn, double *sampl
             DCHK(hipStreamSynchronize(st));
             DCHK(I.fd_part.reserve(nb.nS * (size_t)nb.ntiles * 2));
             DCHK(I.fd_S.reserve(nb.nS));
-            if (nb.windowed) DCHK(I.fd_model.reserve(3 * C * (size_t)c->Nx + 2 * C * (size_t)nb.ntiles * FD_MOM + ((size_t)nb.B * nb.ntiles + 7) / 8));  // three planes (1/M0, y/M0, M0 of the base points) + tile moments (two layouts) + done flags
-            if (c->precision == TAMCMC_PRECISION_FAST) DCHK(I.fd_bg.reserve((size_t)(nb.windowed ? a.C : nb.B) * nb.ntiles * 8));
+            if (nb.model_doubles) DCHK(I.fd_model.reserve(nb.model_doubles));  // three planes (1/M0, y/M0, M0 of the base points) + tile moments (two layouts) + done flags
+            if (c->precision == TAMCMC_PRECISION_FAST) DCHK(I.fd_bg.reserve(nb.bg_rows * nb.ntiles * 8));
             I.grad_valid = false;
         }
     }
@@ -1047,7 +1047,7 @@ int DevSampler::run_mala(long it0, long n_iter, const char *learn, double *sampl
     unsigned char *db = I.fd_block.p;
     MalaArgs M = I.mala;
     M.S = I.fd_S.p; M.lpp = (const double *)(db + fd.o_lpp); M.lpm = (const double *)(db + fd.o_lpm); M.st = (const int *)(db + fd.o_st);
-    M.h = (double *)(db + fd.o_h); M.E = fd.E; M.windowed = fd.windowed ? 1 : 0; M.fd_step_rel = I.fd_step_rel; M.delta = I.delta;
+    M.h = (double *)(db + fd.o_h); M.E = fd.E; M.windowed = fd.deltas() ? 1 : 0; M.fd_step_rel = I.fd_step_rel; M.delta = I.delta;
     if (samples && I.smp_cap < (size_t)n_iter * C * Nv) {
         DCHK(I.dalloc(&a.samples, (size_t)n_iter * C * Nv));
         I.smp_cap = (size_t)n_iter * C * Nv;

@@ -1,5 +1,5 @@
 // fd_batch.h -- one finite-difference batch (C chains x (Nvars + 1) evaluations) as an object: layout of its device block, launch from
-// parameter vectors already on the device (fd_batch.hip).  Used by the host entry points (tamcmc_hip_fd_gradient*) and by the
+// parameter vectors already on the device (fd_batch.hip).  Three routes: brute force, windowed delta tables, table-space adjoint.  Used by the host entry points (tamcmc_hip_fd_gradient*) and by the
 // device-resident Langevin step (dev_mala.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -14,6 +14,14 @@ struct FdBatch {
     int model_id = 0, prior_class = 0, C = 0, E = 0, B = 0, Nvars = 0, per = 0, stride = 1, ntiles = 0;
     int64_t Np = 0;
     bool windowed = false;
+    // TAMCMC_OPT_GRADIENT = TAMCMC_GRADIENT_ADJOINT: no perturbed likelihood at all.  The C base points are evaluated as in the windowed
+    // route (same launch, same planes), the table-space adjoint G / Gn of each is taken in one pass over its windows (adjoint.h), and the
+    // "difference" of evaluation e is the contraction of G / Gn with (table e - base table), written where the DELTA launch writes its
+    // difference -- so the sums read like the windowed route's (deltas()).  `windowed` is then false: no delta tables exist.
+    bool adjoint = false;
+    bool deltas() const { return windowed || adjoint; }  // S = C base sums, then B differences against them
+    size_t model_doubles = 0;  // doubles of `model` that enqueue() needs (0: none)
+    size_t bg_rows = 0;        // rows of `bgbuf` (x ntiles x 8 doubles) under FAST arithmetic
     bool rgb = false;  // red-giant models (ids 25 / 27): tables through the device pre-step, `chunk` vectors at a time
     int chunk = 0;
     // red giants: the host's long-double scalar unpack of the B vectors (rgb::Prep[B], rgb::RowIn[B], the table block's header with counts
@@ -25,7 +33,9 @@ struct FdBatch {
     size_t o_params = 0, o_h = 0, o_pr = 0, o_ex = 0, o_pl = 0, o_idx = 0, o_sw = 0, in_bytes = 0;
     size_t o_lpp = 0, o_lpm = 0, o_st = 0, out_bytes = 0;
     size_t o_tab = 0, o_dtab = 0, o_btab = 0, o_drange = 0, o_dflags = 0, o_drow = 0, o_dnold = 0, total_bytes = 0;
-    size_t nS = 0;  // sums the batch produces: C base sums + B differences (windowed) or B full sums
+    size_t o_adjG = 0, o_adjGn = 0, o_adjpart = 0, o_adjGpart = 0;  // adjoint workspace inside the block: G [C x per x 17], Gn [C x stride], noise tile partials, row segment partials
+    int adj_ntn = 0, adj_nseg = 0;
+    size_t nS = 0;  // sums the batch produces: C base sums + B differences (deltas()) or B full sums
     int layout(tamcmc_hip_ctx *c, int model_id, int prior_class, int C, int64_t Nparams, const int32_t *plength, int Nvars);
     int enqueue(tamcmc_hip_ctx *c, unsigned char *block, const double *d_params, double *part, double *S, double *model, double *bgbuf,
                 hipEvent_t ev0, hipEvent_t ev1);

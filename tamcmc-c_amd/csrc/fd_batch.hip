@@ -10,6 +10,9 @@
 //   k_fd_unpack (tables) -> k_fd_compare (delta tables) -> k_loglike on the C base points (planes 1/M0, y/M0, M0 kept) -> k_fd_moments (tile
 //   moments of the base points) -> k_fd_far (far-only tiles of the light evaluations from the moments) -> k_loglike<DELTA> (everything else)
 //   -> k_finalize.
+// or, adjoint (TAMCMC_OPT_GRADIENT = TAMCMC_GRADIENT_ADJOINT; FAST arithmetic, fixed-length tables):
+//   k_fd_unpack (tables) -> k_adj_base -> k_loglike on the C base points (planes kept) -> k_finalize -> k_adj_rows, k_adj_noise, k_adj_fold
+//   (adjoint.hip: dS/d(table entry) of each base point) -> k_adj_contract (dS of every perturbed table to first order, frozen windows).
 // Red-giant models (ids 25 / 27): the table of a vector needs the mixed-mode solver, so k_fd_unpack's place is taken by
 //   k_fd_rgb_perturb (perturbed vector, class-4 log-prior, scalar unpack into the pre-step workspace) -> rgb_device_stage (solver, rows),
 // in chunks of vectors through ONE workspace slice; everything after the tables is the same.
@@ -25,6 +28,7 @@
 #include "kernels.h"
 #include "fd_batch.h"
 #include "rgb_prestep.h"
+#include "adjoint.h"
 
 namespace tamcmc {
 namespace {
@@ -316,6 +320,18 @@ __global__ void __launch_bounds__(FB) k_fd_compare(const FdArgs a) {
         a.d_range[2 * slot + 1] = all_bins ? a.desc.Nx : (n ? s_hi : 0);
     }
 }
+
+// Adjoint route: the base launch's ranges / counts / noise rows by chain -- what k_fd_compare's e = 0 workgroups write in the windowed route.
+__global__ void __launch_bounds__(64) k_adj_base(const FdArgs a) {
+    const int c = blockIdx.x, slot = c * a.E, tid = threadIdx.x;
+    if (tid == 0) {
+        a.Bs.pairs[2 * c] = a.T.pairs[2 * slot];
+        a.Bs.pairs[2 * c + 1] = a.T.pairs[2 * slot + 1];
+        a.Bs.nh[c] = a.T.nh[slot];
+        a.Bs.nn[c] = a.T.nn[slot];
+    }
+    for (int i = tid; i < a.desc.stride; i += 64) a.Bs.noise[(size_t)c * a.desc.stride + i] = a.T.noise[(size_t)slot * a.desc.stride + i];
+}
 }  // namespace
 }  // namespace tamcmc
 
@@ -334,6 +350,11 @@ int FdBatch::layout(tamcmc_hip_ctx *c, int model_id_, int prior_class_, int C_, 
     model_id = model_id_; prior_class = prior_class_; C = C_; Np = Nparams; Nvars = Nvars_;
     rgb = (model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4_ID || model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4_ID);
     E = Nvars + 1; B = C * E;
+    adjoint = c->gradient == TAMCMC_GRADIENT_ADJOINT;
+    if (adjoint) {
+        if (rgb) return TAMCMC_ERR_BAD_MODEL;  // (tables of variable length: no row-by-row contraction)
+        if (c->precision == TAMCMC_PRECISION_STRICT) return TAMCMC_ERR_BAD_ARG;  // (the planes are the FAST base launch's)
+    }
     if (rgb) {
         // red giants: the tables come from the device pre-step, whose workspace is ~28 KB per vector (Prep, RowIn, three arrays of
         // rgb::MAXSOL doubles).  Chunk rule: the batch goes through ONE workspace slice of at most FD_RGB_WORKSPACE bytes, in chunks of
@@ -365,7 +386,7 @@ int FdBatch::layout(tamcmc_hip_ctx *c, int model_id_, int prior_class_, int C_, 
     out_bytes = o - in_bytes;
     // windowed finite differences (FAST modes): only the multiplets a perturbation changes are re-evaluated, on their
     // windows, against the stored base model row ("the main algorithmic lever")
-    windowed = c->fd_windowed && c->precision != TAMCMC_PRECISION_STRICT && delta_geometry(c->wgs, c->K) && Nvars > 0;
+    windowed = !adjoint && c->fd_windowed && c->precision != TAMCMC_PRECISION_STRICT && delta_geometry(c->wgs, c->K) && Nvars > 0;
     const int nslots = (windowed && !rgb) ? 2 * B : B;         // windowed: slots [B, 2B) = per-block copies of the base table (not for red giants)
     const StageLayout L(nslots, stride, (size_t)nslots * per);
     o_tab = o; o = al16(o + L.bytes);
@@ -380,10 +401,27 @@ int FdBatch::layout(tamcmc_hip_ctx *c, int model_id_, int prior_class_, int C_, 
         o_drow = o; o = al16(o + (size_t)B * 4);
         o_dnold = o; o = al16(o + (size_t)B * stride * 8);
     }
+    o_adjG = o_adjGn = o_adjpart = o_adjGpart = 0;
+    adj_ntn = adj_nseg = 0;
+    if (adjoint) {
+        const StageLayout LB(C, stride, 0);
+        adj_ntn = (int)((c->Nx + ADJ_NTILE - 1) / ADJ_NTILE);
+        o_btab = o; o = al16(o + LB.bytes);
+        o_adjG = o; o = al16(o + (size_t)C * per * ADJ_F * 8);
+        o_adjGn = o; o = al16(o + (size_t)C * stride * 8);
+        o_adjpart = o; o = al16(o + (size_t)C * adj_ntn * stride * 8);
+        adj_nseg = (int)((c->Nx + ADJ_SEG - 1) / ADJ_SEG);
+        o_adjGpart = o; o = al16(o + (size_t)C * per * adj_nseg * ADJ_F * 8);
+    }
     total_bytes = o;
     const int tbins = tile_bins(c->wgs, c->K);
     ntiles = (int)((c->Nx + tbins - 1) / tbins);
-    nS = windowed ? (size_t)C + B : (size_t)B;
+    nS = deltas() ? (size_t)C + B : (size_t)B;
+    // `model`: three planes of the base points (1/M0, y/M0, M0); windowed: + tile moments (two layouts) + done flags
+    model_doubles = 0;
+    if (adjoint) model_doubles = 3 * (size_t)C * c->Nx;
+    if (windowed) model_doubles = 3 * (size_t)C * c->Nx + 2 * (size_t)C * ntiles * FD_MOM + ((size_t)B * ntiles + 7) / 8;
+    bg_rows = deltas() ? (size_t)C : (size_t)B;
     return TAMCMC_OK;
 }
 
@@ -448,6 +486,11 @@ int FdBatch::enqueue(tamcmc_hip_ctx *c, unsigned char *db, const double *d_param
         hipLaunchKernelGGL(k_fd_compare, dim3(B), dim3(FB), 0, st, fa);
         HIPCHK(c, hipGetLastError());
     }
+    if (adjoint) {
+        fa.Bs = table_ptrs(db + o_btab, LB);
+        hipLaunchKernelGGL(k_adj_base, dim3(C), dim3(64), 0, st, fa);
+        HIPCHK(c, hipGetLastError());
+    }
 
     const int Nx = (int)c->Nx;
     LoglikeArgs a;
@@ -455,7 +498,29 @@ int FdBatch::enqueue(tamcmc_hip_ctx *c, unsigned char *db, const double *d_param
     a.x0 = c->hx[0]; a.step = c->hx[1] - c->hx[0];
     a.noise_stride = stride; a.model = nullptr;
     if (ev0) HIPCHK(c, hipEventRecord(ev0, st));
-    if (!windowed) {
+    if (adjoint) {
+        // (1) the C base points, exactly the windowed route's base launch: planes 1/M0, y/M0 (and M0) kept
+        a.B = C;
+        a.mults = fa.T.mults; a.offsets = fa.Bs.pairs; a.noise = fa.Bs.noise; a.nharvey = fa.Bs.nh; a.nnoise = fa.Bs.nn;
+        a.partials = part; a.model = model; a.fd_rows = model; a.fd_plane = (size_t)C * Nx;
+        if (c->precision == TAMCMC_PRECISION_FAST) {
+            HIPCHK(c, launch_bg_poly(a, c->wgs, c->K, bgbuf, st));
+            a.bg_poly = bgbuf;
+        }
+        HIPCHK(c, launch_loglike(a, c->precision, c->wgs, c->K, true, st));
+        HIPCHK(c, launch_finalize(part, C, ntiles, S, st));
+        // (2) dS/d(table entry) of each base point, (3) contracted with every perturbed table's difference from it
+        AdjArgs g;
+        g.x = c->dx.p; g.logx = c->dlogx.p; g.Nx = Nx;
+        g.planes = model; g.plane = (size_t)C * Nx;
+        g.C = C; g.E = E; g.per = per; g.stride = stride;
+        g.mults = fa.T.mults; g.pairs = fa.T.pairs; g.nh = fa.T.nh; g.nn = fa.T.nn; g.status = fa.status; g.noise = fa.T.noise;
+        g.G = (double *)(db + o_adjG); g.Gn = (double *)(db + o_adjGn); g.npart = (double *)(db + o_adjpart); g.ntn = adj_ntn;
+        g.Gpart = (double *)(db + o_adjGpart); g.nseg = adj_nseg;
+        HIPCHK(c, launch_adjoint(g, st));
+        HIPCHK(c, launch_adjoint_contract(g, S + C, st));
+        d_done = nullptr;
+    } else if (!windowed) {
         a.B = B;
         a.mults = fa.T.mults; a.offsets = fa.T.pairs; a.noise = fa.T.noise; a.nharvey = fa.T.nh; a.nnoise = fa.T.nn;
         a.partials = part;
@@ -547,7 +612,7 @@ static int fd_run(tamcmc_hip_ctx *c, int model_id, int prior_class, int C, const
     if (rc) return rc;
     const int E = fb.E, B = fb.B;
     const size_t Np = (size_t)Nparams, Nv = (size_t)Nvars;
-    const bool windowed = fb.windowed;
+    const bool windowed = fb.windowed, deltas = fb.deltas();
     const size_t in_bytes = fb.in_bytes, out_bytes = fb.out_bytes, o_lpp = fb.o_lpp, o_lpm = fb.o_lpm, o_st = fb.o_st, o_drange = fb.o_drange;
     HIPCHK(c, c->h_fd.reserve(in_bytes + out_bytes));
     HIPCHK(c, c->d_fd.reserve(fb.total_bytes));
@@ -597,8 +662,8 @@ static int fd_run(tamcmc_hip_ctx *c, int model_id, int prior_class, int C, const
     HIPCHK(c, c->d_part.reserve(nS * fb.ntiles * 2));
     HIPCHK(c, c->d_S.reserve(nS));
     HIPCHK(c, c->h_S.reserve(nS));
-    if (windowed) HIPCHK(c, c->d_model.reserve(3 * (size_t)C * c->Nx + 2 * (size_t)C * fb.ntiles * FD_MOM + ((size_t)fb.B * fb.ntiles + 7) / 8));  // three planes: 1/M0, y/M0, M0; tile moments (two layouts); done flags
-    if (c->precision == TAMCMC_PRECISION_FAST) HIPCHK(c, c->d_bg.reserve((size_t)(windowed ? C : B) * fb.ntiles * 8));
+    if (fb.model_doubles) HIPCHK(c, c->d_model.reserve(fb.model_doubles));
+    if (c->precision == TAMCMC_PRECISION_FAST) HIPCHK(c, c->d_bg.reserve(fb.bg_rows * fb.ntiles * 8));
     rc = fb.enqueue(c, db, nullptr, c->d_part.p, c->d_S.p, c->d_model.p, c->d_bg.p, c->timing ? c->ev0 : nullptr, c->timing ? c->ev1 : nullptr);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->h_S.p, c->d_S.p, nS * 8, hipMemcpyDeviceToHost, st));
@@ -627,7 +692,7 @@ static int fd_run(tamcmc_hip_ctx *c, int model_id, int prior_class, int C, const
     int first_err = TAMCMC_OK;
     for (int ch = 0; ch < C; ch++) {
         const double T = Tcoefs ? Tcoefs[ch] : 1.0;
-        // S of evaluation e: full sums (non-windowed) or base sum + difference (windowed)
+        // S of evaluation e: full sums (brute force) or base sum + difference (windowed, adjoint)
         auto scaled = [&](double S) {
             long double f = S;
             f = -pl * f;
@@ -638,10 +703,10 @@ static int fd_run(tamcmc_hip_ctx *c, int model_id, int prior_class, int C, const
             if (stt[s] != TAMCMC_OK) { if (first_err == TAMCMC_OK) first_err = stt[s]; return true; }
             return false;
         };
-        const double L0 = failed(0) ? (double)NAN : scaled(windowed ? c->h_S.p[ch] : c->h_S.p[(size_t)ch * E]);
+        const double L0 = failed(0) ? (double)NAN : scaled(deltas ? c->h_S.p[ch] : c->h_S.p[(size_t)ch * E]);
         auto dlogL_of = [&](int e) {  // logL(theta + h e_k) - logL(theta)
             if (failed(e)) return (double)NAN;
-            if (windowed) return scaled(c->h_S.p[(size_t)C + (size_t)ch * E + e]);
+            if (deltas) return scaled(c->h_S.p[(size_t)C + (size_t)ch * E + e]);
             return scaled(c->h_S.p[(size_t)ch * E + e]) - L0;
         };
         logL0[ch] = L0;
@@ -674,6 +739,7 @@ int tamcmc_hip_fd_gradient(tamcmc_hip_ctx *c, int model_id, int C, const double 
                            const double *Tcoefs, double p, double *logL0, double *grad) {
     if (tamcmc::is_envelope_model(model_id)) {  // every parameter moves every bin: Nvars + 1 full evaluations per chain, one batch
         if (!c) return TAMCMC_ERR_BAD_ARG;
+        if (c->gradient == TAMCMC_GRADIENT_ADJOINT) return TAMCMC_ERR_BAD_MODEL;  // (no mode table: no table-space adjoint)
         if (c->Nx <= 0) return TAMCMC_ERR_NO_SPECTRUM;
         if (C < 0 || Nvars < 0 || !params || !index_to_relax || !hstep || !logL0 || !grad || Nparams < 1) return TAMCMC_ERR_BAD_ARG;
         for (int k = 0; k < Nvars; k++)
@@ -694,6 +760,7 @@ int tamcmc_hip_fd_gradient_posterior(tamcmc_hip_ctx *c, int model_id, int prior_
                                      double *grad, double *grad_prior) {
     if (tamcmc::is_envelope_model(model_id)) {  // brute force, priors of classes 0 / 1 on the device (envelope.hip)
         if (!c) return TAMCMC_ERR_BAD_ARG;
+        if (c->gradient == TAMCMC_GRADIENT_ADJOINT) return TAMCMC_ERR_BAD_MODEL;
         if (c->Nx <= 0) return TAMCMC_ERR_NO_SPECTRUM;
         if (C < 0 || Nvars < 0 || !params || !index_to_relax || !hstep || !logL0 || !grad || Nparams < 1 || !priors || !priors_switch)
             return TAMCMC_ERR_BAD_ARG;
@@ -709,6 +776,54 @@ int tamcmc_hip_fd_gradient_posterior(tamcmc_hip_ctx *c, int model_id, int prior_
     if (rgb ? prior_class != 4 : (prior_class != 2 && prior_class != 3)) return TAMCMC_ERR_BAD_MODEL;  // io_asymptotic is the red giants' prior, and theirs only
     return fd_run(c, model_id, prior_class, C, params, Nparams, plength, index_to_relax, Nvars, hstep, Tcoefs, p, priors,
                   priors_switch, extra_priors, logL0, logPr0, grad, grad_prior);
+}
+
+// Audit entry of the adjoint route: the batch with no perturbed vector (Nvars = 0) under TAMCMC_GRADIENT_ADJOINT, whatever the context's
+// option says -- unpack, base launch, k_adj_rows, k_adj_noise -- and G / Gn brought back.
+int tamcmc_hip_adjoint_table(tamcmc_hip_ctx *c, int model_id, int C, const double *params, int64_t Nparams, const int32_t *plength,
+                             const double *Tcoefs, double p, double *G, double *Gn, int *nrows) {
+    (void)Tcoefs; (void)p;  // (the adjoint of the un-tempered sum S: logL = -p S / T)
+    if (!c) return TAMCMC_ERR_BAD_ARG;
+    if (tamcmc::is_envelope_model(model_id)) return TAMCMC_ERR_BAD_MODEL;
+    if (c->Nx <= 0) return TAMCMC_ERR_NO_SPECTRUM;
+    if (C < 0 || !params || !plength || Nparams < 1) return TAMCMC_ERR_BAD_ARG;
+    long psum = 0;
+    for (int i = 0; i < 11; i++) psum += plength[i];
+    if (psum != Nparams) return TAMCMC_ERR_BAD_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    FdBatch fb;
+    const int saved = c->gradient;
+    c->gradient = TAMCMC_GRADIENT_ADJOINT;
+    int rc = fb.layout(c, model_id, 0, C > 0 ? C : 1, Nparams, plength, 0);
+    c->gradient = saved;
+    if (rc) return rc;
+    if (nrows) *nrows = fb.per;
+    if (C == 0) return TAMCMC_OK;
+    rc = fd_ensure_poly(c);
+    if (rc) return rc;
+    const size_t Np = (size_t)Nparams;
+    HIPCHK(c, c->h_fd.reserve(fb.in_bytes + fb.out_bytes));
+    HIPCHK(c, c->d_fd.reserve(fb.total_bytes));
+    unsigned char *hb = c->h_fd.p, *db = c->d_fd.p;
+    std::memset(hb, 0, fb.in_bytes);
+    std::memcpy(hb + fb.o_params, params, (size_t)C * Np * 8);
+    std::memcpy(hb + fb.o_pl, plength, 11 * 4);
+    HIPCHK(c, hipMemcpyAsync(db, hb, fb.in_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(c, c->d_part.reserve(fb.nS * fb.ntiles * 2));
+    HIPCHK(c, c->d_S.reserve(fb.nS));
+    HIPCHK(c, c->d_model.reserve(fb.model_doubles));
+    if (c->precision == TAMCMC_PRECISION_FAST) HIPCHK(c, c->d_bg.reserve(fb.bg_rows * fb.ntiles * 8));
+    rc = fb.enqueue(c, db, nullptr, c->d_part.p, c->d_S.p, c->d_model.p, c->d_bg.p, nullptr, nullptr);
+    if (rc) return rc;
+    if (G) HIPCHK(c, hipMemcpyAsync(G, db + fb.o_adjG, (size_t)C * fb.per * ADJ_F * 8, hipMemcpyDeviceToHost, st));
+    if (Gn) HIPCHK(c, hipMemcpyAsync(Gn, db + fb.o_adjGn, (size_t)C * fb.stride * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(hb + fb.in_bytes, db + fb.in_bytes, fb.out_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    const int *stt = (const int *)(hb + fb.o_st);
+    for (int ch = 0; ch < C; ch++)
+        if (stt[ch] != TAMCMC_OK) return stt[ch];  // (that chain's G and Gn are zero)
+    return TAMCMC_OK;
 }
 
 }  // extern "C"
