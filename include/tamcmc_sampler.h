@@ -103,7 +103,11 @@ int64_t tamcmc_sampler_nvars(const tamcmc_sampler *s);
 #define TAMCMC_INFO_QUICK_SURE 11      /* of those, the tests of chains outside the swap pair whose record said "cannot be accepted"
                                           (proposal outside a prior's support): decided without sums, also under
                                           TAMCMC_OPT_QUICK_DECIDE = 1, where FALLBACKS + SURE = the number of tile tests */
-#define TAMCMC_SAMPLER_INFO_N 12
+#define TAMCMC_INFO_ITER_JOINT 12      /* of ITER_FUSED with two chain groups: iterations run as ONE launch over all chains (a swap pair
+                                          on the moved boundary of a window) */
+#define TAMCMC_INFO_ITER_WINDOW 13     /* ... and iterations run as two launches with the boundary between the groups moved by one chain
+                                          (the iteration of a swap pair that straddles the groups, and the next) */
+#define TAMCMC_SAMPLER_INFO_N 14
 int tamcmc_sampler_get_info(const tamcmc_sampler *s, int64_t *info, int32_t n);
 
 /* Advances all chains by n_iter iterations.  Optional outputs, one record per iteration after the swap step

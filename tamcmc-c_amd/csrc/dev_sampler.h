@@ -83,7 +83,8 @@ class DevSampler {
     // [0] Nvars [1] Nparams [2] adaptation workspace in LDS (1) / global scratch (0) [3] fused step available [4] chain groups
     // [5] iterations run fused [6] iterations run by the lockstep kernels [7] chains [8] fused stretches
     // [9] quick_decide fallbacks taken by the likelihood tiles [10] tile tests decided from a kind-2 record (outside a swap pair)
-    void info(long out[11]) const;
+    // [11] of [5] with two chain groups: iterations run as one joint launch [12] ... run in a window (step_schedule.h: StepPlanner)
+    void info(long out[13]) const;
     int run(long it0, long n_iter, const char *learn, double *samples, double *stats);
     int run_mala(long it0, long n_iter, const char *learn, double *samples, double *stats);  // use_drift = 1 (dev_mala_impl.h)
 };

@@ -23,8 +23,10 @@
 //       * L z blocks two iterations ahead, one wave per chain.
 //     From the size on at which one launch outgrows the GPU's resident waves the chains form TWO GROUPS, each with its own launch per
 //     iteration on its own stream: the groups' launches fill each other's idle ends and share nothing, except in the iterations whose
-//     swap pair straddles the groups -- that iteration and the next are one launch over all chains (step_schedule.h: joint_launch;
-//     RunCall::run_fused for who waits for whom).
+//     swap pair straddles the groups -- for that iteration and the next the boundary between the groups moves by one chain, so that
+//     the pair lies inside one launch, with one event hop each way and the rest of the second group running on through both; only a
+//     pair on the moved boundary still makes an iteration one launch over all chains (step_schedule.h: StepPlanner, with every wait;
+//     RunCall::run_fused enqueues its plan).
 // (B) LOCKSTEP (dev_iterate_impl.h), two kernels per iteration and chain group (k_iterate, k_loglike) -- used where the proposal law is
 //     adapted after every test (the next proposal needs the new Cholesky factor, so it cannot be prepared ahead):
 //       k_iterate (one workgroup per chain) settles iteration it-1 (MH test, swap, record, Robbins-Monro update MALA.cpp:296-319,
@@ -105,6 +107,7 @@ struct DevSampler::Impl {
     int armed_q = 0;
     long it_fused = 0, it_lockstep = 0;  // iterations run by each scheme since creation (tamcmc_sampler_get_info)
     long n_stretch = 0;                  // fused stretches since creation (the first launch of each has nothing to decide)
+    long it_joint = 0, it_window = 0;    // of it_fused with two chain groups: iterations run as one launch / as a window (StepPlanner)
     int mala_chol_lds = -1;
 
     hipEvent_t gev[8][2];  // fused step with two chain groups: event pairs around sampled launches of the second group (on its stream)
@@ -382,7 +385,7 @@ int DevSampler::download_last_proposal(double *vars_prop, double *grad_prop) {
     return TAMCMC_OK;
 }
 
-void DevSampler::info(long out[11]) const {
+void DevSampler::info(long out[13]) const {
     const Impl &I = *impl;
     unsigned long long qc[2] = {0, 0};  // (every entry point returns with the sampler's streams idle)
     if (I.f.qcount && hipSetDevice(I.ctx->device) == hipSuccess) (void)hipMemcpy(qc, I.f.qcount, sizeof qc, hipMemcpyDeviceToHost);
@@ -391,6 +394,7 @@ void DevSampler::info(long out[11]) const {
     out[2] = I.use_drift ? I.mala_chol_lds : I.a.chol_in_lds;
     out[3] = (I.fused_ok && !I.use_drift) ? 1 : 0;
     out[4] = I.G; out[5] = I.it_fused; out[6] = I.it_lockstep; out[7] = I.a.C;
+    out[11] = I.it_joint; out[12] = I.it_window;
 }
 
 int DevSampler::upload_state(const double *vars, const double *params, const double *logL, const double *logPr,
@@ -572,7 +576,8 @@ struct DevSampler::Impl::KernelTiming {
     }
     // fused stretch of `len` iterations.  One launch per iteration: two events around the whole stretch, i.e. the average includes the
     // time between two launches.  Two groups: every 97th iteration, or the middle one of a short stretch -- the first two-group
-    // iteration at or after it: a joint iteration there must not leave a short call without a measured launch
+    // iteration with the nominal groups at or after it: a joint iteration there must not leave a short call without a measured launch,
+    // and a window's launches (eleven and nine chains at the headline shape) are not what the average is multiplied out for
     void begin_fused(long len) {
         stretch_timed = c->timing && fused_ev.size() < 16;
         fe = I.n_ev - 1 - (int)fused_ev.size();
@@ -648,9 +653,8 @@ struct DevSampler::Impl::RunCall {
     // (A) the stretch being enqueued
     StepCtl sc{};
     int q = 0;                   // parity of the iteration being enqueued
-    // (A) with two groups, who waits for whom: the first group's and the joint launches go to st, the second group's to s1 = I.gst[1]
-    bool s1_must_wait = false;   // st holds launches of this call that s1 has not waited for (an event hop precedes s1's next launch)
-    bool s1_ahead = false;       // s1 holds launches of this stretch that st has not waited for (... st's next joint launch)
+    // (A) with two groups: the first group's and the joint launches go to st, the second group's to s1 = I.gst[1]; who waits for whom
+    // is the plan's business (step_schedule.h: StepPlanner, with its s1_must_wait and s1_ahead)
     bool s1_open = false;        // s1 still holds launches at the end of the call: the host waits for both streams (finish)
 
     RunCall(Impl &I_, CallTimeline &tl_, long it0_, long n_iter_, const char *learn_, double *samples_, double *stats_)
@@ -908,12 +912,16 @@ struct DevSampler::Impl::RunCall {
     // ---- (A) fused steps over [ia, ib) (no adaptation inside): one launch per iteration on the context stream, or two (one per chain group).
     // Two chain groups, each with its own launch per iteration on its own stream: a launch is a chain of dependent steps (sums ->
     // decision -> table rows -> tile, ~18 us even for five chains) that leaves most of the GPU idle at its two ends; the two groups'
-    // launches fill each other's ends.  Nothing is shared between the groups' launches except at a swap whose pair straddles the groups:
-    // those iterations are joint launches (step_schedule.h), on the context stream after both groups' earlier launches.  (Same chains bit
-    // for bit: the launches' contents are the same.)
+    // launches fill each other's ends.  Nothing is shared between the groups' launches except at a swap whose pair (xsplit-1, xsplit)
+    // straddles the groups.  For that iteration and the next (a window) the boundary moves by one chain -- [0, xsplit+1) on st,
+    // [xsplit+1, C) on s1 -- so that the pair lies inside the first group's launch: st waits for s1 once on the way in (chain xsplit's
+    // earlier launches are there), s1 waits for st once on the way out, and the rest of the second group keeps running through both
+    // hops (profiles/r05_straddle_summary.md: the cost of the joint launches this replaces, and of what is left).  Only a window iteration whose own or previous pair is (xsplit, xsplit+1) is
+    // still one joint launch over all chains, on st after both groups' earlier launches.  step_schedule.h (StepPlanner) decides all of
+    // this, iteration by iteration, with every wait; here the plan is enqueued.  (Same chains bit for bit: the launches hold the same
+    // workgroups, every buffer of the step is per chain, and a chain's cross candidates stay in the extra block named by f.xsplit.)
     int run_fused(long ia, long ib) {
         const long len = ib - ia;
-        const int first1 = I.f.xsplit;
         hipStream_t s1 = I.gst[1];
         I.it_fused += len;
         I.n_stretch += 1;
@@ -923,46 +931,43 @@ struct DevSampler::Impl::RunCall {
         sc.first = 0; sc.cnt = a.C; sc.extra = 1;
         bool entered;
         if (int rc = fused_entry(ia, &entered)) return rc;
+        StepPlanner plan(split_ok, a.C, I.f.xsplit);
         // does the context stream hold work of this call that the second group's stream has to wait for?  (Every entry point of the
         // library returns with its streams idle, so a call that starts on carried-over candidates has nothing to wait for: the event
-        // hop would only delay the second group's first launch by 10-30 us.)
-        s1_must_wait = ia > 0 || entered;
-        s1_ahead = false;
+        // hop would only delay the second group's first launch by 12-14 us, profiles/r05_straddle_summary.md.)
+        plan.s1_must_wait = ia > 0 || entered;
+        plan.s1_ahead = false;
         T.begin_fused(len);
         if (!split_ok && T.stretch_pair()) DCHK(hipEventRecord(T.stretch_pair()[0], st));
-        long n_split = 0;
+        long n_two = 0;
         int A_prev = -1;
         for (long i = ia; i < ib; i++) {
             const int A = swap_pair_of(it0 + i);
             const bool settled = i == ia;
-            if (!joint_launch(split_ok, first1, A, A_prev, settled)) {
-                if (s1_must_wait) {
-                    if (int rc = s1_waits_for_st()) return rc;
-                    s1_must_wait = false;
-                }
-                if (int rc = launch_group(0, first1, A, A_prev, i, settled, st)) return rc;
-                if (int rc = launch_group(first1, a.C - first1, A, A_prev, i, settled, s1, T.sampled_pair(i - ia))) return rc;
-                s1_ahead = true;
-                n_split++;
-            } else {
-                if (s1_ahead) {
-                    if (int rc = st_waits_for_s1()) return rc;
-                    s1_ahead = false;
-                }
-                if (int rc = launch_group(0, a.C, A, A_prev, i, settled, st)) return rc;
-                s1_must_wait = true;
-            }
+            const StepPlan p = plan.next(A);
+            if (p.st_waits_s1) if (int rc = st_waits_for_s1()) return rc;
+            if (p.s1_waits_st) if (int rc = s1_waits_for_st()) return rc;
+            if (int rc = launch_group(0, p.b, A, A_prev, i, settled, st)) return rc;
+            if (p.b < a.C) {
+                if (int rc = launch_group(p.b, a.C - p.b, A, A_prev, i, settled, s1, p.window ? nullptr : T.sampled_pair(i - ia))) return rc;
+                n_two++;
+                I.it_window += p.window ? 1 : 0;
+            } else if (split_ok) I.it_joint += 1;
             A_prev = A;
             q ^= 1;
         }
-        if (s1_ahead) {  // (the last launches were one per group: iteration ib-1's swap pair lies inside one of them)
-            if (int rc = launch_close(0, first1, ib, st)) return rc;
-            if (int rc = launch_close(first1, a.C - first1, ib, s1)) return rc;
+        // the closing launches, over the ranges the last iteration's pair asks for (iteration ib-1's swap is decided by them)
+        const StepPlan p = plan.next(-1);
+        if (p.st_waits_s1) if (int rc = st_waits_for_s1()) return rc;
+        if (p.s1_waits_st) if (int rc = s1_waits_for_st()) return rc;
+        if (int rc = launch_close(0, p.b, ib, st)) return rc;
+        if (p.b < a.C) {
+            if (int rc = launch_close(p.b, a.C - p.b, ib, s1)) return rc;
             if (ib >= n_iter) s1_open = true;  // the call's last stretch: the host waits for both streams (no event hop on the GPU)
             else if (int rc = st_waits_for_s1()) return rc;
-        } else if (int rc = launch_close(0, a.C, ib, st)) return rc;
+        }
         if (!split_ok && T.stretch_pair()) DCHK(hipEventRecord(T.stretch_pair()[1], st));  // (read after the call's final synchronisation)
-        T.end_fused(len, split_ok, n_split);
+        T.end_fused(len, split_ok, n_two);
         P = q;
         I.armed_it = it0 + ib;
         I.armed_q = q;

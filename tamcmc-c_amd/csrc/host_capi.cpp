@@ -170,7 +170,7 @@ int tamcmc_sampler_get_info(const tamcmc_sampler *s, int64_t *info, int32_t n) {
     v[TAMCMC_INFO_NCHAINS] = s->cfg.MALA.Nchains;
     v[TAMCMC_INFO_ADAPT_IN_LDS] = -1;
     if (s->dev) {
-        long d[11];
+        long d[13];
         s->dev->info(d);
         v[TAMCMC_INFO_ADAPT_IN_LDS] = d[2];
         v[TAMCMC_INFO_FUSED_AVAILABLE] = d[3];
@@ -180,6 +180,8 @@ int tamcmc_sampler_get_info(const tamcmc_sampler *s, int64_t *info, int32_t n) {
         v[TAMCMC_INFO_FUSED_STRETCHES] = d[8];
         v[TAMCMC_INFO_QUICK_FALLBACKS] = d[9];
         v[TAMCMC_INFO_QUICK_SURE] = d[10];
+        v[TAMCMC_INFO_ITER_JOINT] = d[11];
+        v[TAMCMC_INFO_ITER_WINDOW] = d[12];
     }
     for (int32_t i = 0; i < n && i < TAMCMC_SAMPLER_INFO_N; i++) info[i] = v[i];
     return TAMCMC_OK;

@@ -84,4 +84,75 @@ TAMCMC_HD bool joint_launch(bool split_ok, int xsplit, int A, int A_prev, bool f
     return !split_ok || straddles(split_ok, xsplit, A) || (!first && straddles(split_ok, xsplit, A_prev));
 }
 
+// ---- the launches of a two-group fused stretch, iteration by iteration (host only) ----
+//
+// Between straddling pairs the groups are [0, xsplit) on the first stream ("st") and [xsplit, C) on the second ("s1").  Around a
+// straddling pair (xsplit-1, xsplit) the boundary moves instead of the groups merging: an iteration is in a WINDOW when its own pair or
+// the previous iteration's straddles, and runs as [0, xsplit+1) on st and [xsplit+1, C) on s1 -- chain xsplit rides with the first
+// group, so both pairs lie inside one launch and the second group's other chains never stop.  A window iteration whose own or previous
+// pair is (xsplit, xsplit+1) -- it straddles the moved boundary -- or whose second group would be empty is the joint launch of
+// joint_launch().  Who waits for whom (stream events only):
+//   * st waits for s1 before the first launch of a window (chain xsplit's earlier launches ran on s1);
+//   * s1 waits for st before the first two-group launch after a window (chain xsplit returns), and after a joint launch;
+//   * st waits for s1 before a joint launch that follows two-group launches;
+//   * inside a window, past its first iteration, the two streams also meet where they share the SECOND EXTRA BLOCK of candidate slots
+//     (the cross candidates of chains >= xsplit, FusedArgs::xsplit: chain xsplit's on st, the other chains' on s1).  Launch i writes
+//     the block of candidate set (i+1) mod 3 and reads those of sets i mod 3 and (i-1) mod 3, so a writer must follow the other stream's
+//     two previous launches: s1 waits for st before a window launch whose pair lies in [xsplit+1, C), st waits for s1 before a window
+//     launch whose pair straddles again.  (tests/step_hazard_driver.cpp replays the plan against every buffer of the fused step.)
+// Everything else of the fused step is per chain, and a chain changes streams only across one of these waits.
+struct StepPlan {
+    int b;             // group 0 = chains [0, b) on st, group 1 = [b, C) on s1; b == C: one launch over all chains, on st
+    bool window;       // two launches with the moved boundary b = xsplit + 1
+    bool st_waits_s1;  // event hops before this iteration's launches
+    bool s1_waits_st;
+};
+
+struct StepPlanner {
+    bool split_ok;
+    int C, xsplit;
+    // who has not waited for whom (RunCall::run_fused sets s1_must_wait at the entry of a stretch)
+    bool s1_must_wait = false;  // st holds launches that s1's next launch must follow
+    bool s1_ahead = false;      // s1 holds launches that st has not waited for
+    bool in_window = false;     // the previous iteration ran as a window
+    bool first = true;          // nothing planned yet: the chains are settled, the pair before the stretch is nobody's business
+    int A_prev = -1;
+
+    StepPlanner(bool split_ok_, int C_, int xsplit_) : split_ok(split_ok_), C(C_), xsplit(xsplit_) {}
+
+    // The plan of the next iteration, whose swap pair is (A, A+1) (-1: none).  A = -1 after the stretch's last iteration plans its
+    // closing launches (the commit workgroups of the last iteration, which decide that iteration's swap).
+    StepPlan next(int A) {
+        StepPlan p;
+        p.window = false; p.st_waits_s1 = false; p.s1_waits_st = false;
+        const int Ap = first ? -1 : A_prev;
+        const bool near = joint_launch(split_ok, xsplit, A, A_prev, first);  // its own pair or the previous one straddles (or no split)
+        const bool joint = !split_ok || (near && (A == xsplit || Ap == xsplit || xsplit + 1 >= C));
+        if (joint) {
+            p.b = C;
+            p.st_waits_s1 = s1_ahead;
+            s1_ahead = false;
+            s1_must_wait = true;
+            in_window = false;
+        } else if (near) {
+            p.b = xsplit + 1;
+            p.window = true;
+            p.st_waits_s1 = s1_ahead && (!in_window || A == xsplit - 1);
+            p.s1_waits_st = s1_must_wait || (in_window && A > xsplit);
+            s1_ahead = true;
+            s1_must_wait = false;
+            in_window = true;
+        } else {
+            p.b = xsplit;
+            p.s1_waits_st = s1_must_wait || in_window;
+            s1_ahead = true;
+            s1_must_wait = false;
+            in_window = false;
+        }
+        A_prev = A;
+        first = false;
+        return p;
+    }
+};
+
 }  // namespace tamcmc
