@@ -1,7 +1,10 @@
 // fit_star.cpp -- a complete fit of one star driven from C++ through the C ABI only (include/tamcmc_*.h), the way a host that
 // keeps the reference's Config / .model / .data surface would use the library: no Python, no torch.
 //
-//   fit_star <local|global|asymptotic|simple> <star.model> <star.data> <sampler.cfg> <errors.cfg> <output root> [slice index]
+//   fit_star <local|global|asymptotic|simple> <star.model> <star.data> <sampler.cfg> <errors.cfg> <output root> [slice index] [--seed-fisher]
+//
+//   --seed-fisher: before the learning phase, seed every chain's proposal covariance from the Fisher information at the starting point
+//                  (tamcmc_sampler_seed_proposal_fisher; off by default; the table models only)
 //
 //   simple: the Gaussian-envelope fits (model ids 0, 1) -- their `.model` does not name its model, the .cfg's !Modeling model_fct_name does
 //
@@ -39,8 +42,15 @@ static const char *err() {
 }
 
 int main(int argc, char **argv) {
+    bool seed_fisher = false;
+    for (int i = 1, n = argc; i < n; i++)  // the switch may stand anywhere: taken out of the positional arguments
+        if (std::strcmp(argv[i], "--seed-fisher") == 0) {
+            seed_fisher = true;
+            for (int j = i; j + 1 < argc; j++) argv[j] = argv[j + 1];
+            argc--; n--; i--;
+        }
     if (argc < 7) {
-        std::fprintf(stderr, "usage: %s <local|global|asymptotic|simple> <star.model> <star.data> <sampler.cfg> <errors.cfg> <output root> [slice]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <local|global|asymptotic|simple> <star.model> <star.data> <sampler.cfg> <errors.cfg> <output root> [slice] [--seed-fisher]\n", argv[0]);
         return 2;
     }
     const std::string dialect = argv[1], root = argv[6];
@@ -118,6 +128,7 @@ int main(int argc, char **argv) {
     CHECK(tamcmc_sampler_create(&s, g_ctx, &sc), "sampler_create");
     // ---- learning, then the recorded samples (buffers of Nbuffer iterations appended to the output files)
     const int64_t n_learn = sc.n_Nt_learn > 0 ? Nt_learn[sc.n_Nt_learn - 1] : 0;
+    if (seed_fisher) CHECK(tamcmc_sampler_seed_proposal_fisher(s, 0.0, nullptr), "seed_proposal_fisher");
     CHECK(tamcmc_sampler_run(s, n_learn, nullptr, nullptr), "sampler_run (learning)");
     const int32_t C = sc.Nchains;
     const int64_t chunk = Nbuffer > 0 && Nbuffer < Nsamples ? Nbuffer : Nsamples;

@@ -121,6 +121,11 @@ extern "C" {
 #define TAMCMC_GRADIENT_FD 0         /* finite differences: Nvars perturbed likelihoods per chain (windowed or brute force) */
 #define TAMCMC_GRADIENT_ADJOINT 1    /* table-space adjoint with frozen windows: one pass over the bins per chain, whatever Nvars is */
 
+#define TAMCMC_OPT_FISHER_WORKSPACE_MB 10 /* value: MiB (>= 1, default 2048) of model rows tamcmc_hip_fisher keeps on the device per pass: a chain
+                                        takes 2 Nvars Nx 8 bytes, as many chains per pass as fit, a single chain above the budget still
+                                        runs alone.  The result does not depend on it */
+#define TAMCMC_FISHER_SLAB 2048      /* bins per workgroup (and per partial matrix) of the Gram kernel of tamcmc_hip_fisher / _weighted_gram */
+
 /* One (n,l) multiplet: <=7 Lorentzian m-components on its truncation window.
  * This is the flat "mode table" row every Lorentzian model of the dispatch table reduces to
  * (build_lorentzian.cpp:131-161, :208-246).  152 bytes, no padding. */
@@ -271,6 +276,38 @@ int tamcmc_hip_fd_gradient_posterior(tamcmc_hip_ctx *ctx, int model_id, int prio
  * makes the call return that status; its G and Gn are 0.  G, Gn, nrows may be NULL. */
 int tamcmc_hip_adjoint_table(tamcmc_hip_ctx *ctx, int model_id, int C, const double *params, int64_t Nparams, const int32_t *plength,
                              const double *Tcoefs, double p, double *G, double *Gn, int *nrows);
+
+/* Expected (Fisher) information of the chi^2(2p) likelihood at each of the C parameter vectors:
+ *   F_jk = (p / T_c) sum_i (d_j M_i)(d_k M_i) / M0_i^2,   j, k over the Nvars free variables (index_to_relax), the sum over all bins,
+ * M0 the model row at theta, T_c = Tcoefs[c] (NULL -> 1), p truncated to long as in the likelihood.  It is the expectation of the Hessian of
+ * -logL at y = M0: a quick Laplace error bar of a fit ((F + prior curvature)^-1) and a data-driven start for the proposal law
+ * (tamcmc_sampler_seed_proposal_fisher).  The derivative is the CENTRAL difference with FROZEN windows: the tables at theta +- hstep[k] e_k are
+ * built on the device by the gradient batch's builder, every row of both takes the base table's window [i0, i1) (as the adjoint route: no
+ * truncation edge crosses a bin between the two), both model rows are evaluated by the likelihood kernel, and
+ *   U_k,i = (M+_k,i - M-_k,i) / (h_applied,k M0_i),   F = (p / T) U U^T,
+ * h_applied,k = the difference of the two perturbed doubles as stored.  (With unfrozen windows F moves by up to 10 % of sqrt(F_jj F_kk) on a
+ * global fit with asymmetry; a forward difference moves it by 2e-3; the central form agrees with itself at h and h / 2 to 4e-5.)
+ * The rows stay on the device (TAMCMC_OPT_FISHER_WORKSPACE_MB); U U^T is accumulated per slab of TAMCMC_FISHER_SLAB bins in 16x16 blocks
+ * with the fp64 matrix instruction, the slabs are added in slab order.  One fixed order everywhere: two calls give the same bits, F is
+ * symmetric bit for bit, and a chain's F does not depend on the number of chains, its place in the batch or the number of passes.
+ * Out: F [C x Nvars x Nvars].  hstep[k] != 0.
+ * Models: the fixed-length table models, ids 3, 11, 12, 13, 14, 23; ids 0, 1 (no table) and 25, 27 (tables of variable length) return
+ * TAMCMC_ERR_BAD_MODEL.  Arithmetic: FAST or FAST_DIRECT; STRICT returns TAMCMC_ERR_BAD_ARG, as for the adjoint route.  A perturbed
+ * vector whose table fails makes the call return that status; row and column k of that chain's F are then NaN (all of it when the base
+ * table fails), the other chains are unaffected.
+ * Tolerance: the FAST tolerance of a model row (|dM|/M <= 1e-12 per bin) carried through the difference and the product: against the same
+ * quantity from long-double model rows, |dF_jk| <= 2 (p/T) (eps_k ||U_j||_1 + eps_j ||U_k||_1 + Nx eps_j eps_k), eps_k = 2e-12 / |h_applied,k|
+ * (tests/test_gpu_fisher.py; the factor 2 covers the device table builder's last-ulp differences in the frequencies). */
+int tamcmc_hip_fisher(tamcmc_hip_ctx *ctx, int model_id, int C, const double *params, int64_t Nparams, const int32_t *plength,
+                      const int32_t *index_to_relax, int Nvars, const double *hstep, const double *Tcoefs, double p,
+                      double *F /* [C x Nvars x Nvars] */);
+/* The audit entry of the same Gram and fold kernels on caller data: G [N x N] = sum_k w_k A_jk A_lk for A [N x K] row-major, w [K] or NULL
+ * (all ones).  With small integers every sum is exact in double, which checks the block layout and the lane map of the matrix instruction. */
+int tamcmc_hip_weighted_gram(tamcmc_hip_ctx *ctx, int N, int64_t K, const double *A /* [N x K] */, const double *w /* [K] or NULL */,
+                             double *G /* [N x N] */);
+/* Split of the last tamcmc_hip_fisher call made with TAMCMC_OPT_TIMING on, from HIP events on the context's stream, summed over its
+ * passes: table build, window freeze + row launches, Gram + fold (milliseconds; any pointer may be NULL). */
+int tamcmc_hip_get_fisher_times(tamcmc_hip_ctx *ctx, double *tables_ms, double *rows_ms, double *gram_ms);
 
 /* Timing of the likelihood kernel measured with HIP events on the context's own stream
  * (enabled by TAMCMC_OPT_TIMING): totals since the last reset. */

@@ -85,6 +85,8 @@ int64_t tamcmc_sampler_nvars(const tamcmc_sampler *s);
  *                                  TAMCMC_ERR_BAD_MODEL); host-driven engine: random walk or Langevin (tamcmc_hip_fd_gradient_posterior)
  *   Gaussian-envelope models       host-driven engine only (random walk or Langevin); engine = 1 -> TAMCMC_ERR_BAD_MODEL at
  *     (ids 0/1)                    tamcmc_sampler_create
+ *   tamcmc_sampler_seed_proposal   models 3, 11, 12, 13, 14, 23 on a FAST or FAST_DIRECT context (tamcmc_hip_fisher's refusals: ids 0, 1, 25,
+ *     _fisher                      27 -> TAMCMC_ERR_BAD_MODEL, STRICT -> TAMCMC_ERR_BAD_ARG); Nvars <= 16384
  * The host-driven engine has no size-dependent branches (host memory, column Cholesky).
  * tamcmc_sampler_get_info reports which side of each limit a sampler is on and how many iterations each scheme has run. */
 #define TAMCMC_INFO_ENGINE 0          /* 0 host-driven, 1 device-resident */
@@ -151,6 +153,19 @@ int tamcmc_sampler_get_move_counts(const tamcmc_sampler *s, int64_t *moves);
 /* proposal law of chain m: mu [Nvars], covarmat [Nvars x Nvars] (restore file content, outputs.cpp:863-1025) */
 int tamcmc_sampler_get_proposal(const tamcmc_sampler *s, int32_t m, double *mu, double *covarmat);
 int tamcmc_sampler_set_proposal(tamcmc_sampler *s, int32_t m, const double *mu, const double *covarmat, double sigma);
+/* Seeds every chain's proposal covariance from the curvature of the likelihood at the chain's CURRENT position (tamcmc_hip_fisher, one call
+ * per chain with the steps h_k = hstep_rel max(|theta_k|, 1e-2); hstep_rel = 0 means 1e-6): with F_m the expected information at the chain's
+ * temperature T_m and E = diag(init_errors),
+ *   Sigma_m = E (I + E F_m E)^-1 E      ( = (F_m + E^-2)^-1, written so that a zero initial error or a variable without information is harmless:
+ *                                         every eigenvalue of I + E F E is >= 1, and diag Sigma <= e^2 -- never wider than the default law).
+ * The inverse is taken on the host from a Cholesky factor in long double; Sigma_m goes through tamcmc_sampler_set_proposal, so both
+ * engines get it; mu and sigma are not touched.  F (may be NULL) receives the F_m, [Nchains x Nvars x Nvars].  Never called implicitly:
+ * without it nothing changes.  Any failure (a refusal of tamcmc_hip_fisher, a table that fails at a perturbed point, a non-finite F)
+ * returns the status and leaves every proposal law as it was. */
+int tamcmc_sampler_seed_proposal_fisher(tamcmc_sampler *s, double hstep_rel, double *F /* may be NULL, [Nchains x Nv x Nv] */);
+/* The rule alone, on the host (no device): cov [Nvars x Nvars] = E (I + E F E)^-1 E for a symmetric F and E = diag(errors); symmetric bit
+ * for bit.  TAMCMC_ERR_BAD_ARG for a non-finite entry or an F so far from positive semi-definite that I + E F E has no Cholesky factor. */
+int tamcmc_fisher_seed_covariance(int32_t Nvars, const double *F, const double *errors, double *cov);
 /* Chain positions vars [Nchains x Nvars] from outside (restart): priors and likelihoods are re-evaluated on the device;
  * iteration >= 0 also sets the iteration counter (the learning schedule and gamma = c0/(1+i) depend on it). */
 int tamcmc_sampler_set_state(tamcmc_sampler *s, const double *vars, int64_t iteration);

@@ -28,6 +28,8 @@ MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4 = 25  # batched device paths only (loglike_param
 PRECISION_STRICT, PRECISION_FAST, PRECISION_FAST_DIRECT = 0, 1, 2
 OPT_PRECISION, OPT_TIMING, OPT_BINS_PER_THREAD, OPT_WORKGROUP, OPT_FD_WINDOWED, OPT_STEP_SCHEME, OPT_ARMM_DENSE_SCAN = 1, 2, 3, 4, 5, 6, 7
 OPT_GRADIENT, GRADIENT_FD, GRADIENT_ADJOINT = 9, 0, 1  # gradient batches: finite differences (default) / table-space adjoint, frozen windows
+OPT_FISHER_WORKSPACE_MB = 10  # MiB of model rows HipContext.fisher keeps on the device per pass (default 2048)
+FISHER_SLAB = 2048  # bins per workgroup of the Gram kernel (TAMCMC_FISHER_SLAB)
 OPT_QUICK_DECIDE = 8  # test facility: 1 = the fused step's decision shortcut always falls back to the exact evaluation
 
 
@@ -64,6 +66,9 @@ ABI = [
     ("tamcmc_hip_fd_gradient_posterior", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, C.c_int64, _ip, _ip, C.c_int, _dp, _dp, C.c_double,
                                                   _dp, _ip, _dp, _dp, _dp, _dp, _dp]),
     ("tamcmc_hip_adjoint_table", C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int64, _ip, _dp, C.c_double, _dp, _dp, C.POINTER(C.c_int)]),
+    ("tamcmc_hip_fisher", C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int64, _ip, _ip, C.c_int, _dp, _dp, C.c_double, _dp]),
+    ("tamcmc_hip_weighted_gram", C.c_int, [_vp, C.c_int, C.c_int64, _dp, _dp, _dp]),
+    ("tamcmc_hip_get_fisher_times", C.c_int, [_vp, _dp, _dp, _dp]),
     ("tamcmc_hip_rgb_mixed_modes", C.c_int, [_vp, C.c_int, _dp, C.c_int64, _ip, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int)]),
     ("tamcmc_hip_get_kernel_stats", C.c_int, [_vp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("tamcmc_hip_reset_kernel_stats", C.c_int, [_vp]),
@@ -264,6 +269,39 @@ class HipContext:
         self._chk(self._L.tamcmc_hip_adjoint_table(self._h, int(model_id), Cn, _p(params), Np, _p(plength, _ip), _p(T), float(p), _p(G), _p(Gn),
                                                    C.byref(n)))
         return G, Gn
+
+    def fisher(self, model_id, params, plength, index_to_relax, hstep, Tcoefs=None, p=1.0):
+        """Expected (Fisher) information F [C x Nvars x Nvars] of the likelihood at each row of params (tamcmc_hip_fisher): central
+        differences with frozen windows, F = (p / T) U U^T.  A table that fails at a perturbed point leaves NaN in that row and column;
+        the status of the call is left in self.last_fisher_status."""
+        params = _f64(params)
+        if params.ndim == 1:
+            params = params[None, :]
+        Cn, Np = params.shape
+        plength, idx, h = _i32(plength), _i32(index_to_relax), _f64(hstep)
+        assert h.size == idx.size
+        T = _f64(Tcoefs) if Tcoefs is not None else None
+        F = np.zeros((Cn, idx.size, idx.size))
+        st = self._L.tamcmc_hip_fisher(self._h, int(model_id), Cn, _p(params), Np, _p(plength, _ip), _p(idx, _ip), idx.size, _p(h), _p(T),
+                                      float(p), _p(F))
+        self.last_fisher_status = self._chk(st, tolerate=(ERR_EMPTY_WINDOW, ERR_NAN_WINDOW))
+        return F
+
+    def fisher_times(self):
+        """(table build, row launches, Gram + fold) of the last fisher() call in ms (HIP events; the context's timing option on)."""
+        a, b, g = C.c_double(0), C.c_double(0), C.c_double(0)
+        self._chk(self._L.tamcmc_hip_get_fisher_times(self._h, C.byref(a), C.byref(b), C.byref(g)))
+        return a.value, b.value, g.value
+
+    def weighted_gram(self, A, w=None):
+        """G [N x N] = sum_k w_k A_jk A_lk through the Gram and fold kernels of fisher() (tamcmc_hip_weighted_gram; w None: ones)."""
+        A = _f64(A)
+        assert A.ndim == 2
+        w = _f64(w) if w is not None else None
+        assert w is None or w.shape == (A.shape[1],)
+        G = np.zeros((A.shape[0], A.shape[0]))
+        self._chk(self._L.tamcmc_hip_weighted_gram(self._h, A.shape[0], A.shape[1], _p(A), _p(w), _p(G)))
+        return G
 
     def rgb_mixed_modes(self, model_id, params, plength, max_modes=1024):
         """l=1 mixed modes of one red-giant vector from the device pre-step: (nu_m, zeta, H1/H0) -- what ARMM's do_solve prints."""

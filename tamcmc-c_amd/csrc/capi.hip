@@ -68,7 +68,7 @@ void tamcmc_hip_destroy(tamcmc_hip_ctx *c) {
     c->h_stage.release(); c->d_stage.release();
     c->d_part.release(); c->d_S.release(); c->d_model.release(); c->h_S.release();
     c->d_fd.release(); c->d_poly.release(); c->h_fd.release();
-    c->d_rgb.release(); c->h_rgb.release(); c->d_bg.release(); c->d_env.release();
+    c->d_rgb.release(); c->h_rgb.release(); c->d_bg.release(); c->d_env.release(); c->d_fisher.release();
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -105,6 +105,10 @@ int tamcmc_hip_set_option(tamcmc_hip_ctx *c, int option, int64_t value) {
     case TAMCMC_OPT_GRADIENT:
         if (value != TAMCMC_GRADIENT_FD && value != TAMCMC_GRADIENT_ADJOINT) return TAMCMC_ERR_BAD_ARG;
         c->gradient = (int)value;
+        return TAMCMC_OK;
+    case TAMCMC_OPT_FISHER_WORKSPACE_MB:
+        if (value < 1 || value > (1 << 20)) return TAMCMC_ERR_BAD_ARG;
+        c->fisher_ws_mb = value;
         return TAMCMC_OK;
     case TAMCMC_OPT_WORKGROUP:  // sets the workgroup size AND its default bins per thread
         if (value != 64 && value != 256) return TAMCMC_ERR_BAD_ARG;

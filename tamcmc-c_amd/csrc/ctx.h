@@ -69,6 +69,7 @@ struct tamcmc_hip_ctx {
                           // 2 = fused, always one launch per iteration, 3 = fused, two chain groups whenever the chain count allows
     int quick_decide = 0; // device sampler, fused step (a test facility): 1 = every margin test of the decision shortcut answers "undecided"
     int armm_dense = 0;   // red-giant pre-step: 1 = dense grid walk
+    int64_t fisher_ws_mb = 2048;  // tamcmc_hip_fisher: budget of the model rows kept on the device per pass, MiB (fd_rgb_chunk.h: fisher_chunk)
     int gradient = TAMCMC_GRADIENT_FD;  // gradient batches: finite differences, or the table-space adjoint with frozen windows (adjoint.h)
     // resident spectrum
     int64_t Nx = 0;
@@ -88,6 +89,8 @@ struct tamcmc_hip_ctx {
     tamcmc::DevBuf<unsigned char> d_fd, d_poly;
     tamcmc::PinBuf<unsigned char> h_fd;
     bool poly_ready = false;
+    tamcmc::DevBuf<double> d_fisher;  // Fisher information (fisher.hip): 1/h_applied, weights, slab partials, F
+    double fisher_ms[3] = {0, 0, 0};  // last tamcmc_hip_fisher call with timing on: table build, row launches, Gram + fold (HIP events, summed over passes)
     tamcmc::PinBuf<double> h_S;
     // samplers created on this context (they borrow its stream and buffers): tamcmc_hip_destroy with samplers still attached only
     // marks the context; the last tamcmc_sampler_destroy frees it -- any destruction order is safe

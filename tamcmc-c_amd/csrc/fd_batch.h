@@ -20,6 +20,11 @@ struct FdBatch {
     // difference -- so the sums read like the windowed route's (deltas()).  `windowed` is then false: no delta tables exist.
     bool adjoint = false;
     bool deltas() const { return windowed || adjoint; }  // S = C base sums, then B differences against them
+    // Fisher rows (fisher.h; set BEFORE layout(), off by default): neither windowed nor adjoint whatever the context's options say; enqueue()
+    // stops after the tables -- every perturbed table gets its base table's windows [i0, i1) ("frozen window", k_fisher_freeze) -- and ONE
+    // likelihood launch that leaves the B model rows in `model` ([B x Nx]; the sums S are not formed).  The caller passes 2 Nvars "variables":
+    // idx = [index_to_relax, index_to_relax], h = [+h, -h], so with N the caller's variables (this batch's Nvars / 2) slot c*E + 1 + k is theta + h_k e_k and slot c*E + 1 + N + k is theta - h_k e_k.
+    bool rows_only = false;
     size_t model_doubles = 0;  // doubles of `model` that enqueue() needs (0: none)
     size_t bg_rows = 0;        // rows of `bgbuf` (x ntiles x 8 doubles) under FAST arithmetic
     bool rgb = false;  // red-giant models (ids 25 / 27): tables through the device pre-step, `chunk` vectors at a time

@@ -29,6 +29,7 @@
 #include "fd_batch.h"
 #include "rgb_prestep.h"
 #include "adjoint.h"
+#include "fisher.h"
 
 namespace tamcmc {
 namespace {
@@ -350,7 +351,8 @@ int FdBatch::layout(tamcmc_hip_ctx *c, int model_id_, int prior_class_, int C_, 
     model_id = model_id_; prior_class = prior_class_; C = C_; Np = Nparams; Nvars = Nvars_;
     rgb = (model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4_ID || model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4_ID);
     E = Nvars + 1; B = C * E;
-    adjoint = c->gradient == TAMCMC_GRADIENT_ADJOINT;
+    adjoint = !rows_only && c->gradient == TAMCMC_GRADIENT_ADJOINT;
+    if (rows_only && (rgb || c->precision == TAMCMC_PRECISION_STRICT)) return TAMCMC_ERR_BAD_ARG;  // (tamcmc_hip_fisher refuses both before it gets here)
     if (adjoint) {
         if (rgb) return TAMCMC_ERR_BAD_MODEL;  // (tables of variable length: no row-by-row contraction)
         if (c->precision == TAMCMC_PRECISION_STRICT) return TAMCMC_ERR_BAD_ARG;  // (the planes are the FAST base launch's)
@@ -386,7 +388,7 @@ int FdBatch::layout(tamcmc_hip_ctx *c, int model_id_, int prior_class_, int C_, 
     out_bytes = o - in_bytes;
     // windowed finite differences (FAST modes): only the multiplets a perturbation changes are re-evaluated, on their
     // windows, against the stored base model row ("the main algorithmic lever")
-    windowed = !adjoint && c->fd_windowed && c->precision != TAMCMC_PRECISION_STRICT && delta_geometry(c->wgs, c->K) && Nvars > 0;
+    windowed = !adjoint && !rows_only && c->fd_windowed && c->precision != TAMCMC_PRECISION_STRICT && delta_geometry(c->wgs, c->K) && Nvars > 0;
     const int nslots = (windowed && !rgb) ? 2 * B : B;         // windowed: slots [B, 2B) = per-block copies of the base table (not for red giants)
     const StageLayout L(nslots, stride, (size_t)nslots * per);
     o_tab = o; o = al16(o + L.bytes);
@@ -421,6 +423,7 @@ int FdBatch::layout(tamcmc_hip_ctx *c, int model_id_, int prior_class_, int C_, 
     model_doubles = 0;
     if (adjoint) model_doubles = 3 * (size_t)C * c->Nx;
     if (windowed) model_doubles = 3 * (size_t)C * c->Nx + 2 * (size_t)C * ntiles * FD_MOM + ((size_t)B * ntiles + 7) / 8;
+    if (rows_only) model_doubles = (size_t)B * c->Nx;
     bg_rows = deltas() ? (size_t)C : (size_t)B;
     return TAMCMC_OK;
 }
@@ -498,7 +501,19 @@ int FdBatch::enqueue(tamcmc_hip_ctx *c, unsigned char *db, const double *d_param
     a.x0 = c->hx[0]; a.step = c->hx[1] - c->hx[0];
     a.noise_stride = stride; a.model = nullptr;
     if (ev0) HIPCHK(c, hipEventRecord(ev0, st));
-    if (adjoint) {
+    if (rows_only) {
+        // Fisher rows: frozen windows, then the B model rows (no sums are read: the partials are the launch's scratch)
+        HIPCHK(c, launch_fisher_freeze(fa.T.mults, fa.T.pairs, fa.status, per, C, E, st));
+        a.B = B;
+        a.mults = fa.T.mults; a.offsets = fa.T.pairs; a.noise = fa.T.noise; a.nharvey = fa.T.nh; a.nnoise = fa.T.nn;
+        a.partials = part; a.model = model;
+        if (c->precision == TAMCMC_PRECISION_FAST) {
+            HIPCHK(c, launch_bg_poly(a, c->wgs, c->K, bgbuf, st));
+            a.bg_poly = bgbuf;
+        }
+        HIPCHK(c, launch_loglike(a, c->precision, c->wgs, c->K, true, st));
+        d_done = nullptr;
+    } else if (adjoint) {
         // (1) the C base points, exactly the windowed route's base launch: planes 1/M0, y/M0 (and M0) kept
         a.B = C;
         a.mults = fa.T.mults; a.offsets = fa.Bs.pairs; a.noise = fa.Bs.noise; a.nharvey = fa.Bs.nh; a.nnoise = fa.Bs.nn;

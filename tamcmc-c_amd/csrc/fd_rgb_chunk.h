@@ -14,6 +14,12 @@ inline int fd_rgb_chunk(int B, size_t per_vector, size_t budget) {
     if (n < 1) n = 1;
     return n < (size_t)(B > 0 ? B : 1) ? (int)n : (B > 0 ? B : 1);
 }
+// The same rule for the chains of a Fisher-information call (fisher.hip): a chain keeps the model rows of its 2 Nvars perturbed vectors on
+// the device, 2 Nvars Nx 8 bytes; as many chains per pass as fit TAMCMC_OPT_FISHER_WORKSPACE_MB (default below), a single chain above the
+// budget still runs alone.
+constexpr size_t FISHER_WORKSPACE_MB = 2048;
+inline size_t fisher_chain_bytes(int Nvars, long Nx) { return (size_t)2 * (size_t)(Nvars > 0 ? Nvars : 0) * (size_t)(Nx > 0 ? Nx : 0) * 8; }
+inline int fisher_chunk(int C, int Nvars, long Nx, size_t budget_mb) { return fd_rgb_chunk(C, fisher_chain_bytes(Nvars, Nx), budget_mb << 20); }
 // Chunks a batch of B vectors takes.
 inline int fd_rgb_chunks(int B, int chunk) { return B > 0 ? (B + chunk - 1) / chunk : 0; }
 

@@ -357,6 +357,72 @@ int tamcmc_sampler_set_proposal(tamcmc_sampler *s, int32_t m, const double *mu, 
     return TAMCMC_OK;
 }
 
+// Sigma = E (I + E F E)^-1 E (include/tamcmc_sampler.h): A = I + E F E, its Cholesky factor L (lower, in place), X = L^-1, A^-1 = X^T X --
+// all in long double; the upper triangle is computed and mirrored
+int tamcmc_fisher_seed_covariance(int32_t Nvars, const double *F, const double *errors, double *cov) {
+    if (Nvars < 1 || !F || !errors || !cov) return TAMCMC_ERR_BAD_ARG;
+    const size_t n = (size_t)Nvars;
+    std::vector<long double> A(n * n), X(n * n);
+    for (size_t j = 0; j < n; j++)
+        for (size_t k = 0; k < n; k++) {
+            if (!std::isfinite(F[j * n + k]) || !std::isfinite(errors[j])) return TAMCMC_ERR_BAD_ARG;
+            A[j * n + k] = (long double)errors[j] * (long double)F[j * n + k] * (long double)errors[k] + (j == k ? 1.0L : 0.0L);
+        }
+    for (size_t j = 0; j < n; j++) {
+        long double d = A[j * n + j];
+        for (size_t q = 0; q < j; q++) d -= A[j * n + q] * A[j * n + q];
+        if (!(d > 0.0L)) return TAMCMC_ERR_BAD_ARG;  // (not for a positive semi-definite F: every eigenvalue of A is >= 1)
+        d = std::sqrt(d);
+        A[j * n + j] = d;
+        for (size_t i = j + 1; i < n; i++) {
+            long double v = A[i * n + j];
+            for (size_t q = 0; q < j; q++) v -= A[i * n + q] * A[j * n + q];
+            A[i * n + j] = v / d;
+        }
+    }
+    for (size_t col = 0; col < n; col++)  // X = L^-1 by forward substitution, column by column (lower triangular)
+        for (size_t i = 0; i < n; i++) {
+            long double v = i == col ? 1.0L : 0.0L;
+            for (size_t q = col; q < i; q++) v -= A[i * n + q] * X[q * n + col];
+            X[i * n + col] = i < col ? 0.0L : v / A[i * n + i];
+        }
+    for (size_t j = 0; j < n; j++)
+        for (size_t k = j; k < n; k++) {
+            long double v = 0.0L;
+            for (size_t q = k; q < n; q++) v += X[q * n + j] * X[q * n + k];
+            cov[j * n + k] = cov[k * n + j] = (double)((long double)errors[j] * v * (long double)errors[k]);
+        }
+    return TAMCMC_OK;
+}
+
+// Sigma_m = E (I + E F_m E)^-1 E with F_m = tamcmc_hip_fisher at chain m's position and temperature (include/tamcmc_sampler.h)
+int tamcmc_sampler_seed_proposal_fisher(tamcmc_sampler *s, double hstep_rel, double *F) {
+    if (!s || !(hstep_rel >= 0.0)) return TAMCMC_ERR_BAD_ARG;
+    if (int rc = s->refresh()) return rc;
+    const long Nc = s->cfg.MALA.Nchains, Nv = s->cur->get_Nvars(), Np = s->cur->get_Nparams();
+    const double rel = hstep_rel > 0.0 ? hstep_rel : 1e-6;
+    const std::vector<int> idx(s->cur->get_index_to_relax());
+    const std::vector<double> &err = s->cfg.MALA.offset_errors;
+    if ((long)idx.size() != Nv || (long)err.size() != Nv) return TAMCMC_ERR_BAD_ARG;
+    const size_t n = (size_t)Nv;
+    std::vector<double> Fm((size_t)Nc * n * n), cov((size_t)Nc * n * n), h(n);
+    for (long m = 0; m < Nc; m++) {
+        const double *theta = s->cur->params.row(m);
+        for (size_t k = 0; k < n; k++) h[k] = rel * std::fmax(std::fabs(theta[idx[k]]), 1e-2);
+        double *Fc = Fm.data() + (size_t)m * n * n;
+        const int rc = tamcmc_hip_fisher(s->ctx, s->cfg.modeling.model_fct_name_switch, 1, theta, Np, s->cfg.modeling.inputs.plength.data(), idx.data(),
+                                         (int)Nv, h.data(), &s->mala->Tcoefs[(size_t)m], s->cfg.modeling.likelihood_params, Fc);
+        if (rc) return rc;
+        if (int rc2 = tamcmc_fisher_seed_covariance((int32_t)Nv, Fc, err.data(), cov.data() + (size_t)m * n * n)) return rc2;
+    }
+    for (long m = 0; m < Nc; m++) {
+        const int rc = tamcmc_sampler_set_proposal(s, (int32_t)m, nullptr, cov.data() + (size_t)m * n * n, 0.0);
+        if (rc) return rc;
+    }
+    if (F) std::memcpy(F, Fm.data(), Fm.size() * sizeof(double));
+    return TAMCMC_OK;
+}
+
 // Chain positions (and optionally the iteration counter) from outside: restart / resume (Config::read_restore_files +
 // Model_def constructor path of the reference, config.cpp:1734-1990, MALA.cpp:100-131).  Re-evaluates prior and likelihood.
 int tamcmc_sampler_set_state(tamcmc_sampler *s, const double *vars, int64_t iteration) {

@@ -36,6 +36,8 @@ EXTRA_ABI += [
     ("tamcmc_sampler_get_state", C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _i64p]),
     ("tamcmc_sampler_get_proposal", C.c_int, [_vp, C.c_int32, _dp, _dp]),
     ("tamcmc_sampler_set_proposal", C.c_int, [_vp, C.c_int32, _dp, _dp, C.c_double]),
+    ("tamcmc_sampler_seed_proposal_fisher", C.c_int, [_vp, C.c_double, _dp]),
+    ("tamcmc_fisher_seed_covariance", C.c_int, [C.c_int32, _dp, _dp, _dp]),
     ("tamcmc_sampler_set_state", C.c_int, [_vp, _dp, C.c_int64]),
     ("tamcmc_outputs_write_restore", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_char_p), _dp, _dp, _dp, _dp]),
     ("tamcmc_outputs_read_restore", C.c_int, [C.c_char_p, _ip, _ip, _i64p, _dp, _dp, _dp, _dp]),
@@ -230,6 +232,27 @@ class Sampler:
         mu = _f64(mu) if mu is not None else None
         cov = _f64(cov) if cov is not None else None
         self._L.tamcmc_sampler_set_proposal(self._h, int(m), _p(mu), _p(cov), float(sigma))
+
+    def seed_proposal_fisher(self, hstep_rel=0.0):
+        """Seeds every chain's proposal covariance with E (I + E F E)^-1 E, F the Fisher information at the chain's position and temperature
+        (tamcmc_sampler_seed_proposal_fisher; hstep_rel = 0: 1e-6).  Returns F [Nchains x Nvars x Nvars]."""
+        F = np.zeros((self.nchains, self.nvars, self.nvars))
+        rc = self._L.tamcmc_sampler_seed_proposal_fisher(self._h, float(hstep_rel), _p(F))
+        if rc != OK:
+            raise TamcmcError(rc, "tamcmc_sampler_seed_proposal_fisher: " + self._L.tamcmc_hip_last_error(self.ctx._h).decode())
+        return F
+
+
+def fisher_seed_covariance(F, errors):
+    """E (I + E F E)^-1 E on the host (tamcmc_fisher_seed_covariance): the rule of Sampler.seed_proposal_fisher for one chain."""
+    L = _rebind()
+    F, e = _f64(F), _f64(errors)
+    assert F.shape == (e.size, e.size)
+    cov = np.zeros_like(F)
+    rc = L.tamcmc_fisher_seed_covariance(e.size, _p(F), _p(e), _p(cov))
+    if rc != OK:
+        raise TamcmcError(rc, "tamcmc_fisher_seed_covariance")
+    return cov
 
 
 def default_errors(star):
