@@ -16,14 +16,14 @@ struct MalaArgs {
     const double *S, *lpp, *lpm;  // sums / log-priors (forward, backward) of the last finite-difference batch (fd_batch.h)
     const int *st;                // ... and its per-evaluation status
     double *h;                    // [Nv] forward-difference steps of the NEXT batch (written by chain 0's workgroup)
-    int E, windowed;
+    int E, deltas;                // deltas: S = C base sums, then the differences against them (FdBatch::deltas())
     double fd_step_rel, delta;
     double *grad_prop, *gradP_prop, *drift_cur;  // [C][Nv] gradient (and the prior's share) at the proposals; drift used by the proposals
     double *out;                  // [C][5] post-test outcome: acc, r, logL, logPr, logPost
 };
 
-// Gradient of the tempered log-posterior at the batch's base point of chain c (compute_gradients, host_mala.cpp; assembly of fd_run,
-// fd_batch.hip): lane k -> g[k], gp[k] (the prior's share) in LDS.  base = the base point's parameter vector.  L0 / pr0 / st0 of the base
+// Gradient of the tempered log-posterior at the batch's base point of chain c (compute_gradients, host_mala.cpp; the host's assembly is
+// assemble_gradient, fd_batch.hip): lane k -> g[k], gp[k] (the prior's share) in LDS.  base = the base point's parameter vector.  L0 / pr0 / st0 of the base
 // evaluation are returned to every lane.
 __device__ void mala_gradient(const DevSamplerArgs &a, const MalaArgs &M, int c, const double *base, double *g, double *gp, double &L0,
                               double &pr0, int &st0) {
@@ -31,7 +31,7 @@ __device__ void mala_gradient(const DevSamplerArgs &a, const MalaArgs &M, int c,
     const double T = a.Tcoefs[c];
     auto scaled = [&](double S) { return (-(double)a.pl * S) / T; };  // call_likelihood, model_def.cpp:399-401
     st0 = M.st[(size_t)c * E];
-    L0 = (st0 != TAMCMC_OK) ? (double)NAN : scaled(M.windowed ? M.S[c] : M.S[(size_t)c * E]);
+    L0 = (st0 != TAMCMC_OK) ? (double)NAN : scaled(M.deltas ? M.S[c] : M.S[(size_t)c * E]);
     pr0 = M.lpp[(size_t)c * E];
     for (int k = threadIdx.x; k < Nv; k += blockDim.x) {
         const size_t e = (size_t)c * E + k + 1;
@@ -40,7 +40,7 @@ __device__ void mala_gradient(const DevSamplerArgs &a, const MalaArgs &M, int c,
         const double happ = xp - x0;  // the step actually applied (k_fd_unpack adds the same two doubles)
         double dl;
         if (M.st[e] != TAMCMC_OK || st0 != TAMCMC_OK) dl = NAN;
-        else dl = M.windowed ? scaled(M.S[(size_t)C + e]) : scaled(M.S[e]) - L0;
+        else dl = M.deltas ? scaled(M.S[(size_t)C + e]) : scaled(M.S[e]) - L0;
         double gv = dl / happ;
         if (!isfinite(gv)) gv = 0.0;
         const double prp = M.lpp[e], prm = M.lpm[e];

@@ -1023,12 +1023,13 @@ int DevSampler::run_mala(long it0, long n_iter, const char *learn, double *sampl
     hipStream_t st = c->stream;
     I.armed_it = -1;
     const size_t C = (size_t)a.C, Nv = (size_t)a.Nv, Np = (size_t)a.desc.Np;
+    const FdBatch::Buffers fd_ws{I.fd_part, I.fd_S, I.fd_model, I.fd_bg};
     {   // the batch's layout follows the context's options (arithmetic mode, geometry, windowed differences): re-laid out when they change
         FdBatch nb;
-        int rc = nb.layout(c, I.model_id, I.prior_class, a.C, (int64_t)Np, I.h_plength.data(), a.Nv);
+        int rc = nb.layout(c, FdBatch::Request::FromOptions, I.model_id, I.prior_class, a.C, (int64_t)Np, I.h_plength.data(), a.Nv);
         if (rc) return rc;
         const bool need_bg = c->precision == TAMCMC_PRECISION_FAST && !I.fd_bg.p;  // (a switch to FAST between two calls keeps every size)
-        if (nb.total_bytes != I.fd.total_bytes || nb.windowed != I.fd.windowed || nb.adjoint != I.fd.adjoint || nb.ntiles != I.fd.ntiles || !I.fd_block.p || need_bg) {
+        if (nb.total_bytes != I.fd.total_bytes || nb.route != I.fd.route || nb.ntiles != I.fd.ntiles || !I.fd_block.p || need_bg) {
             I.fd = nb;
             rc = fd_ensure_poly(c);
             if (rc) return rc;
@@ -1041,10 +1042,7 @@ int DevSampler::run_mala(long it0, long n_iter, const char *learn, double *sampl
             std::memcpy(hb.data() + nb.o_idx, I.h_idx.data(), Nv * 4);
             DCHK(hipMemcpyAsync(I.fd_block.p, hb.data(), nb.in_bytes, hipMemcpyHostToDevice, st));
             DCHK(hipStreamSynchronize(st));
-            DCHK(I.fd_part.reserve(nb.nS * (size_t)nb.ntiles * 2));
-            DCHK(I.fd_S.reserve(nb.nS));
-            if (nb.model_doubles) DCHK(I.fd_model.reserve(nb.model_doubles));  // three planes (1/M0, y/M0, M0 of the base points) + tile moments (two layouts) + done flags
-            if (c->precision == TAMCMC_PRECISION_FAST) DCHK(I.fd_bg.reserve(nb.bg_rows * nb.ntiles * 8));
+            DCHK(nb.reserve(c, fd_ws));
             I.grad_valid = false;
         }
     }
@@ -1052,7 +1050,7 @@ int DevSampler::run_mala(long it0, long n_iter, const char *learn, double *sampl
     unsigned char *db = I.fd_block.p;
     MalaArgs M = I.mala;
     M.S = I.fd_S.p; M.lpp = (const double *)(db + fd.o_lpp); M.lpm = (const double *)(db + fd.o_lpm); M.st = (const int *)(db + fd.o_st);
-    M.h = (double *)(db + fd.o_h); M.E = fd.E; M.windowed = fd.deltas() ? 1 : 0; M.fd_step_rel = I.fd_step_rel; M.delta = I.delta;
+    M.h = (double *)(db + fd.o_h); M.E = fd.E; M.deltas = fd.deltas() ? 1 : 0; M.fd_step_rel = I.fd_step_rel; M.delta = I.delta;
     if (samples && I.smp_cap < (size_t)n_iter * C * Nv) {
         DCHK(I.dalloc(&a.samples, (size_t)n_iter * C * Nv));
         I.smp_cap = (size_t)n_iter * C * Nv;
@@ -1075,7 +1073,7 @@ int DevSampler::run_mala(long it0, long n_iter, const char *learn, double *sampl
         DCHK(hipFuncSetAttribute((const void *)k_mala_test, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_test0 + lds_adapt)));
     int P = I.parity;
     auto batch = [&](const double *d_params, bool timed) -> int {
-        return fd.enqueue(c, db, d_params, I.fd_part.p, I.fd_S.p, I.fd_model.p, I.fd_bg.p, timed ? I.ev[0][0] : nullptr, timed ? I.ev[0][1] : nullptr);
+        return fd.enqueue(c, db, d_params, fd_ws, timed ? I.ev[0][0] : nullptr, timed ? I.ev[0][1] : nullptr);
     };
     if (!I.grad_valid) {  // gradient at the chains' current positions (start of a run, new positions from outside)
         hipLaunchKernelGGL(k_mala_steps, dim3(1), dim3(256), 0, st, args, M);
@@ -1109,12 +1107,10 @@ int DevSampler::run_mala(long it0, long n_iter, const char *learn, double *sampl
             DCHK(hipEventElapsedTime(&ms, I.ev[0][0], I.ev[0][1]));
             kernel_ms += ms;
             n_timed++;
-            if (fd.windowed) {  // what the delta launch really touched (roofline bookkeeping, as fd_run does)
-                std::vector<int> rg((size_t)2 * fd.B);
-                DCHK(hipMemcpy(rg.data(), db + fd.o_drange, rg.size() * sizeof(int), hipMemcpyDeviceToHost));
+            if (fd.route == FdBatch::Route::Windowed) {  // what the delta launch really touched (roofline bookkeeping, as fd_run does)
                 long bins = 0;
-                for (int q2 = 0; q2 < fd.B; q2++) bins += rg[2 * (size_t)q2 + 1] - rg[2 * (size_t)q2];
-                fd_bins_sampled += bins - fd.bins_not_walked();
+                DCHK(fd.delta_stats(db, &bins, nullptr));
+                fd_bins_sampled += bins;
             }
         }
     }
@@ -1127,7 +1123,7 @@ int DevSampler::run_mala(long it0, long n_iter, const char *learn, double *sampl
         c->launches += n_iter;
         c->evals += n_iter * (long)fd.B;
         c->fd_bins += fd_bins_sampled / n_timed * n_iter;
-        c->fd_delta_evals += fd.windowed ? n_iter * (long)fd.B : 0;
+        c->fd_delta_evals += fd.route == FdBatch::Route::Windowed ? n_iter * (long)fd.B : 0;
     }
     return TAMCMC_OK;
 }

@@ -25,6 +25,7 @@
 #include "../../include/tamcmc_hip.h"
 #include "ctx.h"
 #include "envelope.h"
+#include "fd_batch.h"
 #include "kernels.h"
 #include "priors_impl.h"
 
@@ -309,7 +310,7 @@ int envelope_fd_run(tamcmc_hip_ctx *c, int model_id, bool with_prior, int prior_
     if (rc) return rc;
     if (with_prior && prior_class != model_id) return TAMCMC_ERR_BAD_MODEL;  // priors_ctrl.list pairs class 0 with id 0, class 1 with id 1
     const int E = Nvars + 1;
-    const size_t B = (size_t)C * E, Np = (size_t)Nparams, Nv = (size_t)Nvars;
+    const size_t B = (size_t)C * E, Np = (size_t)Nparams;
     if (B > 65535) return TAMCMC_ERR_BAD_ARG;  // grid.y
     // forward points theta + h e_k (the same double addition the gradient's divisor uses), then the backward points theta - h e_k
     std::vector<double> P((with_prior ? 2 : 1) * B * Np);
@@ -358,35 +359,9 @@ int envelope_fd_run(tamcmc_hip_ctx *c, int model_id, bool with_prior, int prior_
     int first_err = TAMCMC_OK;
     for (size_t s = 0; s < lst.size(); s++)
         if (lst[s] != TAMCMC_OK && first_err == TAMCMC_OK) first_err = lst[s];
-    const long pl = (long)p;
-    for (int ch = 0; ch < C; ch++) {
-        const double T = Tcoefs ? Tcoefs[ch] : 1.0;
-        auto scaled = [&](double S) {
-            long double f = S;
-            f = -pl * f;
-            return (double)(f / T);
-        };
-        const double L0 = scaled(c->h_S.p[(size_t)ch * E]);
-        logL0[ch] = L0;
-        const double pr0 = with_prior ? lp[(size_t)ch * E] : 0.0;
-        if (logPr0) logPr0[ch] = pr0;
-        for (int k = 0; k < Nvars; k++) {
-            const double x0 = params[(size_t)ch * Np + index_to_relax[k]];
-            volatile double xp = x0 + hstep[k];
-            const double happ = xp - x0;
-            double g = (scaled(c->h_S.p[(size_t)ch * E + k + 1]) - L0) / happ;
-            if (with_prior) {  // same combination as the Lorentzian batches (fd_batch.hip)
-                if (!std::isfinite(g)) g = 0.0;
-                const double prp = lp[(size_t)ch * E + k + 1], prm = lp[B + (size_t)ch * E + k + 1];
-                double gp;
-                if (std::isfinite(prp)) gp = (prp - pr0) / happ;
-                else gp = std::isfinite(prm) ? (pr0 - prm) / happ : 0.0;
-                g += gp;
-                if (grad_prior) grad_prior[(size_t)ch * Nv + k] = gp;
-            }
-            grad[(size_t)ch * Nv + k] = g;
-        }
-    }
+    // same combination as the Lorentzian batches (no status per evaluation: these models have no table that can fail)
+    assemble_gradient(C, Nvars, params, Nparams, index_to_relax, hstep, Tcoefs, p, c->h_S.p, false, with_prior ? lp.data() : nullptr,
+                      lp.data() + B, nullptr, logL0, logPr0, grad, grad_prior);
     return first_err;
 }
 

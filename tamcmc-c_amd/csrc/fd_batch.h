@@ -1,32 +1,31 @@
-// fd_batch.h -- one finite-difference batch (C chains x (Nvars + 1) evaluations) as an object: layout of its device block, launch from
-// parameter vectors already on the device (fd_batch.hip).  Three routes: brute force, windowed delta tables, table-space adjoint.  Used by the host entry points (tamcmc_hip_fd_gradient*) and by the
-// device-resident Langevin step (dev_mala.hip).
+// fd_batch.h -- one gradient batch (C chains x (Nvars + 1) evaluations) as an object: the route it takes (fd_route.h), the layout of its
+// device block, its workspace, and its launch from parameter vectors already on the device (fd_batch.hip).  Used by the host entry points
+// (tamcmc_hip_fd_gradient*, tamcmc_hip_adjoint_table, tamcmc_hip_fisher) and by the device-resident Langevin step (dev_sampler.hip: run_mala).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "ctx.h"
 #include "fd_rgb_chunk.h"
+#include "fd_route.h"
 
 namespace tamcmc {
 
 struct FdBatch {
+    using Route = FdRoute;
+    using Request = FdRequest;
     int model_id = 0, prior_class = 0, C = 0, E = 0, B = 0, Nvars = 0, per = 0, stride = 1, ntiles = 0;
     int64_t Np = 0;
-    bool windowed = false;
-    // TAMCMC_OPT_GRADIENT = TAMCMC_GRADIENT_ADJOINT: no perturbed likelihood at all.  The C base points are evaluated as in the windowed
-    // route (same launch, same planes), the table-space adjoint G / Gn of each is taken in one pass over its windows (adjoint.h), and the
-    // "difference" of evaluation e is the contraction of G / Gn with (table e - base table), written where the DELTA launch writes its
-    // difference -- so the sums read like the windowed route's (deltas()).  `windowed` is then false: no delta tables exist.
-    bool adjoint = false;
-    bool deltas() const { return windowed || adjoint; }  // S = C base sums, then B differences against them
-    // Fisher rows (fisher.h; set BEFORE layout(), off by default): neither windowed nor adjoint whatever the context's options say; enqueue()
-    // stops after the tables -- every perturbed table gets its base table's windows [i0, i1) ("frozen window", k_fisher_freeze) -- and ONE
-    // likelihood launch that leaves the B model rows in `model` ([B x Nx]; the sums S are not formed).  The caller passes 2 Nvars "variables":
-    // idx = [index_to_relax, index_to_relax], h = [+h, -h], so with N the caller's variables (this batch's Nvars / 2) slot c*E + 1 + k is theta + h_k e_k and slot c*E + 1 + N + k is theta - h_k e_k.
-    bool rows_only = false;
-    size_t model_doubles = 0;  // doubles of `model` that enqueue() needs (0: none)
-    size_t bg_rows = 0;        // rows of `bgbuf` (x ntiles x 8 doubles) under FAST arithmetic
+    Route route = Route::Brute;
+    bool deltas() const { return route == Route::Windowed || route == Route::Adjoint; }  // S = C base sums, then B differences against them
+    // Route::Rows: the caller passes 2 N "variables" for its N, idx = [index_to_relax, index_to_relax], h = [+h, -h]: slot c*E + 1 + k is
+    // theta + h_k e_k, slot c*E + 1 + N + k is theta - h_k e_k.
+    // What enqueue() needs beside the block, in doubles.  part: tile partials; S: the sums; model: the base points' planes 1/M0, y/M0, M0
+    // (Adjoint), + tile moments in two layouts + done flags (Windowed), the B model rows (Rows); bg: background series, FAST arithmetic only
+    struct Workspace { size_t part = 0, S = 0, model = 0, bg = 0; } ws;
+    struct Buffers { DevBuf<double> &part, &S, &model, &bg; };  // the context's d_part, d_S, d_model, d_bg, or a sampler's own
+    hipError_t reserve(const tamcmc_hip_ctx *c, const Buffers &w) const;  // (model only when needed, bg only under TAMCMC_PRECISION_FAST)
+    int table_slots() const { return (route == Route::Windowed && !rgb) ? 2 * B : B; }  // Windowed: slots [B, 2B) = per-block copies of the base table (not for red giants)
     bool rgb = false;  // red-giant models (ids 25 / 27): tables through the device pre-step, `chunk` vectors at a time
     int chunk = 0;
     // red giants: the host's long-double scalar unpack of the B vectors (rgb::Prep[B], rgb::RowIn[B], the table block's header with counts
@@ -40,16 +39,32 @@ struct FdBatch {
     size_t o_tab = 0, o_dtab = 0, o_btab = 0, o_drange = 0, o_dflags = 0, o_drow = 0, o_dnold = 0, total_bytes = 0;
     size_t o_adjG = 0, o_adjGn = 0, o_adjpart = 0, o_adjGpart = 0;  // adjoint workspace inside the block: G [C x per x 17], Gn [C x stride], noise tile partials, row segment partials
     int adj_ntn = 0, adj_nseg = 0;
-    size_t nS = 0;  // sums the batch produces: C base sums + B differences (deltas()) or B full sums
-    int layout(tamcmc_hip_ctx *c, int model_id, int prior_class, int C, int64_t Nparams, const int32_t *plength, int Nvars);
-    int enqueue(tamcmc_hip_ctx *c, unsigned char *block, const double *d_params, double *part, double *S, double *model, double *bgbuf,
-                hipEvent_t ev0, hipEvent_t ev1);
-    // [B x ntiles] flags of the last enqueue (device memory, inside `model`): 1 = that (evaluation, tile) was a far-only tile taken from
-    // the base point's moments -- no bin of it was read; nullptr: no such pass (roofline bookkeeping: bins_not_walked)
+    int layout(tamcmc_hip_ctx *c, Request request, int model_id, int prior_class, int C, int64_t Nparams, const int32_t *plength, int Nvars);
+    // block: the batch's device block (total_bytes), constants in place; d_params: C x Np parameter vectors on the device (nullptr: the
+    // block's own params area); w: reserve()d.  ev0 / ev1 (optional) bracket the likelihood launches
+    int enqueue(tamcmc_hip_ctx *c, unsigned char *block, const double *d_params, const Buffers &w, hipEvent_t ev0, hipEvent_t ev1);
+    // Windowed, after the batch has finished (synchronous copies; roofline bookkeeping): bins the DELTA launch really walked -- the affected
+    // ranges less the far-only tiles taken from the base point's moments -- and (full != nullptr) its "full table" evaluations
+    hipError_t delta_stats(const unsigned char *block, long *bins, long *full) const;
+    // [B x ntiles] flags of the last enqueue (device memory, inside `model`): 1 = that (evaluation, tile) was a far-only tile; nullptr: no such pass
     const unsigned char *d_done = nullptr;
     int tile_bins_ = 0;
-    long bins_not_walked() const;  // (synchronous copy; call after the batch has finished)
 };
 int fd_ensure_poly(tamcmc_hip_ctx *c);  // Pslm/Qlm tables in c->d_poly
+
+// The argument checks the gradient entries share, after the context and the model: spectrum, counts, pointers, layout, variables.
+// rest_ok: the entry's own pointers (outputs, priors) are there.  GA_PLENGTH: plength required, and its sum must be Nparams.  GA_VARS:
+// index_to_relax (in range) and hstep required.  GA_FISHER: 1 <= Nvars <= 16384 and no zero step.  GA_EMPTY_FIRST: an empty batch
+// (C == 0) is accepted before plength and the variables are looked at.
+enum : unsigned { GA_PLENGTH = 1, GA_VARS = 2, GA_FISHER = 4, GA_EMPTY_FIRST = 8 };
+int check_gradient_args(const tamcmc_hip_ctx *c, int C, const double *params, int64_t Nparams, const int32_t *plength,
+                        const int32_t *index_to_relax, int Nvars, const double *hstep, bool rest_ok, unsigned rules);
+
+// Sums and log-priors of a finished batch -> logL0, logPr0, grad, grad_prior (host; the device's counterpart is mala_gradient,
+// dev_mala_impl.h).  S: B full sums, or (deltas) C base sums then B differences; lpp / lpm: log-priors at the forward / backward points by
+// slot (nullptr: no prior, logPr0 = 0); status by slot (nullptr: no evaluation can fail).  Returns the first status that is not TAMCMC_OK.
+int assemble_gradient(int C, int Nvars, const double *params, int64_t Nparams, const int32_t *index_to_relax, const double *hstep,
+                      const double *Tcoefs, double p, const double *S, bool deltas, const double *lpp, const double *lpm, const int *status,
+                      double *logL0, double *logPr0, double *grad, double *grad_prior);
 
 }  // namespace tamcmc

@@ -1,18 +1,21 @@
-// fd_batch.hip -- finite-difference gradient batches built ON the device.
+// fd_batch.hip -- gradient batches built ON the device.
 //
 // The forward-difference gradient (the drift the reference leaves as a stub, MALA.cpp:321-337) needs, per chain,
 // Nvars+1 evaluations.  Building those tables on the host costs far more than evaluating them (C3: 1880 tables,
 // ~20 us each, against ~4 ms of likelihood kernel); here one workgroup per (chain, perturbed variable) perturbs the
 // parameter vector, evaluates the log-prior (and the prior at the backward point, for the one-sided fallback at the
-// edge of a prior's support) and writes its multiplet table straight into the likelihood kernel's input block:
-//   k_fd_unpack (C*(Nvars+1) workgroups) -> k_loglike (one launch, B = C*(Nvars+1)) -> k_finalize,
-// or, windowed (FAST arithmetic: the default):
-//   k_fd_unpack (tables) -> k_fd_compare (delta tables) -> k_loglike on the C base points (planes 1/M0, y/M0, M0 kept) -> k_fd_moments (tile
-//   moments of the base points) -> k_fd_far (far-only tiles of the light evaluations from the moments) -> k_loglike<DELTA> (everything else)
-//   -> k_finalize.
-// or, adjoint (TAMCMC_OPT_GRADIENT = TAMCMC_GRADIENT_ADJOINT; FAST arithmetic, fixed-length tables):
-//   k_fd_unpack (tables) -> k_adj_base -> k_loglike on the C base points (planes kept) -> k_finalize -> k_adj_rows, k_adj_noise, k_adj_fold
-//   (adjoint.hip: dS/d(table entry) of each base point) -> k_adj_contract (dS of every perturbed table to first order, frozen windows).
+// edge of a prior's support) and writes its multiplet table straight into the likelihood kernel's input block.
+// A batch is: the tables (build_tables), then what its route (FdBatch::Route, fd_route.h) does with them; every route begins with the
+// same launch on some of the tables (evaluate_tables):
+//   Brute     k_fd_unpack -> k_loglike on all B = C*(Nvars+1) tables -> k_finalize;
+//   Windowed  (FAST arithmetic: the default) k_fd_unpack -> k_fd_compare (delta tables) -> k_loglike on the C base points (planes 1/M0,
+//             y/M0, M0 kept) -> k_finalize -> k_fd_moments (tile moments of the base points) -> k_fd_far (far-only tiles of the light
+//             evaluations from the moments) -> k_loglike<DELTA> (everything else) -> k_finalize;
+//   Adjoint   (TAMCMC_OPT_GRADIENT = TAMCMC_GRADIENT_ADJOINT; FAST arithmetic, fixed-length tables) k_fd_unpack -> k_adj_base -> k_loglike
+//             on the C base points (planes kept) -> k_finalize -> k_adj_rows, k_adj_noise, k_adj_fold (adjoint.hip: dS/d(table entry) of
+//             each base point) -> k_adj_contract (dS of every perturbed table to first order, frozen windows);
+//   Rows      (tamcmc_hip_fisher) k_fd_unpack -> k_fisher_freeze (every perturbed table gets its base table's windows) -> k_loglike on
+//             all B tables, model rows kept, no sums.
 // Red-giant models (ids 25 / 27): the table of a vector needs the mixed-mode solver, so k_fd_unpack's place is taken by
 //   k_fd_rgb_perturb (perturbed vector, class-4 log-prior, scalar unpack into the pre-step workspace) -> rgb_device_stage (solver, rows),
 // in chunks of vectors through ONE workspace slice; everything after the tables is the same.
@@ -339,24 +342,20 @@ __global__ void __launch_bounds__(64) k_adj_base(const FdArgs a) {
 using namespace tamcmc;
 
 // ---------------------------------------------------------------------------------------------------------------
-// One finite-difference batch = C chains x (Nvars + 1) evaluations.  fd_layout() places its constants, tables and results in ONE
-// device block; fd_enqueue() launches the batch on the context's stream from parameter vectors that are ALREADY on the device and
-// leaves the results there (the device-resident Langevin step, dev_mala.hip, consumes them in its next kernel); fd_run() is the host
-// entry: upload, enqueue, download, gradient assembly.
+// One gradient batch = C chains x (Nvars + 1) evaluations.  layout() chooses the route and places the batch's constants, tables and
+// results in ONE device block; enqueue() launches the batch on the context's stream from parameter vectors that are ALREADY on the device
+// and leaves the results there (the device-resident Langevin step, run_mala in dev_sampler.hip, consumes them in its next kernel);
+// fd_run() is the host entry: upload, enqueue, download, gradient assembly.
 namespace tamcmc {
 
 static size_t al16(size_t v) { return (v + 15) & ~(size_t)15; }
+static bool is_rgb_model(int id) { return id == TAMCMC_MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4_ID || id == TAMCMC_MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4_ID; }
 
-int FdBatch::layout(tamcmc_hip_ctx *c, int model_id_, int prior_class_, int C_, int64_t Nparams, const int32_t *plength, int Nvars_) {
+int FdBatch::layout(tamcmc_hip_ctx *c, Request request, int model_id_, int prior_class_, int C_, int64_t Nparams, const int32_t *plength, int Nvars_) {
     model_id = model_id_; prior_class = prior_class_; C = C_; Np = Nparams; Nvars = Nvars_;
-    rgb = (model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4_ID || model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4_ID);
+    rgb = is_rgb_model(model_id);
     E = Nvars + 1; B = C * E;
-    adjoint = !rows_only && c->gradient == TAMCMC_GRADIENT_ADJOINT;
-    if (rows_only && (rgb || c->precision == TAMCMC_PRECISION_STRICT)) return TAMCMC_ERR_BAD_ARG;  // (tamcmc_hip_fisher refuses both before it gets here)
-    if (adjoint) {
-        if (rgb) return TAMCMC_ERR_BAD_MODEL;  // (tables of variable length: no row-by-row contraction)
-        if (c->precision == TAMCMC_PRECISION_STRICT) return TAMCMC_ERR_BAD_ARG;  // (the planes are the FAST base launch's)
-    }
+    if (int rc = fd_route(request, c->gradient, c->fd_windowed, c->precision, delta_geometry(c->wgs, c->K), Nvars, rgb, &route)) return rc;
     if (rgb) {
         // red giants: the tables come from the device pre-step, whose workspace is ~28 KB per vector (Prep, RowIn, three arrays of
         // rgb::MAXSOL doubles).  Chunk rule: the batch goes through ONE workspace slice of at most FD_RGB_WORKSPACE bytes, in chunks of
@@ -386,14 +385,11 @@ int FdBatch::layout(tamcmc_hip_ctx *c, int model_id_, int prior_class_, int C_, 
     o_lpm = o; o = al16(o + (size_t)B * 8);
     o_st = o; o = al16(o + (size_t)B * 4);
     out_bytes = o - in_bytes;
-    // windowed finite differences (FAST modes): only the multiplets a perturbation changes are re-evaluated, on their
-    // windows, against the stored base model row ("the main algorithmic lever")
-    windowed = !adjoint && !rows_only && c->fd_windowed && c->precision != TAMCMC_PRECISION_STRICT && delta_geometry(c->wgs, c->K) && Nvars > 0;
-    const int nslots = (windowed && !rgb) ? 2 * B : B;         // windowed: slots [B, 2B) = per-block copies of the base table (not for red giants)
+    const int nslots = table_slots();
     const StageLayout L(nslots, stride, (size_t)nslots * per);
     o_tab = o; o = al16(o + L.bytes);
     o_dtab = o_btab = o_drange = o_dflags = o_drow = o_dnold = 0;
-    if (windowed) {
+    if (route == Route::Windowed) {
         const StageLayout LD(B, stride, (size_t)B * 2 * per);      // delta launch input block
         const StageLayout LB(C, stride, 0);                        // base launch: ranges / counts / noise rows by chain
         o_dtab = o; o = al16(o + LD.bytes);
@@ -405,7 +401,7 @@ int FdBatch::layout(tamcmc_hip_ctx *c, int model_id_, int prior_class_, int C_, 
     }
     o_adjG = o_adjGn = o_adjpart = o_adjGpart = 0;
     adj_ntn = adj_nseg = 0;
-    if (adjoint) {
+    if (route == Route::Adjoint) {
         const StageLayout LB(C, stride, 0);
         adj_ntn = (int)((c->Nx + ADJ_NTILE - 1) / ADJ_NTILE);
         o_btab = o; o = al16(o + LB.bytes);
@@ -418,35 +414,107 @@ int FdBatch::layout(tamcmc_hip_ctx *c, int model_id_, int prior_class_, int C_, 
     total_bytes = o;
     const int tbins = tile_bins(c->wgs, c->K);
     ntiles = (int)((c->Nx + tbins - 1) / tbins);
-    nS = deltas() ? (size_t)C + B : (size_t)B;
-    // `model`: three planes of the base points (1/M0, y/M0, M0); windowed: + tile moments (two layouts) + done flags
-    model_doubles = 0;
-    if (adjoint) model_doubles = 3 * (size_t)C * c->Nx;
-    if (windowed) model_doubles = 3 * (size_t)C * c->Nx + 2 * (size_t)C * ntiles * FD_MOM + ((size_t)B * ntiles + 7) / 8;
-    if (rows_only) model_doubles = (size_t)B * c->Nx;
-    bg_rows = deltas() ? (size_t)C : (size_t)B;
+    const size_t planes = 3 * (size_t)C * c->Nx;
+    ws.S = deltas() ? (size_t)C + B : (size_t)B;
+    ws.part = ws.S * ntiles * 2;
+    ws.model = 0;
+    if (route == Route::Adjoint) ws.model = planes;
+    if (route == Route::Windowed) ws.model = planes + 2 * (size_t)C * ntiles * FD_MOM + ((size_t)B * ntiles + 7) / 8;
+    if (route == Route::Rows) ws.model = (size_t)B * c->Nx;
+    ws.bg = (deltas() ? (size_t)C : (size_t)B) * ntiles * 8;
     return TAMCMC_OK;
 }
 
-// db = the batch's device block (total_bytes), constants in place; d_params: C x Np parameter vectors on the device (nullptr: the
-// block's own params area); part / S / model: scratch sized nS*ntiles*2, nS, 3*C*Nx + 2*C*ntiles*FD_MOM + ceil(B*ntiles/8) (model only when windowed); bgbuf: C or B x ntiles x 8.
-int FdBatch::enqueue(tamcmc_hip_ctx *c, unsigned char *db, const double *d_params, double *part, double *S, double *model, double *bgbuf,
-                     hipEvent_t ev0, hipEvent_t ev1) {
+hipError_t FdBatch::reserve(const tamcmc_hip_ctx *c, const Buffers &w) const {
+    hipError_t e = w.part.reserve(ws.part);
+    if (e == hipSuccess) e = w.S.reserve(ws.S);
+    if (e == hipSuccess && ws.model) e = w.model.reserve(ws.model);
+    if (e == hipSuccess && c->precision == TAMCMC_PRECISION_FAST) e = w.bg.reserve(ws.bg);
+    return e;
+}
+
+namespace {
+
+TablePtrs table_ptrs(unsigned char *base, const StageLayout &Lx) {
+    TablePtrs T;
+    T.mults = (tamcmc_multiplet *)(base + Lx.off_mults); T.pairs = (int *)(base + Lx.off_pairs);
+    T.nh = (int *)(base + Lx.off_nh); T.nn = (int *)(base + Lx.off_nn); T.noise = (double *)(base + Lx.off_noise);
+    return T;
+}
+
+// The tables of the B vectors in fa.T (red giants: chunk by chunk through the pre-step, with the host's unpack uploaded where there is
+// one), then what the route reads beside them: the delta tables (Windowed), the base launch's ranges / counts / noise rows by chain
+// (Windowed, Adjoint).
+int build_tables(tamcmc_hip_ctx *c, const FdBatch &b, unsigned char *db, const StageLayout &L, FdArgs &fa) {
     hipStream_t st = c->stream;
-    auto table_ptrs = [](unsigned char *base, const StageLayout &Lx) {
-        TablePtrs T;
-        T.mults = (tamcmc_multiplet *)(base + Lx.off_mults); T.pairs = (int *)(base + Lx.off_pairs);
-        T.nh = (int *)(base + Lx.off_nh); T.nn = (int *)(base + Lx.off_nn); T.noise = (double *)(base + Lx.off_noise);
-        return T;
-    };
-    const int nslots = (windowed && !rgb) ? 2 * B : B;
-    const StageLayout L(nslots, stride, (size_t)nslots * per), LD(B, stride, (size_t)B * 2 * per), LB(C, stride, 0);
+    if (b.rgb) {
+        RgbDeviceTables R;
+        R.mults = fa.T.mults; R.pairs = fa.T.pairs; R.nh = fa.T.nh; R.nn = fa.T.nn; R.noise = fa.T.noise; R.status = fa.status; R.stride = b.stride;
+        const rgb::Slice rs = rgb_device_slice(c, b.chunk, 0);
+        if (b.h_prep)  // counts and noise rows of the host unpack: the table block's header
+            HIPCHK(c, hipMemcpyAsync(db + b.o_tab, b.h_header, L.off_mults, hipMemcpyHostToDevice, st));
+        for (int b0 = 0; b0 < b.B; b0 += b.chunk) {  // (one stream: a chunk's solver and row kernels are done with the slice before the next chunk's unpack)
+            const int n = b.B - b0 < b.chunk ? b.B - b0 : b.chunk;
+            if (b.h_prep) {
+                HIPCHK(c, hipMemcpyAsync(rs.preps, (const rgb::Prep *)b.h_prep + b0, (size_t)n * sizeof(rgb::Prep), hipMemcpyHostToDevice, st));
+                HIPCHK(c, hipMemcpyAsync(rs.rows, (const rgb::RowIn *)b.h_rows + b0, (size_t)n * sizeof(rgb::RowIn), hipMemcpyHostToDevice, st));
+            }
+            hipLaunchKernelGGL(k_fd_rgb_perturb, dim3(n), dim3(FB), (size_t)b.Np * 16, st, fa, rs, b0, b.h_prep ? 1 : 0);
+            HIPCHK(c, hipGetLastError());
+            const int rc = rgb_device_stage(c, b0, n, b.chunk, 0, b.per, R, st);
+            if (rc) return rc;
+        }
+    } else {
+        const size_t lds = (size_t)b.Np * 8 + unpack_lds_bytes() + 32;
+        hipLaunchKernelGGL(k_fd_unpack, dim3(b.B), dim3(FB), lds, st, fa);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (b.route == FdRoute::Windowed) {
+        hipLaunchKernelGGL(k_fd_compare, dim3(b.B), dim3(FB), 0, st, fa);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (b.route == FdRoute::Adjoint) {
+        fa.Bs = table_ptrs(db + b.o_btab, StageLayout(b.C, b.stride, 0));
+        hipLaunchKernelGGL(k_adj_base, dim3(b.C), dim3(64), 0, st, fa);
+        HIPCHK(c, hipGetLastError());
+    }
+    return TAMCMC_OK;
+}
+
+// Evaluate n tables -- every route's first likelihood launch.  The multiplets are fa.T's; ranges, counts and noise rows come from `ix`:
+// fa.T (n = B, by slot) or fa.Bs (n = C, by chain).  keep: what stays in w.model -- nothing, the n model rows, or the three planes 1/M0,
+// y/M0, M0 of the n points.  sums: the tile partials are folded into w.S[0, n).  `a` is left as launched (Windowed goes on from it).
+enum class Keep { Nothing, Rows, Planes };
+int evaluate_tables(tamcmc_hip_ctx *c, const FdArgs &fa, const TablePtrs &ix, int n, Keep keep, bool sums,
+                    const FdBatch::Buffers &w, LoglikeArgs &a) {
+    hipStream_t st = c->stream;
+    a.B = n;
+    a.mults = fa.T.mults; a.offsets = ix.pairs; a.noise = ix.noise; a.nharvey = ix.nh; a.nnoise = ix.nn;
+    a.partials = w.part.p;
+    if (keep != Keep::Nothing) a.model = w.model.p;
+    if (keep == Keep::Planes) { a.fd_rows = w.model.p; a.fd_plane = (size_t)n * a.Nx; }  // (the planes instead of the rows)
+    if (c->precision == TAMCMC_PRECISION_FAST) {
+        HIPCHK(c, launch_bg_poly(a, c->wgs, c->K, w.bg.p, st));
+        a.bg_poly = w.bg.p;
+    }
+    HIPCHK(c, launch_loglike(a, c->precision, c->wgs, c->K, keep != Keep::Nothing, st));
+    if (sums) HIPCHK(c, launch_finalize(w.part.p, n, a.ntiles, w.S.p, st));
+    return TAMCMC_OK;
+}
+
+}  // namespace
+
+int FdBatch::enqueue(tamcmc_hip_ctx *c, unsigned char *db, const double *d_params, const Buffers &w, hipEvent_t ev0, hipEvent_t ev1) {
+    hipStream_t st = c->stream;
+    const bool windowed = route == Route::Windowed;
+    double *const part = w.part.p, *const S = w.S.p, *const model = w.model.p, *const bgbuf = w.bg.p;
     FdArgs fa;
     fa.desc.model_id = model_id; fa.desc.prior_class = prior_class; fa.desc.Np = (int)Np; fa.desc.per = per;
     fa.desc.stride = stride; fa.desc.Nx = (int)c->Nx;
     fa.desc.x_first = c->hx[0]; fa.desc.x_last = c->hx[(size_t)c->Nx - 1]; fa.desc.step = c->hx[1] - c->hx[0];
     fa.desc.plength = (const int *)(db + o_pl); fa.desc.priors_switch = (const int *)(db + o_sw);
     fa.desc.priors = (const double *)(db + o_pr); fa.desc.extra = (const double *)(db + o_ex); fa.desc.poly = c->d_poly.p;
+    const StageLayout L(table_slots(), stride, (size_t)table_slots() * per);
     fa.T = table_ptrs(db + o_tab, L);
     fa.C = C; fa.E = E; fa.Nv = Nvars;
     fa.params = d_params ? d_params : (const double *)(db + o_params);
@@ -458,42 +526,13 @@ int FdBatch::enqueue(tamcmc_hip_ctx *c, unsigned char *db, const double *d_param
     fa.D = fa.T; fa.Bs = fa.T;
     fa.d_range = nullptr; fa.d_flags = nullptr; fa.d_row = nullptr; fa.d_noise_old = nullptr;
     if (windowed) {
-        fa.D = table_ptrs(db + o_dtab, LD);
-        fa.Bs = table_ptrs(db + o_btab, LB);
+        fa.D = table_ptrs(db + o_dtab, StageLayout(B, stride, (size_t)B * 2 * per));
+        fa.Bs = table_ptrs(db + o_btab, StageLayout(C, stride, 0));
         fa.d_range = (int *)(db + o_drange); fa.d_flags = (int *)(db + o_dflags); fa.d_row = (int *)(db + o_drow);
         fa.d_noise_old = (double *)(db + o_dnold);
     }
     if (rgb && c->precision == TAMCMC_PRECISION_STRICT && !h_prep) return TAMCMC_ERR_BAD_ARG;  // (fd_batch.h: STRICT needs the host unpack)
-    if (rgb) {
-        RgbDeviceTables R;
-        R.mults = fa.T.mults; R.pairs = fa.T.pairs; R.nh = fa.T.nh; R.nn = fa.T.nn; R.noise = fa.T.noise; R.status = fa.status; R.stride = stride;
-        const rgb::Slice rs = rgb_device_slice(c, chunk, 0);
-        if (h_prep) HIPCHK(c, hipMemcpyAsync(db + o_tab, h_header, L.off_mults, hipMemcpyHostToDevice, st));  // counts and noise rows of the host unpack
-        for (int b0 = 0; b0 < B; b0 += chunk) {  // (one stream: a chunk's solver and row kernels are done with the slice before the next chunk's unpack)
-            const int n = B - b0 < chunk ? B - b0 : chunk;
-            if (h_prep) {
-                HIPCHK(c, hipMemcpyAsync(rs.preps, (const rgb::Prep *)h_prep + b0, (size_t)n * sizeof(rgb::Prep), hipMemcpyHostToDevice, st));
-                HIPCHK(c, hipMemcpyAsync(rs.rows, (const rgb::RowIn *)h_rows + b0, (size_t)n * sizeof(rgb::RowIn), hipMemcpyHostToDevice, st));
-            }
-            hipLaunchKernelGGL(k_fd_rgb_perturb, dim3(n), dim3(FB), (size_t)Np * 16, st, fa, rs, b0, h_prep ? 1 : 0);
-            HIPCHK(c, hipGetLastError());
-            const int rc = rgb_device_stage(c, b0, n, chunk, 0, per, R, st);
-            if (rc) return rc;
-        }
-    } else {
-        const size_t lds = (size_t)Np * 8 + unpack_lds_bytes() + 32;
-        hipLaunchKernelGGL(k_fd_unpack, dim3(B), dim3(FB), lds, st, fa);
-        HIPCHK(c, hipGetLastError());
-    }
-    if (windowed) {
-        hipLaunchKernelGGL(k_fd_compare, dim3(B), dim3(FB), 0, st, fa);
-        HIPCHK(c, hipGetLastError());
-    }
-    if (adjoint) {
-        fa.Bs = table_ptrs(db + o_btab, LB);
-        hipLaunchKernelGGL(k_adj_base, dim3(C), dim3(64), 0, st, fa);
-        HIPCHK(c, hipGetLastError());
-    }
+    if (int rc = build_tables(c, *this, db, L, fa)) return rc;
 
     const int Nx = (int)c->Nx;
     LoglikeArgs a;
@@ -501,29 +540,18 @@ int FdBatch::enqueue(tamcmc_hip_ctx *c, unsigned char *db, const double *d_param
     a.x0 = c->hx[0]; a.step = c->hx[1] - c->hx[0];
     a.noise_stride = stride; a.model = nullptr;
     if (ev0) HIPCHK(c, hipEventRecord(ev0, st));
-    if (rows_only) {
-        // Fisher rows: frozen windows, then the B model rows (no sums are read: the partials are the launch's scratch)
+    d_done = nullptr;
+    switch (route) {
+    case Route::Brute:
+        if (int rc = evaluate_tables(c, fa, fa.T, B, Keep::Nothing, true, w, a)) return rc;
+        break;
+    case Route::Rows:  // frozen windows, then the B model rows (no sums are read: the partials are the launch's scratch)
         HIPCHK(c, launch_fisher_freeze(fa.T.mults, fa.T.pairs, fa.status, per, C, E, st));
-        a.B = B;
-        a.mults = fa.T.mults; a.offsets = fa.T.pairs; a.noise = fa.T.noise; a.nharvey = fa.T.nh; a.nnoise = fa.T.nn;
-        a.partials = part; a.model = model;
-        if (c->precision == TAMCMC_PRECISION_FAST) {
-            HIPCHK(c, launch_bg_poly(a, c->wgs, c->K, bgbuf, st));
-            a.bg_poly = bgbuf;
-        }
-        HIPCHK(c, launch_loglike(a, c->precision, c->wgs, c->K, true, st));
-        d_done = nullptr;
-    } else if (adjoint) {
-        // (1) the C base points, exactly the windowed route's base launch: planes 1/M0, y/M0 (and M0) kept
-        a.B = C;
-        a.mults = fa.T.mults; a.offsets = fa.Bs.pairs; a.noise = fa.Bs.noise; a.nharvey = fa.Bs.nh; a.nnoise = fa.Bs.nn;
-        a.partials = part; a.model = model; a.fd_rows = model; a.fd_plane = (size_t)C * Nx;
-        if (c->precision == TAMCMC_PRECISION_FAST) {
-            HIPCHK(c, launch_bg_poly(a, c->wgs, c->K, bgbuf, st));
-            a.bg_poly = bgbuf;
-        }
-        HIPCHK(c, launch_loglike(a, c->precision, c->wgs, c->K, true, st));
-        HIPCHK(c, launch_finalize(part, C, ntiles, S, st));
+        if (int rc = evaluate_tables(c, fa, fa.T, B, Keep::Rows, false, w, a)) return rc;
+        break;
+    case Route::Adjoint: {
+        // (1) the C base points, exactly the windowed route's base launch
+        if (int rc = evaluate_tables(c, fa, fa.Bs, C, Keep::Planes, true, w, a)) return rc;
         // (2) dS/d(table entry) of each base point, (3) contracted with every perturbed table's difference from it
         AdjArgs g;
         g.x = c->dx.p; g.logx = c->dlogx.p; g.Nx = Nx;
@@ -534,28 +562,11 @@ int FdBatch::enqueue(tamcmc_hip_ctx *c, unsigned char *db, const double *d_param
         g.Gpart = (double *)(db + o_adjGpart); g.nseg = adj_nseg;
         HIPCHK(c, launch_adjoint(g, st));
         HIPCHK(c, launch_adjoint_contract(g, S + C, st));
-        d_done = nullptr;
-    } else if (!windowed) {
-        a.B = B;
-        a.mults = fa.T.mults; a.offsets = fa.T.pairs; a.noise = fa.T.noise; a.nharvey = fa.T.nh; a.nnoise = fa.T.nn;
-        a.partials = part;
-        if (c->precision == TAMCMC_PRECISION_FAST) {
-            HIPCHK(c, launch_bg_poly(a, c->wgs, c->K, bgbuf, st));
-            a.bg_poly = bgbuf;
-        }
-        HIPCHK(c, launch_loglike(a, c->precision, c->wgs, c->K, false, st));
-        HIPCHK(c, launch_finalize(part, B, ntiles, S, st));
-    } else {
-        // (1) the C base points: full evaluation, model rows kept
-        a.B = C;
-        a.mults = fa.T.mults; a.offsets = fa.Bs.pairs; a.noise = fa.Bs.noise; a.nharvey = fa.Bs.nh; a.nnoise = fa.Bs.nn;
-        a.partials = part; a.model = model; a.fd_rows = model; a.fd_plane = (size_t)C * Nx;  // (1/M0, y/M0 and M0 planes instead of the rows)
-        if (c->precision == TAMCMC_PRECISION_FAST) {
-            HIPCHK(c, launch_bg_poly(a, c->wgs, c->K, bgbuf, st));
-            a.bg_poly = bgbuf;
-        }
-        HIPCHK(c, launch_loglike(a, c->precision, c->wgs, c->K, true, st));
-        HIPCHK(c, launch_finalize(part, C, ntiles, S, st));
+        break;
+    }
+    case Route::Windowed: {
+        // (1) the C base points: full evaluation, planes kept
+        if (int rc = evaluate_tables(c, fa, fa.Bs, C, Keep::Planes, true, w, a)) return rc;
         // (1b) moments of the base points per tile, behind the three planes: the delta launch's far-only tiles take their sums from them
         double *mom = (c->precision == TAMCMC_PRECISION_FAST && c->wgs == 64) ? model + 3 * (size_t)C * Nx : nullptr;
         double *momT = mom ? mom + (size_t)C * ntiles * FD_MOM : nullptr;
@@ -578,18 +589,27 @@ int FdBatch::enqueue(tamcmc_hip_ctx *c, unsigned char *db, const double *d_param
         tile_bins_ = tile_bins(c->wgs, c->K);
         HIPCHK(c, launch_loglike_delta(d, c->precision, c->wgs, c->K, st));
         HIPCHK(c, launch_finalize(d.partials, B, ntiles, S + C, st));
+        break;
+    }
     }
     if (ev1) HIPCHK(c, hipEventRecord(ev1, st));
     return TAMCMC_OK;
 }
 
-long FdBatch::bins_not_walked() const {
-    if (!d_done) return 0;
-    std::vector<unsigned char> f((size_t)B * ntiles);
-    if (hipMemcpy(f.data(), d_done, f.size(), hipMemcpyDeviceToHost) != hipSuccess) return 0;
-    long n = 0;
-    for (unsigned char v : f) n += v ? 1 : 0;
-    return n * (long)tile_bins_;
+hipError_t FdBatch::delta_stats(const unsigned char *db, long *bins, long *full) const {
+    std::vector<int> v((size_t)2 * B);
+    std::vector<unsigned char> done(d_done ? (size_t)B * ntiles : 0);
+    hipError_t e = hipMemcpy(v.data(), db + o_drange, v.size() * sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && d_done) e = hipMemcpy(done.data(), d_done, done.size(), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return e;
+    *bins = 0;
+    for (int s = 0; s < B; s++) *bins += v[2 * (size_t)s + 1] - v[2 * (size_t)s];
+    for (unsigned char t : done) *bins -= t ? (long)tile_bins_ : 0;  // (far-only tiles taken from the base point's moments: no bin of them was read)
+    if (!full) return hipSuccess;
+    e = hipMemcpy(v.data(), db + o_dflags, (size_t)B * sizeof(int), hipMemcpyDeviceToHost);
+    *full = 0;
+    for (int s = 0; s < B && e == hipSuccess; s++) *full += (v[(size_t)s] & 2) ? 1 : 0;
+    return e;
 }
 
 int fd_ensure_poly(tamcmc_hip_ctx *c) {
@@ -602,137 +622,57 @@ int fd_ensure_poly(tamcmc_hip_ctx *c) {
     return TAMCMC_OK;
 }
 
-}  // namespace tamcmc
-
-static int fd_run(tamcmc_hip_ctx *c, int model_id, int prior_class, int C, const double *params, int64_t Nparams,
-                  const int32_t *plength, const int32_t *index_to_relax, int Nvars, const double *hstep, const double *Tcoefs,
-                  double p, const double *priors, const int32_t *priors_switch, const double *extra_priors, double *logL0,
-                  double *logPr0, double *grad, double *grad_prior) {
-    if (!c) return TAMCMC_ERR_BAD_ARG;
+int check_gradient_args(const tamcmc_hip_ctx *c, int C, const double *params, int64_t Nparams, const int32_t *plength,
+                        const int32_t *index_to_relax, int Nvars, const double *hstep, bool rest_ok, unsigned rules) {
+    const bool need_pl = rules & GA_PLENGTH, vars = rules & GA_VARS, fisher = rules & GA_FISHER;
     if (c->Nx <= 0) return TAMCMC_ERR_NO_SPECTRUM;
-    if (C < 0 || Nvars < 0 || !params || !plength || !index_to_relax || !hstep || !logL0 || !grad || Nparams < 1) return TAMCMC_ERR_BAD_ARG;
-    if (prior_class != 0 && (!priors || !priors_switch || !extra_priors)) return TAMCMC_ERR_BAD_ARG;
-    if (C == 0) return TAMCMC_OK;
+    if (C < 0 || !params || Nparams < 1 || !rest_ok || (need_pl && !plength)) return TAMCMC_ERR_BAD_ARG;
+    if (vars && (Nvars < (fisher ? 1 : 0) || (fisher && Nvars > 16384) || !index_to_relax || !hstep)) return TAMCMC_ERR_BAD_ARG;
+    if (C == 0 && (rules & GA_EMPTY_FIRST)) return TAMCMC_OK;
     long psum = 0;
-    for (int i = 0; i < 11; i++) psum += plength[i];
-    if (psum != Nparams) return TAMCMC_ERR_BAD_ARG;
-    for (int k = 0; k < Nvars; k++)
-        if (index_to_relax[k] < 0 || index_to_relax[k] >= Nparams) return TAMCMC_ERR_BAD_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    FdBatch fb;
-    int rc = fb.layout(c, model_id, prior_class, C, Nparams, plength, Nvars);
-    if (rc) return rc;
-    rc = fd_ensure_poly(c);
-    if (rc) return rc;
-    const int E = fb.E, B = fb.B;
+    for (int i = 0; need_pl && i < 11; i++) psum += plength[i];
+    if (need_pl && psum != Nparams) return TAMCMC_ERR_BAD_ARG;
+    for (int k = 0; vars && k < Nvars; k++)
+        if (index_to_relax[k] < 0 || index_to_relax[k] >= Nparams || (fisher && !(hstep[k] != 0.0))) return TAMCMC_ERR_BAD_ARG;
+    return TAMCMC_OK;
+}
+
+int assemble_gradient(int C, int Nvars, const double *params, int64_t Nparams, const int32_t *index_to_relax, const double *hstep,
+                      const double *Tcoefs, double p, const double *S, bool deltas, const double *lpp, const double *lpm, const int *status,
+                      double *logL0, double *logPr0, double *grad, double *grad_prior) {
+    const int E = Nvars + 1;
     const size_t Np = (size_t)Nparams, Nv = (size_t)Nvars;
-    const bool windowed = fb.windowed, deltas = fb.deltas();
-    const size_t in_bytes = fb.in_bytes, out_bytes = fb.out_bytes, o_lpp = fb.o_lpp, o_lpm = fb.o_lpm, o_st = fb.o_st, o_drange = fb.o_drange;
-    HIPCHK(c, c->h_fd.reserve(in_bytes + out_bytes));
-    HIPCHK(c, c->d_fd.reserve(fb.total_bytes));
-    unsigned char *hb = c->h_fd.p, *db = c->d_fd.p;
-    std::memcpy(hb + fb.o_params, params, (size_t)C * Np * 8);
-    std::memcpy(hb + fb.o_h, hstep, Nv * 8);
-    if (prior_class != 0) {
-        std::memcpy(hb + fb.o_pr, priors, 4 * Np * 8);
-        std::memcpy(hb + fb.o_ex, extra_priors, 10 * 8);
-        std::memcpy(hb + fb.o_sw, priors_switch, Np * 4);
-    }
-    std::memcpy(hb + fb.o_pl, plength, 11 * 4);
-    std::memcpy(hb + fb.o_idx, index_to_relax, Nv * 4);
-    HIPCHK(c, hipMemcpyAsync(db, hb, in_bytes, hipMemcpyHostToDevice, st));
-    if (fb.rgb && c->precision == TAMCMC_PRECISION_STRICT) {
-        // STRICT keeps the reference's arithmetic for the scalar unpack too: long double on the host, exactly what
-        // tamcmc_hip_loglike_params_batch does with the same vector -- a vector's STRICT logL is the same bits from either entry
-        const size_t bytes_prep = ((size_t)B * sizeof(rgb::Prep) + 15) & ~(size_t)15;
-        const StageLayout L(B, fb.stride, (size_t)B * fb.per);
-        HIPCHK(c, c->h_rgb.reserve(bytes_prep + (size_t)B * sizeof(rgb::RowIn)));
-        HIPCHK(c, c->h_stage.reserve(L.off_mults));
-        rgb::Prep *hp = (rgb::Prep *)c->h_rgb.p;
-        rgb::RowIn *hr = (rgb::RowIn *)(c->h_rgb.p + bytes_prep);
-        unsigned char *hh = c->h_stage.p;
-        std::memset(hh, 0, L.off_mults);
-        int32_t *h_nh = (int32_t *)(hh + L.off_nh), *h_nn = (int32_t *)(hh + L.off_nn);
-        double *h_noise = (double *)(hh + L.off_noise);
-        const bool cte = model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4_ID;
-        const double ustep = c->hx[2] - c->hx[1];
-        int nthr = B / 4 > 0 ? (B / 4 < 8 ? B / 4 : 8) : 1;
-        (void)nthr;  // (only the host pass sees the OpenMP pragma)
-#pragma omp parallel for schedule(static) num_threads(nthr)
-        for (int s = 0; s < B; s++) {
-            const int ch = s / E, e = s - ch * E;
-            std::vector<double> v(params + (size_t)ch * Np, params + (size_t)(ch + 1) * Np);
-            if (e > 0) {
-                volatile double xp = v[(size_t)index_to_relax[e - 1]] + hstep[e - 1];
-                v[(size_t)index_to_relax[e - 1]] = xp;
-            }
-            double fmin;
-            rgb::unpack_vector(rgb::OneThread(), v.data(), plength, ustep, cte, c->armm_dense ? 1 : 0, hp[s], hr[s], h_noise + (size_t)s * fb.stride, h_nh + s,
-                               h_nn + s, &fmin);
-        }
-        fb.h_prep = hp; fb.h_rows = hr; fb.h_header = hh;
-    }
-    const size_t nS = fb.nS;
-    HIPCHK(c, c->d_part.reserve(nS * fb.ntiles * 2));
-    HIPCHK(c, c->d_S.reserve(nS));
-    HIPCHK(c, c->h_S.reserve(nS));
-    if (fb.model_doubles) HIPCHK(c, c->d_model.reserve(fb.model_doubles));
-    if (c->precision == TAMCMC_PRECISION_FAST) HIPCHK(c, c->d_bg.reserve(fb.bg_rows * fb.ntiles * 8));
-    rc = fb.enqueue(c, db, nullptr, c->d_part.p, c->d_S.p, c->d_model.p, c->d_bg.p, c->timing ? c->ev0 : nullptr, c->timing ? c->ev1 : nullptr);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->h_S.p, c->d_S.p, nS * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(hb + in_bytes, db + in_bytes, out_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (c->timing) {
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        c->kernel_ms += ms;
-        c->launches += 1;
-        c->evals += B;
-        if (windowed) {  // what the delta launch really touched (roofline bookkeeping of bench.py)
-            std::vector<int> rg((size_t)2 * B);
-            HIPCHK(c, hipMemcpy(rg.data(), db + o_drange, rg.size() * sizeof(int), hipMemcpyDeviceToHost));
-            for (int s = 0; s < B; s++) c->fd_bins += rg[2 * (size_t)s + 1] - rg[2 * (size_t)s];
-            c->fd_bins -= fb.bins_not_walked();  // (far-only tiles taken from the base point's moments)
-            c->fd_delta_evals += B;
-            std::vector<int> fl((size_t)B);
-            HIPCHK(c, hipMemcpy(fl.data(), db + fb.o_dflags, fl.size() * sizeof(int), hipMemcpyDeviceToHost));
-            for (int s = 0; s < B; s++) c->fd_full_evals += (fl[(size_t)s] & 2) ? 1 : 0;
-        }
-    }
-    const double *lpp = (const double *)(hb + o_lpp), *lpm = (const double *)(hb + o_lpm);
-    const int *stt = (const int *)(hb + o_st);
     const long pl = (long)p;
     int first_err = TAMCMC_OK;
     for (int ch = 0; ch < C; ch++) {
         const double T = Tcoefs ? Tcoefs[ch] : 1.0;
-        // S of evaluation e: full sums (brute force) or base sum + difference (windowed, adjoint)
-        auto scaled = [&](double S) {
-            long double f = S;
+        // call_likelihood (model_def.cpp:399-401): f = -p*(sum1+sum2) in long double, then / Tcoefs[m]
+        auto scaled = [&](double s) {
+            long double f = s;
             f = -pl * f;
             return (double)(f / T);
         };
         auto failed = [&](int e) {
-            const size_t s = (size_t)ch * E + e;
-            if (stt[s] != TAMCMC_OK) { if (first_err == TAMCMC_OK) first_err = stt[s]; return true; }
-            return false;
+            const int st = status ? status[(size_t)ch * E + e] : TAMCMC_OK;
+            if (first_err == TAMCMC_OK) first_err = st;
+            return st != TAMCMC_OK;
         };
-        const double L0 = failed(0) ? (double)NAN : scaled(deltas ? c->h_S.p[ch] : c->h_S.p[(size_t)ch * E]);
+        // S of evaluation e: full sums (B of them) or base sum + difference (deltas)
+        const double L0 = failed(0) ? (double)NAN : scaled(deltas ? S[ch] : S[(size_t)ch * E]);
         auto dlogL_of = [&](int e) {  // logL(theta + h e_k) - logL(theta)
             if (failed(e)) return (double)NAN;
-            if (deltas) return scaled(c->h_S.p[(size_t)C + (size_t)ch * E + e]);
-            return scaled(c->h_S.p[(size_t)ch * E + e]) - L0;
+            if (deltas) return scaled(S[(size_t)C + (size_t)ch * E + e]);
+            return scaled(S[(size_t)ch * E + e]) - L0;
         };
         logL0[ch] = L0;
-        if (logPr0) logPr0[ch] = lpp[(size_t)ch * E];
-        const double pr0 = lpp[(size_t)ch * E];
+        const double pr0 = lpp ? lpp[(size_t)ch * E] : 0.0;
+        if (logPr0) logPr0[ch] = pr0;
         for (int k = 0; k < Nvars; k++) {
             const double x0 = params[(size_t)ch * Np + index_to_relax[k]];
             volatile double xp = x0 + hstep[k];
             const double happ = xp - x0;  // the step actually applied (the device adds the same two doubles)
             double g = dlogL_of(k + 1) / happ;
-            if (prior_class != 0) {
+            if (lpp) {
                 if (!std::isfinite(g)) g = 0.0;
                 const double prp = lpp[(size_t)ch * E + k + 1], prm = lpm[(size_t)ch * E + k + 1];
                 double gp;
@@ -747,6 +687,99 @@ static int fd_run(tamcmc_hip_ctx *c, int model_id, int prior_class, int C, const
     return first_err;
 }
 
+}  // namespace tamcmc
+
+// STRICT keeps the reference's arithmetic for a red giant's scalar unpack too: long double on the host, exactly what
+// tamcmc_hip_loglike_params_batch does with the same vector -- a vector's STRICT logL is the same bits from either entry.  Fills the
+// context's pinned h_rgb / h_stage for the B vectors and points the batch at them.
+static int rgb_host_unpack(tamcmc_hip_ctx *c, FdBatch &fb, const double *params, const int32_t *plength, const int32_t *index_to_relax,
+                           const double *hstep) {
+    const int E = fb.E, B = fb.B;
+    const size_t Np = (size_t)fb.Np;
+    const size_t bytes_prep = ((size_t)B * sizeof(rgb::Prep) + 15) & ~(size_t)15;
+    const StageLayout L(B, fb.stride, (size_t)B * fb.per);
+    HIPCHK(c, c->h_rgb.reserve(bytes_prep + (size_t)B * sizeof(rgb::RowIn)));
+    HIPCHK(c, c->h_stage.reserve(L.off_mults));
+    rgb::Prep *hp = (rgb::Prep *)c->h_rgb.p;
+    rgb::RowIn *hr = (rgb::RowIn *)(c->h_rgb.p + bytes_prep);
+    unsigned char *hh = c->h_stage.p;
+    std::memset(hh, 0, L.off_mults);
+    int32_t *h_nh = (int32_t *)(hh + L.off_nh), *h_nn = (int32_t *)(hh + L.off_nn);
+    double *h_noise = (double *)(hh + L.off_noise);
+    const bool cte = fb.model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4_ID;
+    const double ustep = c->hx[2] - c->hx[1];
+    int nthr = B / 4 > 0 ? (B / 4 < 8 ? B / 4 : 8) : 1;
+    (void)nthr;  // (only the host pass sees the OpenMP pragma)
+#pragma omp parallel for schedule(static) num_threads(nthr)
+    for (int s = 0; s < B; s++) {
+        const int ch = s / E, e = s - ch * E;
+        std::vector<double> v(params + (size_t)ch * Np, params + (size_t)(ch + 1) * Np);
+        if (e > 0) {
+            volatile double xp = v[(size_t)index_to_relax[e - 1]] + hstep[e - 1];
+            v[(size_t)index_to_relax[e - 1]] = xp;
+        }
+        double fmin;
+        rgb::unpack_vector(rgb::OneThread(), v.data(), plength, ustep, cte, c->armm_dense ? 1 : 0, hp[s], hr[s], h_noise + (size_t)s * fb.stride, h_nh + s,
+                           h_nn + s, &fmin);
+    }
+    fb.h_prep = hp; fb.h_rows = hr; fb.h_header = hh;
+    return TAMCMC_OK;
+}
+
+static int fd_run(tamcmc_hip_ctx *c, int model_id, int prior_class, int C, const double *params, int64_t Nparams,
+                  const int32_t *plength, const int32_t *index_to_relax, int Nvars, const double *hstep, const double *Tcoefs,
+                  double p, const double *priors, const int32_t *priors_switch, const double *extra_priors, double *logL0,
+                  double *logPr0, double *grad, double *grad_prior) {
+    if (!c) return TAMCMC_ERR_BAD_ARG;
+    int rc = check_gradient_args(c, C, params, Nparams, plength, index_to_relax, Nvars, hstep,
+                                 logL0 && grad && (prior_class == 0 || (priors && priors_switch && extra_priors)), GA_PLENGTH | GA_VARS | GA_EMPTY_FIRST);
+    if (rc || C == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    FdBatch fb;
+    if ((rc = fb.layout(c, FdBatch::Request::FromOptions, model_id, prior_class, C, Nparams, plength, Nvars))) return rc;
+    if ((rc = fd_ensure_poly(c))) return rc;
+    const size_t Np = (size_t)Nparams, Nv = (size_t)Nvars, nS = fb.ws.S;
+    HIPCHK(c, c->h_fd.reserve(fb.in_bytes + fb.out_bytes));
+    HIPCHK(c, c->d_fd.reserve(fb.total_bytes));
+    unsigned char *hb = c->h_fd.p, *db = c->d_fd.p;
+    std::memcpy(hb + fb.o_params, params, (size_t)C * Np * 8);
+    std::memcpy(hb + fb.o_h, hstep, Nv * 8);
+    if (prior_class != 0) {
+        std::memcpy(hb + fb.o_pr, priors, 4 * Np * 8);
+        std::memcpy(hb + fb.o_ex, extra_priors, 10 * 8);
+        std::memcpy(hb + fb.o_sw, priors_switch, Np * 4);
+    }
+    std::memcpy(hb + fb.o_pl, plength, 11 * 4);
+    std::memcpy(hb + fb.o_idx, index_to_relax, Nv * 4);
+    HIPCHK(c, hipMemcpyAsync(db, hb, fb.in_bytes, hipMemcpyHostToDevice, st));
+    if (fb.rgb && c->precision == TAMCMC_PRECISION_STRICT && (rc = rgb_host_unpack(c, fb, params, plength, index_to_relax, hstep))) return rc;
+    const FdBatch::Buffers w{c->d_part, c->d_S, c->d_model, c->d_bg};
+    HIPCHK(c, fb.reserve(c, w));
+    HIPCHK(c, c->h_S.reserve(nS));
+    if ((rc = fb.enqueue(c, db, nullptr, w, c->timing ? c->ev0 : nullptr, c->timing ? c->ev1 : nullptr))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->h_S.p, c->d_S.p, nS * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(hb + fb.in_bytes, db + fb.in_bytes, fb.out_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (c->timing) {
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        c->kernel_ms += ms;
+        c->launches += 1;
+        c->evals += fb.B;
+        if (fb.route == FdBatch::Route::Windowed) {  // what the delta launch really touched (roofline bookkeeping of bench.py)
+            long bins = 0, full = 0;
+            HIPCHK(c, fb.delta_stats(db, &bins, &full));
+            c->fd_bins += bins;
+            c->fd_delta_evals += fb.B;
+            c->fd_full_evals += full;
+        }
+    }
+    return assemble_gradient(C, Nvars, params, Nparams, index_to_relax, hstep, Tcoefs, p, c->h_S.p, fb.deltas(),
+                             prior_class != 0 ? (const double *)(hb + fb.o_lpp) : nullptr, (const double *)(hb + fb.o_lpm),
+                             (const int *)(hb + fb.o_st), logL0, logPr0, grad, grad_prior);
+}
+
 extern "C" {
 
 int tamcmc_hip_fd_gradient(tamcmc_hip_ctx *c, int model_id, int C, const double *params, int64_t Nparams,
@@ -755,11 +788,8 @@ int tamcmc_hip_fd_gradient(tamcmc_hip_ctx *c, int model_id, int C, const double 
     if (tamcmc::is_envelope_model(model_id)) {  // every parameter moves every bin: Nvars + 1 full evaluations per chain, one batch
         if (!c) return TAMCMC_ERR_BAD_ARG;
         if (c->gradient == TAMCMC_GRADIENT_ADJOINT) return TAMCMC_ERR_BAD_MODEL;  // (no mode table: no table-space adjoint)
-        if (c->Nx <= 0) return TAMCMC_ERR_NO_SPECTRUM;
-        if (C < 0 || Nvars < 0 || !params || !index_to_relax || !hstep || !logL0 || !grad || Nparams < 1) return TAMCMC_ERR_BAD_ARG;
-        for (int k = 0; k < Nvars; k++)
-            if (index_to_relax[k] < 0 || index_to_relax[k] >= Nparams) return TAMCMC_ERR_BAD_ARG;
-        if (C == 0) return TAMCMC_OK;
+        const int rc = check_gradient_args(c, C, params, Nparams, nullptr, index_to_relax, Nvars, hstep, logL0 && grad, GA_VARS);
+        if (rc || C == 0) return rc;
         HIPCHK(c, hipSetDevice(c->device));
         return tamcmc::envelope_fd_run(c, model_id, false, 0, C, params, Nparams, index_to_relax, Nvars, hstep, Tcoefs, p, nullptr, nullptr,
                                        logL0, nullptr, grad, nullptr);
@@ -776,47 +806,36 @@ int tamcmc_hip_fd_gradient_posterior(tamcmc_hip_ctx *c, int model_id, int prior_
     if (tamcmc::is_envelope_model(model_id)) {  // brute force, priors of classes 0 / 1 on the device (envelope.hip)
         if (!c) return TAMCMC_ERR_BAD_ARG;
         if (c->gradient == TAMCMC_GRADIENT_ADJOINT) return TAMCMC_ERR_BAD_MODEL;
-        if (c->Nx <= 0) return TAMCMC_ERR_NO_SPECTRUM;
-        if (C < 0 || Nvars < 0 || !params || !index_to_relax || !hstep || !logL0 || !grad || Nparams < 1 || !priors || !priors_switch)
-            return TAMCMC_ERR_BAD_ARG;
-        for (int k = 0; k < Nvars; k++)
-            if (index_to_relax[k] < 0 || index_to_relax[k] >= Nparams) return TAMCMC_ERR_BAD_ARG;
+        const int rc = check_gradient_args(c, C, params, Nparams, nullptr, index_to_relax, Nvars, hstep, logL0 && grad && priors && priors_switch,
+                                           GA_VARS);
+        if (rc) return rc;
         if (prior_class != 0 && prior_class != 1) return TAMCMC_ERR_BAD_MODEL;
         if (C == 0) return TAMCMC_OK;
         HIPCHK(c, hipSetDevice(c->device));
         return tamcmc::envelope_fd_run(c, model_id, true, prior_class, C, params, Nparams, index_to_relax, Nvars, hstep, Tcoefs, p, priors,
                                        priors_switch, logL0, logPr0, grad, grad_prior);
     }
-    const bool rgb = (model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4_ID || model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4_ID);
-    if (rgb ? prior_class != 4 : (prior_class != 2 && prior_class != 3)) return TAMCMC_ERR_BAD_MODEL;  // io_asymptotic is the red giants' prior, and theirs only
+    if (is_rgb_model(model_id) ? prior_class != 4 : (prior_class != 2 && prior_class != 3)) return TAMCMC_ERR_BAD_MODEL;  // io_asymptotic is the red giants' prior, and theirs only
     return fd_run(c, model_id, prior_class, C, params, Nparams, plength, index_to_relax, Nvars, hstep, Tcoefs, p, priors,
                   priors_switch, extra_priors, logL0, logPr0, grad, grad_prior);
 }
 
-// Audit entry of the adjoint route: the batch with no perturbed vector (Nvars = 0) under TAMCMC_GRADIENT_ADJOINT, whatever the context's
+// Audit entry of the adjoint route: the batch with no perturbed vector (Nvars = 0) on Route::Adjoint, whatever the context's
 // option says -- unpack, base launch, k_adj_rows, k_adj_noise -- and G / Gn brought back.
 int tamcmc_hip_adjoint_table(tamcmc_hip_ctx *c, int model_id, int C, const double *params, int64_t Nparams, const int32_t *plength,
                              const double *Tcoefs, double p, double *G, double *Gn, int *nrows) {
     (void)Tcoefs; (void)p;  // (the adjoint of the un-tempered sum S: logL = -p S / T)
     if (!c) return TAMCMC_ERR_BAD_ARG;
     if (tamcmc::is_envelope_model(model_id)) return TAMCMC_ERR_BAD_MODEL;
-    if (c->Nx <= 0) return TAMCMC_ERR_NO_SPECTRUM;
-    if (C < 0 || !params || !plength || Nparams < 1) return TAMCMC_ERR_BAD_ARG;
-    long psum = 0;
-    for (int i = 0; i < 11; i++) psum += plength[i];
-    if (psum != Nparams) return TAMCMC_ERR_BAD_ARG;
+    int rc = check_gradient_args(c, C, params, Nparams, plength, nullptr, 0, nullptr, true, GA_PLENGTH);
+    if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     FdBatch fb;
-    const int saved = c->gradient;
-    c->gradient = TAMCMC_GRADIENT_ADJOINT;
-    int rc = fb.layout(c, model_id, 0, C > 0 ? C : 1, Nparams, plength, 0);
-    c->gradient = saved;
-    if (rc) return rc;
+    if ((rc = fb.layout(c, FdBatch::Request::Adjoint, model_id, 0, C > 0 ? C : 1, Nparams, plength, 0))) return rc;
     if (nrows) *nrows = fb.per;
     if (C == 0) return TAMCMC_OK;
-    rc = fd_ensure_poly(c);
-    if (rc) return rc;
+    if ((rc = fd_ensure_poly(c))) return rc;
     const size_t Np = (size_t)Nparams;
     HIPCHK(c, c->h_fd.reserve(fb.in_bytes + fb.out_bytes));
     HIPCHK(c, c->d_fd.reserve(fb.total_bytes));
@@ -825,12 +844,9 @@ int tamcmc_hip_adjoint_table(tamcmc_hip_ctx *c, int model_id, int C, const doubl
     std::memcpy(hb + fb.o_params, params, (size_t)C * Np * 8);
     std::memcpy(hb + fb.o_pl, plength, 11 * 4);
     HIPCHK(c, hipMemcpyAsync(db, hb, fb.in_bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(c, c->d_part.reserve(fb.nS * fb.ntiles * 2));
-    HIPCHK(c, c->d_S.reserve(fb.nS));
-    HIPCHK(c, c->d_model.reserve(fb.model_doubles));
-    if (c->precision == TAMCMC_PRECISION_FAST) HIPCHK(c, c->d_bg.reserve(fb.bg_rows * fb.ntiles * 8));
-    rc = fb.enqueue(c, db, nullptr, c->d_part.p, c->d_S.p, c->d_model.p, c->d_bg.p, nullptr, nullptr);
-    if (rc) return rc;
+    const FdBatch::Buffers w{c->d_part, c->d_S, c->d_model, c->d_bg};
+    HIPCHK(c, fb.reserve(c, w));
+    if ((rc = fb.enqueue(c, db, nullptr, w, nullptr, nullptr))) return rc;
     if (G) HIPCHK(c, hipMemcpyAsync(G, db + fb.o_adjG, (size_t)C * fb.per * ADJ_F * 8, hipMemcpyDeviceToHost, st));
     if (Gn) HIPCHK(c, hipMemcpyAsync(Gn, db + fb.o_adjGn, (size_t)C * fb.stride * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(hb + fb.in_bytes, db + fb.in_bytes, fb.out_bytes, hipMemcpyDeviceToHost, st));

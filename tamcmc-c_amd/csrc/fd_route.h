@@ -1,0 +1,40 @@
+// fd_route.h -- which of its four routes a gradient batch (fd_batch.h) takes, plain C++ so that a host test can compile it
+// (tests/fd_route_driver.cpp).
+#pragma once
+#include "../../include/tamcmc_hip.h"
+
+namespace tamcmc {
+
+// What comes after the tables of the C x (Nvars + 1) vectors:
+//   Brute     every table evaluated in full: B sums;
+//   Windowed  the C base points in full (planes 1/M0, y/M0, M0 kept), then the DELTA launch on the rows a perturbation changed: C base sums
+//             and B differences;
+//   Adjoint   the C base points as in Windowed, then the table-space adjoint G / Gn of each (adjoint.h) contracted with (table e - base
+//             table), written where the DELTA launch writes its difference: the sums read like Windowed's;
+//   Rows      every perturbed table given its base table's windows, then ONE launch that leaves the B model rows (fisher.h): no sums.
+enum class FdRoute { Brute, Windowed, Adjoint, Rows };
+// Who asks: the gradient entries and the sampler follow the context's options, the audit entry (tamcmc_hip_adjoint_table) and the Fisher
+// information (tamcmc_hip_fisher) name their route whatever the options say.
+enum class FdRequest { FromOptions, Adjoint, Rows };
+
+// gradient = TAMCMC_OPT_GRADIENT, fd_windowed = TAMCMC_OPT_FD_WINDOWED, precision = TAMCMC_OPT_PRECISION, delta_geometry: the DELTA variant
+// of the likelihood kernel exists for the context's workgroup geometry; rgb: a red-giant model (tables of variable length).
+// Returns TAMCMC_OK and the route, or the refusal.
+inline int fd_route(FdRequest request, int gradient, int fd_windowed, int precision, bool delta_geometry, int Nvars, bool rgb, FdRoute *route) {
+    const bool strict = precision == TAMCMC_PRECISION_STRICT;
+    if (request == FdRequest::Rows) {
+        if (rgb || strict) return TAMCMC_ERR_BAD_ARG;  // (tamcmc_hip_fisher refuses both before it gets here)
+        *route = FdRoute::Rows;
+    } else if (request == FdRequest::Adjoint || gradient == TAMCMC_GRADIENT_ADJOINT) {
+        if (rgb) return TAMCMC_ERR_BAD_MODEL;  // (no row-by-row contraction of tables that differ in length)
+        if (strict) return TAMCMC_ERR_BAD_ARG;  // (the planes are the FAST base launch's)
+        *route = FdRoute::Adjoint;
+    } else {
+        // only the multiplets a perturbation changes are re-evaluated, on their windows, against the stored base model row (SURVEY
+        // section 7, step 6: "the main algorithmic lever")
+        *route = (fd_windowed && !strict && delta_geometry && Nvars > 0) ? FdRoute::Windowed : FdRoute::Brute;
+    }
+    return TAMCMC_OK;
+}
+
+}  // namespace tamcmc

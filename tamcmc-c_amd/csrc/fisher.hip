@@ -175,18 +175,13 @@ int tamcmc_hip_fisher(tamcmc_hip_ctx *c, int model_id, int C, const double *para
     if (!c) return TAMCMC_ERR_BAD_ARG;
     if (is_envelope_model(model_id) || model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4 || model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4)
         return TAMCMC_ERR_BAD_MODEL;  // (no table / tables of variable length)
-    if (c->Nx <= 0) return TAMCMC_ERR_NO_SPECTRUM;
-    if (C < 0 || Nvars < 1 || Nvars > 16384 || !params || !plength || !index_to_relax || !hstep || !F || Nparams < 1) return TAMCMC_ERR_BAD_ARG;
+    int rc = check_gradient_args(c, C, params, Nparams, plength, index_to_relax, Nvars, hstep, F != nullptr, GA_PLENGTH | GA_VARS | GA_FISHER);
+    if (rc) return rc;
     if (c->precision == TAMCMC_PRECISION_STRICT) return TAMCMC_ERR_BAD_ARG;  // (as the adjoint route)
-    long psum = 0;
-    for (int i = 0; i < 11; i++) psum += plength[i];
-    if (psum != Nparams) return TAMCMC_ERR_BAD_ARG;
-    for (int k = 0; k < Nvars; k++)
-        if (index_to_relax[k] < 0 || index_to_relax[k] >= Nparams || !(hstep[k] != 0.0)) return TAMCMC_ERR_BAD_ARG;
     if (C == 0) return TAMCMC_OK;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    int rc = fd_ensure_poly(c);
+    rc = fd_ensure_poly(c);
     if (rc) return rc;
     const size_t Np = (size_t)Nparams, N = (size_t)Nvars, Nx = (size_t)c->Nx;
     const int NP = fisher_padded(Nvars), nslab = fisher_slabs((long)c->Nx);
@@ -214,8 +209,7 @@ int tamcmc_hip_fisher(tamcmc_hip_ctx *c, int model_id, int C, const double *para
     int first_err = TAMCMC_OK;
     auto pass = [&](int c0, int cp) -> int {
         FdBatch fb;
-        fb.rows_only = true;
-        int r = fb.layout(c, model_id, 0, cp, Nparams, plength, 2 * Nvars);
+        int r = fb.layout(c, FdBatch::Request::Rows, model_id, 0, cp, Nparams, plength, 2 * Nvars);
         if (r) return r;
         HIPCHK(c, c->h_fd.reserve(fb.in_bytes + fb.out_bytes));
         HIPCHK(c, c->d_fd.reserve(fb.total_bytes));
@@ -244,12 +238,10 @@ int tamcmc_hip_fisher(tamcmc_hip_ctx *c, int model_id, int C, const double *para
         HIPCHK(c, c->d_fisher.reserve(n_rh + cp + n_F + n_part));
         double *d_rh = c->d_fisher.p, *d_T = d_rh + n_rh, *d_F = d_T + cp, *d_part = d_F + n_F;
         HIPCHK(c, hipMemcpyAsync(d_rh, c->h_S.p, (n_rh + cp) * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(c, c->d_part.reserve(fb.nS * fb.ntiles * 2));
-        HIPCHK(c, c->d_S.reserve(fb.nS));
-        HIPCHK(c, c->d_model.reserve(fb.model_doubles));
-        if (c->precision == TAMCMC_PRECISION_FAST) HIPCHK(c, c->d_bg.reserve(fb.bg_rows * fb.ntiles * 8));
+        const FdBatch::Buffers w{c->d_part, c->d_S, c->d_model, c->d_bg};
+        HIPCHK(c, fb.reserve(c, w));
         if (c->timing) HIPCHK(c, hipEventRecord(ev[0], st));
-        r = fb.enqueue(c, db, nullptr, c->d_part.p, c->d_S.p, c->d_model.p, c->d_bg.p, c->timing ? c->ev0 : nullptr, c->timing ? c->ev1 : nullptr);
+        r = fb.enqueue(c, db, nullptr, w, c->timing ? c->ev0 : nullptr, c->timing ? c->ev1 : nullptr);
         if (r) return r;
         GramArgs g;
         g.M0 = c->d_model.p; g.P = g.M0 + Nx; g.Mn = g.M0 + (1 + N) * Nx; g.rh = d_rh;
