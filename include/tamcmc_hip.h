@@ -124,7 +124,11 @@ extern "C" {
 #define TAMCMC_OPT_FISHER_WORKSPACE_MB 10 /* value: MiB (>= 1, default 2048) of model rows tamcmc_hip_fisher keeps on the device per pass: a chain
                                         takes 2 Nvars Nx 8 bytes, as many chains per pass as fit, a single chain above the budget still
                                         runs alone.  The result does not depend on it */
-#define TAMCMC_FISHER_SLAB 2048      /* bins per workgroup (and per partial matrix) of the Gram kernel of tamcmc_hip_fisher / _weighted_gram */
+#define TAMCMC_OPT_RGB_DEVICE_LANGEVIN 11 /* value: 0/1 (default 0) -- 1: tamcmc_sampler_create builds the device-resident engine's Langevin
+                                        sampler (engine = 1, use_drift = 1) for the red-giant models, ids 25 and 27; 0: it refuses them
+                                        with TAMCMC_ERR_BAD_MODEL.  Read when the sampler is created: changing it afterwards does not
+                                        affect an existing sampler.  FAST arithmetic and TAMCMC_GRADIENT_FD only (tamcmc_sampler.h) */
+#define TAMCMC_FISHER_SLAB 2048     /* bins per workgroup (and per partial matrix) of the Gram kernel of tamcmc_hip_fisher / _weighted_gram */
 
 /* One (n,l) multiplet: <=7 Lorentzian m-components on its truncation window.
  * This is the flat "mode table" row every Lorentzian model of the dispatch table reduces to

@@ -45,7 +45,8 @@ typedef struct tamcmc_sampler_config {
     int32_t n_Nt_learn;
     int32_t engine;                /* 0 = host-driven loop (one batched device call per iteration),
                                       1 = device-resident iteration (proposal, priors, unpack, accept, swap, adaptation on the GPU;
-                                          use_drift must be 0) */
+                                          use_drift = 1: the Langevin step with the gradient batch on the device -- see the limits
+                                          table below for the red-giant and the Gaussian-envelope models) */
     int64_t dN_mixing;
     const double *init_errors;     /* [Nvars] initial proposal standard deviations (errors_default.cfg), NULL -> 1 */
     /* additions of this build */
@@ -81,8 +82,14 @@ int64_t tamcmc_sampler_nvars(const tamcmc_sampler *s);
  *   Nparams + 2 Nvars, device      <= 971                the fused one-launch iteration borrows the likelihood tile's 12 KB of LDS for its
  *     engine, fused step                                 candidate roles; longer vectors run every iteration on the lockstep kernels
  *                                                        (TAMCMC_INFO_FUSED_AVAILABLE = 0) -- same chains bit for bit
- *   red-giant models (ids 25/27)   device engine: lockstep kernels only, no Langevin step (engine = 1 with use_drift = 1 ->
- *                                  TAMCMC_ERR_BAD_MODEL); host-driven engine: random walk or Langevin (tamcmc_hip_fd_gradient_posterior)
+ *   red-giant models (ids 25/27)   device engine: lockstep kernels only.  Its Langevin step (engine = 1 with use_drift = 1) is opt-in:
+ *                                  TAMCMC_ERR_BAD_MODEL at tamcmc_sampler_create unless the context has TAMCMC_OPT_RGB_DEVICE_LANGEVIN = 1
+ *                                  at that moment.  Such a sampler runs under FAST / FAST_DIRECT arithmetic and TAMCMC_GRADIENT_FD:
+ *                                  tamcmc_sampler_run on a STRICT context returns TAMCMC_ERR_BAD_ARG (the long-double unpack STRICT
+ *                                  promises is the host's, and the proposals never leave the device), under TAMCMC_GRADIENT_ADJOINT
+ *                                  TAMCMC_ERR_BAD_MODEL; either way the chains stay where they were and a later call continues them.
+ *                                  Nchains (Nvars + 1) <= 65535.  Host-driven engine: random walk or Langevin, any arithmetic mode
+ *                                  (tamcmc_hip_fd_gradient_posterior)
  *   Gaussian-envelope models       host-driven engine only (random walk or Langevin); engine = 1 -> TAMCMC_ERR_BAD_MODEL at
  *     (ids 0/1)                    tamcmc_sampler_create
  *   tamcmc_sampler_seed_proposal   models 3, 11, 12, 13, 14, 23 on a FAST or FAST_DIRECT context (tamcmc_hip_fisher's refusals: ids 0, 1, 25,

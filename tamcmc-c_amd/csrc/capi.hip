@@ -110,6 +110,10 @@ int tamcmc_hip_set_option(tamcmc_hip_ctx *c, int option, int64_t value) {
         if (value < 1 || value > (1 << 20)) return TAMCMC_ERR_BAD_ARG;
         c->fisher_ws_mb = value;
         return TAMCMC_OK;
+    case TAMCMC_OPT_RGB_DEVICE_LANGEVIN:
+        if (value < 0 || value > 1) return TAMCMC_ERR_BAD_ARG;
+        c->rgb_device_langevin = (int)value;
+        return TAMCMC_OK;
     case TAMCMC_OPT_WORKGROUP:  // sets the workgroup size AND its default bins per thread
         if (value != 64 && value != 256) return TAMCMC_ERR_BAD_ARG;
         c->wgs = (int)value;

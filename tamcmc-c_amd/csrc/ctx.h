@@ -71,6 +71,7 @@ struct tamcmc_hip_ctx {
     int armm_dense = 0;   // red-giant pre-step: 1 = dense grid walk
     int64_t fisher_ws_mb = 2048;  // tamcmc_hip_fisher: budget of the model rows kept on the device per pass, MiB (fd_rgb_chunk.h: fisher_chunk)
     int gradient = TAMCMC_GRADIENT_FD;  // gradient batches: finite differences, or the table-space adjoint with frozen windows (adjoint.h)
+    int rgb_device_langevin = 0;  // 1: the device-resident engine builds its Langevin sampler for the red-giant ids (read at sampler creation)
     // resident spectrum
     int64_t Nx = 0;
     std::vector<double> hx;  // host copy of x (table builders need x[0], x[Nx-1], step)

@@ -10,7 +10,8 @@
 //                   adaptation of the chain's proposal law when the schedule says so (MALA.cpp:296-319);
 //   k_mala_settle   parallel-tempering swap on the post-test outcomes (MALA.cpp:397-461; the stored gradients follow the positions,
 //                   their likelihood share re-tempered), settled state + records, then the next proposal x' = x + drift + L z.
-// Nothing crosses PCIe inside an iteration; the host only enqueues.
+// Nothing crosses PCIe inside an iteration; the host only enqueues.  Neither kernel knows a model: the red-giant ids (25 / 27, opt-in:
+// TAMCMC_OPT_RGB_DEVICE_LANGEVIN) differ in how the batch builds its tables only (fd_batch.hip: k_fd_rgb_perturb + the pre-step).
 
 struct MalaArgs {
     const double *S, *lpp, *lpm;  // sums / log-priors (forward, backward) of the last finite-difference batch (fd_batch.h)

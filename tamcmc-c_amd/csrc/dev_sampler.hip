@@ -112,8 +112,8 @@ struct DevSampler::Impl {
 
     hipEvent_t gev[8][2];  // fused step with two chain groups: event pairs around sampled launches of the second group (on its stream)
     int n_gev = 0;
-    bool rgb = false;  // ids 25 / 27: k_iterate leaves the table to the pre-step kernels (rgb_device_stage), lockstep scheme
-    int rgb_bmax = 0;  // chains per workspace slice (one slice per chain group)
+    bool rgb = false;  // ids 25 / 27: k_iterate leaves the table to the pre-step kernels (rgb_device_stage), lockstep scheme; Langevin step: the gradient batch builds the tables
+    int rgb_bmax = 0;  // chains per workspace slice (one slice per chain group; Langevin step: unused after init)
     bool fused_ok = false;
     int fused_mode = -1, fused_K = 0;  // the geometry the (A) buffers were sized for
     int tile_rot = 0;  // launch-order hint of k_loglike (first near-field tile of chain 0's initial table)
@@ -260,11 +260,16 @@ int DevSampler::init(tamcmc_hip_ctx *c, const DevSamplerInit &in) {
         I.G = G;
     }
     if (I.rgb) {
-        // the finite-difference batch builds red-giant tables now (fd_batch.hip); what this engine's Langevin step still lacks is its
-        // candidate tables through the pre-step (k_mala_settle's proposals are unpacked by wg_unpack, which knows no mixed modes)
-        if (I.use_drift) return TAMCMC_ERR_BAD_MODEL;
-        I.rgb_bmax = (in.C + I.G - 1) / I.G;
-        int rc = rgb_device_prepare(c, I.rgb_bmax, I.G, in.plength, &a.desc.per, &a.desc.stride);  // one workspace slice per chain group
+        // Langevin step: opt-in (TAMCMC_OPT_RGB_DEVICE_LANGEVIN, read here and nowhere else).  Its proposals are unpacked by the
+        // gradient batch (FdBatch::enqueue on a.params_prop: k_fd_rgb_perturb -> rgb_device_stage), which sizes the pre-step workspace
+        // for its own chunk at every call (FdBatch::layout); k_mala_test and k_mala_settle see the batch's sums, priors and statuses only.
+        // Such a sampler never runs k_iterate or the lockstep pre-step: no workspace slices per chain group, one slice of C vectors
+        // here for the table dimensions (per, stride) the arrays below are sized with
+        if (I.use_drift && !c->rgb_device_langevin) return TAMCMC_ERR_BAD_MODEL;
+        if (I.use_drift && ((long)in.C * (in.Nv + 1) > 65535 || in.plength[10] < 6)) return TAMCMC_ERR_BAD_ARG;  // (FdBatch::layout's limits, at creation)
+        const int slices = I.use_drift ? 1 : I.G;
+        I.rgb_bmax = (in.C + slices - 1) / slices;
+        int rc = rgb_device_prepare(c, I.rgb_bmax, slices, in.plength, &a.desc.per, &a.desc.stride);  // random walk: one workspace slice per chain group
         if (rc) return rc;
     }
     a.desc.Nx = (int)c->Nx;
@@ -1014,7 +1019,8 @@ int DevSampler::run(long it0, long n_iter, const char *learn, double *samples, d
 }
 
 // The Langevin engine (use_drift): per iteration k_mala_settle (settle it-1, propose it) -> the finite-difference batch of the proposals
-// (k_fd_unpack, base k_loglike with model rows, k_loglike<DELTA>, k_finalize x2) -> k_mala_test.  See dev_mala_impl.h.
+// (k_fd_unpack -- red giants: k_fd_rgb_perturb and the pre-step --, base k_loglike with model rows, k_loglike<DELTA>, k_finalize x2)
+// -> k_mala_test.  See dev_mala_impl.h.
 int DevSampler::run_mala(long it0, long n_iter, const char *learn, double *samples, double *stats) {
     Impl &I = *impl;
     tamcmc_hip_ctx *c = I.ctx;
@@ -1024,12 +1030,19 @@ int DevSampler::run_mala(long it0, long n_iter, const char *learn, double *sampl
     I.armed_it = -1;
     const size_t C = (size_t)a.C, Nv = (size_t)a.Nv, Np = (size_t)a.desc.Np;
     const FdBatch::Buffers fd_ws{I.fd_part, I.fd_S, I.fd_model, I.fd_bg};
+    // Red giants under STRICT: the batch would need the host's long-double unpack of every proposal (FdBatch::h_prep), and the proposals
+    // exist on the device only.  Refused here, before anything is enqueued or counted: state, iteration and gradients stay as they are
+    if (I.rgb && c->precision == TAMCMC_PRECISION_STRICT) return TAMCMC_ERR_BAD_ARG;
     {   // the batch's layout follows the context's options (arithmetic mode, geometry, windowed differences): re-laid out when they change
+        // (red giants: layout() also re-reserves the context's pre-step workspace for the batch's chunk -- another sampler or a direct
+        // gradient call may have been the last to size it; the slice is taken from the context at every enqueue, never kept.  A route
+        // the model has not -- the adjoint -- is refused by layout() with the chains where they were)
         FdBatch nb;
         int rc = nb.layout(c, FdBatch::Request::FromOptions, I.model_id, I.prior_class, a.C, (int64_t)Np, I.h_plength.data(), a.Nv);
         if (rc) return rc;
         const bool need_bg = c->precision == TAMCMC_PRECISION_FAST && !I.fd_bg.p;  // (a switch to FAST between two calls keeps every size)
-        if (nb.total_bytes != I.fd.total_bytes || nb.route != I.fd.route || nb.ntiles != I.fd.ntiles || !I.fd_block.p || need_bg) {
+        if (nb.total_bytes != I.fd.total_bytes || nb.route != I.fd.route || nb.ntiles != I.fd.ntiles || nb.rgb != I.fd.rgb ||
+            nb.chunk != I.fd.chunk || !I.fd_block.p || need_bg) {
             I.fd = nb;
             rc = fd_ensure_poly(c);
             if (rc) return rc;
