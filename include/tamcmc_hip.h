@@ -245,6 +245,9 @@ int tamcmc_hip_fd_gradient(tamcmc_hip_ctx *ctx, int model_id, int C, const doubl
  * priors = 4 x Nparams row-major table,
  * priors_switch = primitive ids, extra_priors[10]: Input_Data of tamcmc/headers/data.h:51-62).  Where the forward point
  * leaves a prior's support the backward difference of the prior is used, else that prior term is flat.
+ * A prior that tamcmc_log_prior refuses -- a primitive id without an implementation (3, 9, 11, 12), impose_normHnlm = 2, model_index
+ * 0..8 -- is refused here with the same status, TAMCMC_ERR_BAD_MODEL, for every prior class: the evaluation's slot fails like one whose
+ * table failed and the call returns the status; it is never reported as TAMCMC_OK with a log-prior of -inf.
  * Out: logL0[C] (tempered), logPr0[C] (may be NULL), grad[C x Nvars], grad_prior[C x Nvars] (may be NULL: the prior's
  * share of grad, so that a caller can re-temper the likelihood share after a parallel-tempering swap). */
 int tamcmc_hip_fd_gradient_posterior(tamcmc_hip_ctx *ctx, int model_id, int prior_class, int C, const double *params,

@@ -95,13 +95,15 @@ __global__ void __launch_bounds__(FB) k_fd_unpack(const FdArgs a) {
         if (tid == FB - 1) mt::shared_scalars_base(a.desc.model_id, s_params, a.desc.plength, *U.S);
         __syncthreads();
     }
-    // the likelihood is evaluated whatever the prior says: the caller combines the parts
-    if (tid == 0) *U.status = TAMCMC_OK;
+    // the likelihood is evaluated whatever the prior says: the caller combines the parts.  A prior the device cannot evaluate (an unsupported
+    // id or option: TAMCMC_ERR_BAD_MODEL, as tamcmc_log_prior says) is not a "-inf": its status is kept across the reset and fails the slot
+    int st_prior = TAMCMC_OK;
+    if (tid == 0) { st_prior = *U.status; *U.status = TAMCMC_OK; }
     __syncthreads();
     wg_unpack(a.desc, s_params, U, slot, a.T, true);
     if (tid == 0) {
         a.logPr_plus[slot] = lp;
-        a.status[slot] = *U.status;
+        a.status[slot] = st_prior != TAMCMC_OK ? st_prior : *U.status;
     }
     // the log-prior at theta - h e_k is only ever looked at when the forward point lies outside a prior's support (one-sided fallback of
     // the gradient's prior share): evaluated in that case alone (workgroup-uniform: every lane holds the same lp)

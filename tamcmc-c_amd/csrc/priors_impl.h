@@ -7,7 +7,7 @@
 // Where the reference exits (unsupported prior ids, model classes flagged "needs checks") *status is set to
 // TAMCMC_ERR_BAD_MODEL and -inf is returned.
 // The priors are a SUM of independent terms; `term range` arguments let the device evaluate the terms in parallel
-// (one term per thread, tree-summed) while the host evaluates them all in the reference's order.
+// (one term per thread, tree-summed) while the host evaluates them all in the reference's order.  The host's sum is compensated (TermSum below).
 #pragma once
 #include "mode_tables_impl.h"
 
@@ -284,6 +284,34 @@ TM_HD bool envelope_width_rejects(double numax, double sigma) {
     return (xreal)sigma < Dnu_expected / 2;
 }
 
+// Sum of the additive terms in the reference's order.  Device (double): plain left-to-right additions, the sum every device path is
+// compared with.  Host (long double): the same order with the rounding of each addition carried along (Neumaier) and added at the end --
+// a prior of ~170 terms at |f| ~ 1e3 otherwise drifts ~1e-15 from the exact sum of its terms, more than the 4 x 2^-63 x sum max(1, |term|)
+// that tests/test_priors.py allows against the 50-digit reference.  A term of -inf makes the sum -inf as before.
+struct TermSum {
+    xreal s = 0, c = 0;
+    TM_HD void add(xreal t) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        s = s + t;
+#else
+        if (!((t - t) == 0 && (s - s) == 0)) {  // a non-finite operand: no compensation to keep
+            s = s + t;
+            return;
+        }
+        const xreal n = s + t;
+        c = c + ((xfabs(s) >= xfabs(t)) ? ((s - n) + t) : ((t - n) + s));
+        s = n;
+#endif
+    }
+    TM_HD xreal value() const {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return s;
+#else
+        return ((s - s) == 0) ? s + c : s;
+#endif
+    }
+};
+
 // ---- serial evaluation in the reference's order (host; also usable on the device by one thread) ----
 // generic_terms (class 4): the Np generic prior terms already evaluated (the device spreads them over lanes; summed here in the same order)
 TM_HD xreal prior_serial(int prior_class, const double *params, const int *pl, long Np, const double *pp, const int *sw,
@@ -291,9 +319,9 @@ TM_HD xreal prior_serial(int prior_class, const double *params, const int *pl, l
     xreal f = 0;
     if (prior_class == 1) {  // priors_Harvey_Gaussian: [H1, tc1, p1, H2, tc2, p2, B0, Amax, numax, Gauss_sigma]
         if (envelope_width_rejects(params[8], params[9])) return neg_inf();
-        xreal pena = 0;  // apply_generic_priors' own sum, then added to f (priors_calc.cpp:642)
-        for (long i = 0; i < Np; i++) pena = pena + generic_prior_term(params, Np, pp, sw, i, status);
-        return f + pena;
+        TermSum pena;  // apply_generic_priors' own sum, then added to f (priors_calc.cpp:642)
+        for (long i = 0; i < Np; i++) pena.add(generic_prior_term(params, Np, pp, sw, i, status));
+        return f + pena.value();
     }
     if (prior_class == 0) {  // priors_Kallinger2014_Gaussian: 14 noise parameters, Amax, numax, sigma, mu_numax, omega_numax
         const double a1 = params[5], a2 = params[6];
@@ -302,29 +330,32 @@ TM_HD xreal prior_serial(int prior_class, const double *params, const int *pl, l
         const xreal numax = params[15], mu_numax = params[17], omega_numax = params[18];
         if (numax + mu_numax < 0) return neg_inf();
         f = f + logP_gaussian(0, xfabs(omega_numax), mu_numax);
-        xreal pena = 0;
-        for (long i = 0; i < Np; i++) pena = pena + generic_prior_term(params, Np, pp, sw, i, status);
-        return f + pena;
+        TermSum pena;
+        for (long i = 0; i < Np; i++) pena.add(generic_prior_term(params, Np, pp, sw, i, status));
+        return f + pena.value();
     }
     if (prior_class == 2) {
         const xreal c = ms_global_constraints(params, pl, sw, extra, status);
         if (c != 0) return c;
         const int nnorm = ((int)extra[8] == 1 && ms_global_norm_active(extra)) ? 3 : 0;
-        for (int t = 0; t < nnorm; t++) f = f - ms_global_norm_term();  // before everything else (priors_calc.cpp:228-241)
-        xreal pena = 0;  // apply_generic_priors' own sum, then added to f (priors_calc.cpp:276)
-        for (long i = 0; i < Np; i++) pena = pena + generic_prior_term(params, Np, pp, sw, i, status);
-        f = f + pena;
+        TermSum F;
+        for (int t = 0; t < nnorm; t++) F.add(-ms_global_norm_term());  // before everything else (priors_calc.cpp:228-241)
+        TermSum pena;  // apply_generic_priors' own sum, then added to f (priors_calc.cpp:276)
+        for (long i = 0; i < Np; i++) pena.add(generic_prior_term(params, Np, pp, sw, i, status));
+        F.add(pena.s);
+        F.c = F.c + pena.c;
         double fit[2];
         mt::linfit_index(params + pl[0] + pl[1], pl[2], fit);
         const int ne = ms_global_extra_terms(pl, extra) - nnorm;
-        for (int t = 0; t < ne; t++) f = f + ms_global_extra_term(params, pl, extra, fit[0], t);
-        return f;
+        for (int t = 0; t < ne; t++) F.add(ms_global_extra_term(params, pl, extra, fit[0], t));
+        return F.value();
     }
     if (prior_class == 3) {
         const xreal c = local_constraints(params, pl, sw, extra);
         if (c != 0) return c;
-        for (long i = 0; i < Np; i++) f = f + generic_prior_term(params, Np, pp, sw, i, status);
-        return f;
+        TermSum F;
+        for (long i = 0; i < Np; i++) F.add(generic_prior_term(params, Np, pp, sw, i, status));
+        return F.value();
     }
     if (prior_class == 4) {  // io_asymptotic: priors_asymptotic, priors_calc.cpp:319-512 (host engine only: the RGB model's pre-step)
         const int Nmax = pl[0], lmax = pl[1], Nfl0 = pl[2], Nfl1 = pl[3], Nfl2 = pl[4], Nfl3 = pl[5], Nsplit = pl[6], Nwidth = pl[7];
@@ -341,7 +372,8 @@ TM_HD xreal prior_serial(int prior_class, const double *params, const int *pl, l
         if ((sw[Nmax + lmax + Nf + 9] != 0) && (params[on + 9] < 0)) return neg_inf();  // index as in priors_calc.cpp:391
         for (int i = i0; i < i0 + Nwidth; i++)
             if (sw[i] == 2 && params[i] < 0) return neg_inf();  // Gaussian priors on the width law: positive support only
-        for (long i = 0; i < Np; i++) f = f + (generic_terms ? generic_terms[i] : generic_prior_term(params, Np, pp, sw, i, status));
+        TermSum F;
+        for (long i = 0; i < Np; i++) F.add(generic_terms ? generic_terms[i] : generic_prior_term(params, Np, pp, sw, i, status));
         if (model_switch == 1) {  // the v3 models (l=1 p-mode list in the parameter vector): not built here
             if (status) *status = TAMCMC_ERR_BAD_MODEL;
             return neg_inf();
@@ -353,11 +385,11 @@ TM_HD xreal prior_serial(int prior_class, const double *params, const int *pl, l
         // smoothness of the l=0 and l=3 ladders.  The reference switches it on the prior id of parameter i0+Nwidth -- the loop
         // variable left over from the width check above (priors_calc.cpp:466; most likely meant extra_priors[0]) -- kept as is.
         if (sw[on] == 1) {
-            for (int i = 0; i < Nfl0; i++) f = f + logP_gaussian(0, scoef, second_difference(params + Nmax + lmax, Nfl0, i));
+            for (int i = 0; i < Nfl0; i++) F.add(logP_gaussian(0, scoef, second_difference(params + Nmax + lmax, Nfl0, i)));
             for (int i = 0; i < Nfl3; i++)
-                f = f + logP_gaussian(0, scoef, second_difference(params + Nmax + lmax + Nfl0 + Nfl1 + Nfl2, Nfl3, i));
+                F.add(logP_gaussian(0, scoef, second_difference(params + Nmax + lmax + Nfl0 + Nfl1 + Nfl2, Nfl3, i)));
         }
-        return f;
+        return F.value();
     }
     if (status) *status = TAMCMC_ERR_BAD_MODEL;
     return neg_inf();
