@@ -89,8 +89,20 @@ extern "C" {
 /* STRICT: per-bin operation order of the reference (IEEE divides, no FMA contraction): the model row is
  *         bit-identical to the CPU restatement when the Harvey pow() terms are inactive.
  * FAST  : same function, re-associated (common-denominator multiplet sum, reciprocal+Newton, exp/log Harvey) and,
- *         for multiplets far from a tile, summed as ONE degree-15 polynomial per tile (truncation <= 8^-16 of the far
- *         term); stated tolerance: |dM|/M <= 1e-12 per bin, |dlogL|/|logL| <= 1e-11. */
+ *         for multiplets far from a tile, summed as ONE degree-15 polynomial per tile.  A multiplet is far when its window
+ *         covers the tile and rho = beta / sqrt(A_m^2 + 1) <= 1/6 for every component (1/8 for a multiplet with asymmetry;
+ *         beta = tile half-width x 2/gamma, A_m = (nu_m - tile centre) x 2/gamma).  Stated tolerance, per bin:
+ *             FAST_DIRECT  |dM| <= 1e-12 M
+ *             FAST         |dM| <= 1e-12 M + tau_far F(x) + tau_asym F_asym(x)
+ *         with F (F_asym) the sum of the far components without (with) asymmetry at the bin.  tau_far = rho^16 (17 + 16 rho) at
+ *         rho = 1/6 = 6.96e-12: in its wing a Lorentzian is a DOUBLE pole, hv / (A^2 (1 - rho s)^2), whose series loses
+ *         rho^n (n + 1 + n rho) of the term after n coefficients (reached at the gate when the tile lies deep in the wing of one
+ *         component; the simple-pole figure 6^-16 / (1 - 1/6) = 4e-13 quoted here before omitted the factor 17).  tau_asym =
+ *         2.8e-12, four times the measured worst case (the asymmetry factor can come close to zero on a tile far from nu_c, and
+ *         relative to the term the coefficients' rounding then counts; 3.6e-15 at the tile centre).  The background joins the
+ *         polynomial on tiles where its series keeps 2.3e-13 of every Harvey term (csrc/bg_series.h), inside the 1e-12 M.
+ *         |dlogL|/|logL| <= 1e-11 in both FAST modes.  Pinned by tests/test_tile_bounds.py (CPU, against a 50-digit reference)
+ *         and tests/test_gpu_tile_reference.py. */
 #define TAMCMC_PRECISION_STRICT 0
 #define TAMCMC_PRECISION_FAST 1        /* far-field expansion per tile + direct near field */
 #define TAMCMC_PRECISION_FAST_DIRECT 2 /* FAST arithmetic, every component evaluated per bin (no far field) */

@@ -151,13 +151,14 @@ __device__ inline void wg_bg_tiles(const ModelDesc &d, const double *s_params, c
     const double *np_ = s_params + S->L.o_noise;
     const int nh = S->nharvey, nn = S->L.Nnoise;
     if (t_hi > T.ntiles) t_hi = T.ntiles;
+    const auto at = [np_](int i) { return fabs(np_[i]); };
+    const double pmax = bg::gate_coef(bg::max_exponent(at, nh));  // C(p_max+7, 8) of the gate
     if (tid >= first && tid < first + nw)
         for (int t = t_lo + tid - first; t < t_hi; t += nw) {
             double xc, h;
             bg::tile_geometry(t, T.tile_bins, d.x_first, d.step, xc, h);
-            if (!bg::series_valid(xc, h)) continue;
             double o[bg::NH];
-            bg::tile_series([np_](int i) { return fabs(np_[i]); }, nh, nn, xc, h, o);
+            if (!bg::prebuilt_series(at, nh, nn, xc, h, pmax, o)) continue;
             double *dst = T.bg + ((size_t)slot * T.ntiles + t) * bg::NH;
 #pragma unroll
             for (int k = 0; k < bg::NH; k++) dst[k] = o[k];

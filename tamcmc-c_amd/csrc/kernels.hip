@@ -54,10 +54,10 @@ __global__ void __launch_bounds__(WG) k_bg_poly(const double *noise, int noise_s
     if (nn <= 0) return;
     double xc, h;
     bg::tile_geometry(tile, tile_bins, x0, step, xc, h);
-    if (!bg::series_valid(xc, h)) return;
     const double *nz = noise + (size_t)b * noise_stride;
+    const auto at = [nz](int i) { return nz[i]; };
     double o[NH];
-    bg::tile_series([nz](int i) { return nz[i]; }, nharvey[b], nn, xc, h, o);
+    if (!bg::prebuilt_series(at, nharvey[b], nn, xc, h, bg::gate_coef(bg::max_exponent(at, nharvey[b])), o)) return;
 #pragma unroll
     for (int k = 0; k < NH; k++) out[(size_t)id * NH + k] = o[k];
 }

@@ -26,11 +26,21 @@ constexpr int M_STRICT = 0, M_FAST_DIRECT = 2, M_FAST = 1;
 // half-widths away from the tile centre is an analytic function of x on the tile; the sum of ALL such multiplets is ONE
 // polynomial of degree NC-1 in s = (x - x_c)/h, evaluated per bin by Horner (NC-1 fma) instead of ~6 ops per component.
 // Component: hv/(1+(beta s - A)^2) = sum_k c_k s^k, c_k = -hv Im(u q^k), u = 1/(A+i), q = beta u, |q| = rho, with the
-// three-term recurrence c_{k+1} = 2 Re(q) c_k - |q|^2 c_{k-1}.  Truncation error <= rho^NC/(1-rho) of the (small) far term.
+// three-term recurrence c_{k+1} = 2 Re(q) c_k - |q|^2 c_{k-1}.
+// Truncation.  Deep in the wing (A >> 1) the component is hv / (A^2 (1 - rho s)^2), a DOUBLE pole with c_k ~ (k+1) rho^k: after n
+// coefficients the series lacks tau(rho, n) = rho^n (n + 1 + n rho) of the far term (at s = -1, the end of the tile away from the
+// mode; n + 1 - n rho at s = +1), and for smaller A no more.  At the gate: tau_far = tau(1/6, 16) = 6.96e-12 of the far term -- which
+// may be all of M on a tile in the wing of one tall, broad mode -- not the simple pole's rho^NC / (1 - rho) = 4e-13 this line quoted
+// before.  FAST states |dM| <= 1e-12 M + tau_far F per bin, F the sum of the far components (include/tamcmc_hip.h); logL keeps 1e-11.
+// The gate is not tightened: rho <= 1/7 would move about a sixth more components into the per-bin loop (estimated at C3, not measured).
+// The early stop of far_coefs keeps every shorter loop inside tau_far: tau(sqrt(1.39e-2), 14) = 1.7e-12 .. tau(sqrt(4.6e-5), 6) = 6.9e-13.
+// tests/test_tile_bounds.py pins NC, both radii and the early-stop table against a 50-digit reference.
 constexpr int NC = 16;
-constexpr double RHO_MAX2 = 1.0 / 36.0;  // rho <= 1/6 -> truncation <= 6^-16/(1-1/6) = 4e-13 of the far term (itself <~ 0.3 M)
-constexpr double RHO_MAX2_ASYM = 1.0 / 64.0;  // asymmetric profiles: the far wing can dominate M and the quadratic
-                                              // factor feeds degree >= NC terms back -> rho <= 1/8 (3.6e-15)
+constexpr double RHO_MAX2 = 1.0 / 36.0;  // rho <= 1/6 -> truncation <= tau_far = 6.96e-12 of the far term
+constexpr double RHO_MAX2_ASYM = 1.0 / 64.0;  // asymmetric profiles: the far wing can dominate M and the quadratic factor feeds degree >= NC
+                                              // terms back -> rho <= 1/8: truncation tau(1/8, 16) = 6.8e-14 of the term; where the factor
+                                              // comes close to zero on the tile the coefficients' rounding counts more, measured
+                                              // 6.9e-13 of the term at worst (3.6e-15 at A = 0); stated tau_asym = 2.8e-12
 constexpr int NH = bg::NH;               // Taylor coefficients of the background on a tile (bg_series.h)
 constexpr int ROW = NC + 2;  // LDS row stride of the coefficient reduction (16-byte aligned, conflict-free b128 writes)
 
@@ -263,7 +273,7 @@ __device__ __forceinline__ FarSeed far_seed(double hv, double A, double beta) {
     const double inv = rcp_nr2(fma(A, A, 1.0));
     return {hv * inv, 2.0 * beta * A * inv, beta * beta * inv};
 }
-// fc[k] += c_k.  EARLY_STOP (the caller's choice; the whole wave must be here): terms beyond rho^n <= 1e-13 are dropped, the wave's longest loop runs
+// fc[k] += c_k.  EARLY_STOP (the caller's choice; the whole wave must be here): n coefficients where rho^n <= 1e-13, i.e. tau(rho, n) <= 1.7e-12 (above), the wave's longest loop runs
 template <bool EARLY_STOP>
 __device__ __forceinline__ void far_coefs(const FarSeed &f, double (&fc)[NC]) {
     double cm = f.c0, cc = cm * f.two_req;  // c_0, c_1
@@ -316,7 +326,7 @@ struct __attribute__((aligned(16))) TileLds {
     double red[2 * (WGS / 64)];
     double lt[TAMCMC_MAX_HARVEY];  // FAST: ln(1e-3*tau_k)
     double lto[TAMCMC_MAX_HARVEY]; // DELTA: ln(1e-3*tau_k) of the base point
-    int n, nfar, anyfar;
+    int n, nfar, anyfar;           // anyfar: bit 0 = the tile polynomial is in use, bit 1 = the prebuilt background series came refused (bg_series.h)
     unsigned short slot[CHUNK * 7];  // FARFIELD: this chunk's far COMPONENTS, packed: (position in the list) << 3 | m
 };
 
@@ -591,6 +601,11 @@ __device__ __forceinline__ bool delta_moment_shortcut(const LoglikeArgs &a, cons
     return true;
 }
 
+// (rare, and out of line: inlined, the logarithm's temporaries would count against the tile's register budget)
+__device__ __attribute__((noinline)) inline void refused_logs(double *s_lt, const double *nz, int nh, int tid) {
+    for (int hh = tid; hh < nh; hh += NH) s_lt[hh] = log(1e-3 * nz[3 * hh + 1]);
+}
+
 // One tile of one evaluation: table slot `sb` (its multiplets, noise row, background series), result row `b` (partials / model).
 // xpre (may be null): the lane's K values of x, requested by a caller that had something to wait for first (loglike_tile).
 template <int MODE, int WGS, int K, bool WRITE_MODEL, bool DELTA, class Hook>
@@ -647,7 +662,18 @@ __device__ __forceinline__ void tile_compute(const LoglikeArgs &a, const int til
     bg::tile_geometry(tile, TILE, a.x0, a.step, xc, h);
     // FARFIELD: the background H/(1+(a x)^p) + N0 is analytic on the tile with its singularities ~x_c away, so it joins the
     // tile polynomial: u(s) = (a x_c)^p (1+eps s)^p (binomial series), then the reciprocal series of 1+u.
-    const bool harvey_poly = FARFIELD && bg && bg::series_valid(xc, h);
+    // The gate also looks at the steepest exponent of the evaluation's terms (of both noise rows where a DELTA evaluation subtracts the
+    // old one).  With a prebuilt series its builder has applied that part -- here only the geometry, nothing to wait for -- and a tile it
+    // refused comes marked: the polynomial then takes zeros for it (bg_mark) and the likelihood terms add the background per bin (series_on).
+    bool harvey_poly = false;
+    if (FARFIELD && bg) {
+        if (bg_prebuilt) harvey_poly = bg::series_geometry(xc, h);
+        else {
+            double pmax = bg::max_exponent([nz](int i) { return nz[i]; }, nh);
+            if (dsub) pmax = fmax(pmax, bg::max_exponent([nzo](int i) { return nzo[i]; }, nh));
+            harvey_poly = bg::series_valid(xc, h, bg::gate_coef(pmax));
+        }
+    }
     if (FAST && bg && !harvey_poly) {
         if (tid < nh) {
             s_lt[tid] = log(1e-3 * nz[3 * tid + 1]);
@@ -689,6 +715,8 @@ __device__ __forceinline__ void tile_compute(const LoglikeArgs &a, const int til
 
     // the table builder already summed the series of this (evaluation, tile) (bg_series.h, same arithmetic): still in registers
     bool bg_in_regs = harvey_poly && bg_prebuilt;
+    // a series its builder refused (bg_series.h, NaN in every coefficient): the polynomial takes zeros for the background
+    const auto bg_mark = [](double c) { return bg::refused(c) ? 0.0 : c; };
     bool any_near = false;  // (workgroup-uniform) a chunk held a multiplet of the near field
     probe.stamp(1);
     for (int c0 = mbeg; c0 < mend; c0 += CHUNK) {
@@ -735,7 +763,7 @@ __device__ __forceinline__ void tile_compute(const LoglikeArgs &a, const int til
             }
             __syncthreads();
             if (tid < NC) {
-                double sum = (bg_in_regs && tid < NH) ? bg_pre : s_coef[tid];  // background first, then the parts: the order of the sum
+                double sum = (bg_in_regs && tid < NH) ? bg_mark(bg_pre) : s_coef[tid];  // background first, then the parts: the order of the sum
 #pragma unroll
                 for (int p = 0; p < WGS / 16; p++) sum = sum + s_part[p][tid];
                 s_coef[tid] = sum;
@@ -743,12 +771,17 @@ __device__ __forceinline__ void tile_compute(const LoglikeArgs &a, const int til
             bg_in_regs = false;
         }
     }
-    if (bg_in_regs && tid < NH) s_coef[tid] = bg_pre;  // (no far multiplet on this tile: the polynomial is the background alone)
+    if (bg_in_regs && tid < NH) s_coef[tid] = bg_mark(bg_pre);  // (no far multiplet on this tile: the polynomial is the background alone)
+    if (FARFIELD && bg_prebuilt && harvey_poly && tid < NH && bg::refused(bg_pre)) {  // rare: the per-bin background after all -- the lanes
+        if (tid == 0) s_anyfar = 3;                                                    // that hold the series mark the tile and set up its logs
+        refused_logs(s_lt, nz, nh, tid);
+    }
     probe.stamp(4);
     // the power values: issued before the polynomial evaluation, consumed after it
 #pragma unroll
     for (int k = 0; k < K; k++) yv[k] = DELTA ? 0.0 : a.y[min(bin[k], a.Nx - 1)];  // (DELTA: y enters through the base point's y/M0 plane)
     if (FAST) __syncthreads();  // s_lt / s_coef visible (also when the evaluation has no multiplet chunk)
+    const bool series_on = harvey_poly && !(FARFIELD && (s_anyfar & 2));  // (workgroup-uniform)
     if constexpr (DELTA && FARFIELD && WGS == 64) {
         // A tile whose changed multiplets are ALL in its far field (most tiles of a perturbed frequency's window: the mode is near for
         // three or four of a hundred) has dM = P(s), the tile polynomial, with |u| = |dM / M0| ~ 1e-7 of a far wing: the change of its
@@ -765,7 +798,7 @@ __device__ __forceinline__ void tile_compute(const LoglikeArgs &a, const int til
     probe.stamp(5);
     // ---- background + likelihood terms ----
     double s[2] = {0.0, 0.0};
-    likelihood_terms<MODE, K, WRITE_MODEL, DELTA>(a, b, nh, nn, nz, nzo, bg, harvey_poly, dsub, fullnew, s_lt, s_lto, xv, yv, bin, acc, probe, s);
+    likelihood_terms<MODE, K, WRITE_MODEL, DELTA>(a, b, nh, nn, nz, nzo, bg, series_on, dsub, fullnew, s_lt, s_lto, xv, yv, bin, acc, probe, s);
     __syncthreads();
     reduce_and_store<WGS>(a, s, s_red, b, tile, hook);
     probe.stamp(6);

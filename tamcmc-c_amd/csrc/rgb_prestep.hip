@@ -413,12 +413,13 @@ __global__ void __launch_bounds__(WG) k_rgb_finish(const Prep *preps, const RowI
     if (bg.out) {  // the vector's background series per likelihood tile (k_bg_poly's arithmetic; the noise row is in place since the proposal kernel)
         const int nn = bg.nn[e];
         const double *nz = bg.noise + (size_t)e * bg.stride;
+        const auto at = [nz](int i) { return nz[i]; };
+        const double pmax = nn > 0 ? bg::gate_coef(bg::max_exponent(at, bg.nh[e])) : 0.0;  // C(p_max+7, 8) of the gate
         for (int tile = tid; nn > 0 && tile < bg.ntiles; tile += WG) {
             double xc, h;
             bg::tile_geometry(tile, bg.tile_bins, bg.x0, bg.step, xc, h);
-            if (!bg::series_valid(xc, h)) continue;
             double o[bg::NH];
-            bg::tile_series([nz](int i) { return nz[i]; }, bg.nh[e], nn, xc, h, o);
+            if (!bg::prebuilt_series(at, bg.nh[e], nn, xc, h, pmax, o)) continue;
             for (int k = 0; k < bg::NH; k++) bg.out[((size_t)e * bg.ntiles + tile) * bg::NH + k] = o[k];
         }
     }

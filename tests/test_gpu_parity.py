@@ -400,29 +400,10 @@ def test_many_multiplets_multiple_chunks(pkg, oracle, synth, ctxs):
     assert np.all(np.abs(g_w - g_f) <= 5e-14 * x.size / h + 1e-6 * np.max(np.abs(g_f)))
 
 
-def _numpy_table_model(x, mults, noise, nh):
-    """The path's arithmetic written out in numpy (build_lorentzian.cpp:131-246 per component on its window, noise_models.cpp:15-39)."""
-    m = np.zeros_like(x)
-    for r in mults:
-        sl = slice(int(r["i0"]), int(r["i1"]))
-        xs = x[sl]
-        res = np.zeros_like(xs)
-        for k in range(2 * int(r["l"]) + 1):
-            u = 4.0 * (xs - r["nu"][k]) ** 2 / r["gamma"] ** 2
-            prof = r["hv"][k] / (1.0 + u)
-            if r["asym"] != 0.0:
-                prof = prof * ((1.0 + r["asym"] * (xs / r["fc"] - 1.0)) ** 2 + (0.5 * r["gamma"] * r["asym"] / r["fc"]) ** 2)
-            res += prof
-        m[sl] += res
-    for k in range(nh):
-        if noise[3 * k + 1] != 0:
-            m += noise[3 * k] / (1.0 + (1e-3 * noise[3 * k + 1] * x) ** noise[3 * k + 2])
-    return m + noise[-1]
-
-
 @pytest.mark.parametrize("nx", [3, 64, 511, 512, 513, 1025, 4097])
 def test_random_tables_on_awkward_grids(pkg, ctxs, nx):
-    """Table-level entry (tamcmc_hip_loglike_batch) against the formula written out in numpy: grids shorter than a wave, one bin
+    """Table-level entry (tamcmc_hip_loglike_batch) against the longdouble twin of the 50-digit reference (tile_reference.py), with the
+    per-bin assertions of test_gpu_tile_reference.py: grids shorter than a wave, one bin
     either side of a tile boundary, windows clipped at both ends or one bin wide, zero to 150 multiplets per evaluation (more than
     one staging chunk), widths from a fraction of a bin to the whole grid, asymmetric profiles, 0-3 Harvey terms, several
     evaluations of different lengths in one launch -- all three arithmetic modes and both kernel geometries."""
@@ -459,15 +440,21 @@ def test_random_tables_on_awkward_grids(pkg, ctxs, nx):
     mults = np.concatenate(tabs)
     noise = np.stack(noises)
     nn = [3 * h + 1 for h in nhs]
-    ref_m = np.stack([_numpy_table_model(x, tabs[b], noises[b][:nn[b]], nhs[b]) for b in range(B)])
-    y = ref_m[2] * rng.exponential(1.0, nx)
+    import tile_reference as tr
+    from test_gpu_tile_reference import check_logl, check_rows
+    ref_m = [tr.model_row_ld(tabs[b], noises[b], nhs[b], nn[b], x) for b in range(B)]
+    y = (ref_m[2] * rng.exponential(1.0, nx)).astype(np.float64)
     T = 1.3 ** np.arange(B)
-    ref_l = np.array([-(y / ref_m[b] + np.log(ref_m[b])).sum() / T[b] for b in range(B)])
-    for name, tol_m, tol_l in (("strict", 1e-12, 1e-12), ("fast_direct", 1e-11, 1e-11), ("fast", 1e-10, 1e-10)):
-        for wg in (64, 256):
+    ref_l = [tr.loglike_ld(ref_m[b], y, T[b], 1) for b in range(B)]
+    for wg, tile_bins in ((64, 512), (256, 1024)):   # (the workgroup size picks its default bins per thread: 8 and 4)
+        out = {}
+        for name in ("strict", "fast_direct", "fast"):
             c = ctxs[name]
             c.set_option(pkg.OPT_WORKGROUP, wg)
             c.set_spectrum(x, y)
-            logL, model = c.loglike_batch(mults, np.array(offsets, dtype=np.int32), noise, nhs, nn, T, 1.0, want_model=True)
-            assert np.max(np.abs(model - ref_m) / ref_m) < tol_m, (name, wg, np.max(np.abs(model - ref_m) / ref_m))
-            assert np.allclose(logL, ref_l, rtol=tol_l, atol=1e-9), (name, wg, logL, ref_l)
+            out[name] = c.loglike_batch(mults, np.array(offsets, dtype=np.int32), noise, nhs, nn, T, 1.0, want_model=True)
+        for b in range(B):
+            F, Fa = tr.far_abs_sum(tabs[b], x, tile_bins, float(x[0]), float(x[1] - x[0])) if tabs[b].size else (np.zeros(nx, tr.LD),) * 2
+            label = "nx %d wg %d evaluation %d" % (nx, wg, b)
+            check_rows(label, {k: v[1][b] for k, v in out.items()}, ref_m[b], F, Fa)
+            check_logl(label, {k: v[0][b] for k, v in out.items()}, ref_l[b])
