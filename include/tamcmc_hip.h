@@ -139,7 +139,11 @@ extern "C" {
 #define TAMCMC_OPT_RGB_DEVICE_LANGEVIN 11 /* value: 0/1 (default 0) -- 1: tamcmc_sampler_create builds the device-resident engine's Langevin
                                         sampler (engine = 1, use_drift = 1) for the red-giant models, ids 25 and 27; 0: it refuses them
                                         with TAMCMC_ERR_BAD_MODEL.  Read when the sampler is created: changing it afterwards does not
-                                        affect an existing sampler.  FAST arithmetic and TAMCMC_GRADIENT_FD only (tamcmc_sampler.h) */
+                                        affect an existing sampler.  FAST arithmetic; TAMCMC_GRADIENT_FD, or TAMCMC_GRADIENT_ADJOINT with
+                                        TAMCMC_OPT_RGB_ADJOINT = 1 (tamcmc_sampler.h) */
+#define TAMCMC_OPT_RGB_ADJOINT 12     /* value: 0/1 (default 0) -- 1: with TAMCMC_OPT_GRADIENT = TAMCMC_GRADIENT_ADJOINT the red-giant models, ids 25
+                                        and 27, take the hybrid adjoint batch (see tamcmc_hip_adjoint_table) instead of being refused.  Read at
+                                        every call, like TAMCMC_OPT_GRADIENT; nothing else changes with it.  Any other value: TAMCMC_ERR_BAD_ARG */
 #define TAMCMC_FISHER_SLAB 2048     /* bins per workgroup (and per partial matrix) of the Gram kernel of tamcmc_hip_fisher / _weighted_gram */
 
 /* One (n,l) multiplet: <=7 Lorentzian m-components on its truncation window.
@@ -292,9 +296,42 @@ int tamcmc_hip_fd_gradient_posterior(tamcmc_hip_ctx *ctx, int model_id, int prio
  * The audit entry: G [C x *nrows x 17] and Gn [C x max(plength[8], 1)] of the C parameter vectors, for the UN-tempered S (Tcoefs and p are
  * accepted for symmetry and not read: logL = -p S / T).  *nrows = rows per table.  Runs under the adjoint route whatever the option says;
  * entries of rows a table does not have, of components m >= 2l+1 and, where asym = 0, of asym and fc are 0.  A vector whose table fails
- * makes the call return that status; its G and Gn are 0.  G, Gn, nrows may be NULL. */
+ * makes the call return that status; its G and Gn are 0.  G, Gn, nrows may be NULL.
+ *
+ * Red giants (ids 25, 27) with TAMCMC_OPT_RGB_ADJOINT = 1: the HYBRID batch.  A red-giant table is the l=0 list, the l=1 mixed modes in
+ * frequency order, then the l=2 and l=3 lists, and a perturbation may change the set of mixed modes: every later row then shifts and a
+ * row-by-row contraction means nothing.  So every perturbed slot is classified on the device (csrc/adj_rgb_match.h).  It is LINEARISABLE
+ * when its status and the base's are TAMCMC_OK, it has the base table's row count, every row has the base row's l, and every l=1 row's fc
+ * lies within half the distance from the base row's fc to that row's nearest l=1 neighbour in the base table (a set that lost one mode and
+ * gained another keeps its count and fails this).  A linearisable slot's difference is the contraction above; every other slot with two valid
+ * tables is a FALLBACK slot and takes the windowed finite difference (tamcmc_hip_fd_gradient: delta table against the stored base point),
+ * bit for bit what the windowed route gives for that component; a slot with a failed table gives NaN and the status, as there.  The base
+ * launch is the windowed route's: logL0 is its bits, and the prior's share is the finite-difference route's bits.  Same determinism as
+ * above.  FAST or FAST_DIRECT with a workgroup geometry that has the windowed route (256 x 4, 64 x 8, 64 x 4: others return
+ * TAMCMC_ERR_BAD_ARG); STRICT returns TAMCMC_ERR_BAD_ARG; tamcmc_hip_fisher keeps refusing the ids.  With the option at 0 the ids are
+ * refused as before.
+ * Tolerance of a linearisable component: G and Gn as above, within 1e-11 of their absolute sums A, An, carried through the contraction with
+ * the batch's own tables (tamcmc_hip_rgb_batch_tables):
+ *   |d grad_k| <= (p/T)/|h_applied| 1e-11 [sum_rows sum_f A[row][f] |dT[row].f| + sum_j An[j] |d noise_j|];
+ * the tables themselves carry the red-giant tolerance above.  The forward table Jacobian adds the curvature of the mixed-mode frequencies
+ * in the period spacing, the coupling and the large separation: against the frozen-window central difference the gradient lies within
+ * 3 R + J, R that reference's |g(h) - g(h/2)| and J the distance between the adjoint with the forward and with the central table Jacobian
+ * (tests/test_gpu_rgb_adjoint.py; sizes in DESIGN section 9).
+ * This entry then accepts the ids: G [C x *nrows x 17] with *nrows = the rows RESERVED per table (Nfl0 + Nfl2 + Nfl3 + 400) and zeros
+ * beyond a table's own rows. */
 int tamcmc_hip_adjoint_table(tamcmc_hip_ctx *ctx, int model_id, int C, const double *params, int64_t Nparams, const int32_t *plength,
                              const double *Tcoefs, double p, double *G, double *Gn, int *nrows);
+
+/* Audit entry of the red-giant gradient batches (ids 25, 27; others: TAMCMC_ERR_BAD_MODEL): the tables of the B = C x (Nvars + 1) vectors
+ * of a batch -- slot c (Nvars + 1) is chain c's vector, slot c (Nvars + 1) + 1 + k the same with hstep[k] added to index_to_relax[k] --
+ * after the batch's own table builder and nothing else: the very bits every route of tamcmc_hip_fd_gradient goes on from (the host cannot
+ * build a red-giant table: tamcmc_build_mode_table refuses the ids).  Same params, index_to_relax and hstep as tamcmc_hip_fd_gradient; any
+ * arithmetic mode (STRICT: the host's long-double unpack, as there).
+ * Out (any may be NULL): *per = rows reserved per slot; rows [B x *per] (a slot's first nrows[slot] rows are its table); noise
+ * [B x max(plength[8], 1)], nharvey [B], nnoise [B]; status [B].  Call with C = 0 for *per.  Returns the first status that is not TAMCMC_OK. */
+int tamcmc_hip_rgb_batch_tables(tamcmc_hip_ctx *ctx, int model_id, int C, const double *params, int64_t Nparams, const int32_t *plength,
+                                const int32_t *index_to_relax, int Nvars, const double *hstep, tamcmc_multiplet *rows, int32_t *nrows,
+                                double *noise, int32_t *nharvey, int32_t *nnoise, int32_t *status, int *per);
 
 /* Expected (Fisher) information of the chi^2(2p) likelihood at each of the C parameter vectors:
  *   F_jk = (p / T_c) sum_i (d_j M_i)(d_k M_i) / M0_i^2,   j, k over the Nvars free variables (index_to_relax), the sum over all bins,
@@ -341,6 +378,13 @@ int tamcmc_hip_get_fd_stats(tamcmc_hip_ctx *ctx, int64_t *affected_bins, int64_t
  * the asymmetry) is evaluated as the whole perturbed table minus the stored base model row instead of +new / -old row pairs
  * (FAST arithmetic only; same tolerance as the pair tables: the unchanged rows cancel exactly). */
 int tamcmc_hip_get_fd_full_tables(tamcmc_hip_ctx *ctx, int64_t *full_table_evaluations);
+/* Hybrid red-giant adjoint batches (TAMCMC_OPT_RGB_ADJOINT, timing enabled): since the last reset, the perturbed slots of the gradient
+ * calls (host entries and both samplers' Langevin steps) that were contracted and that fell back to the windowed difference; slots with a
+ * failed table are in neither. */
+int tamcmc_hip_get_rgb_adjoint_stats(tamcmc_hip_ctx *ctx, int64_t *linearised_slots, int64_t *fallback_slots);
+/* ... and the HIP-event split of the last such batch of a host entry, ms6 = table build (with the classification), base launch, row pass,
+ * noise pass + folds, fallback delta launches (moments, far-only tiles, DELTA launch, its fold), contraction (milliseconds). */
+int tamcmc_hip_get_rgb_adjoint_times(tamcmc_hip_ctx *ctx, double *ms6);
 
 #ifdef __cplusplus
 }

@@ -88,8 +88,14 @@ int64_t tamcmc_sampler_nvars(const tamcmc_sampler *s);
  *                                  tamcmc_sampler_run on a STRICT context returns TAMCMC_ERR_BAD_ARG (the long-double unpack STRICT
  *                                  promises is the host's, and the proposals never leave the device), under TAMCMC_GRADIENT_ADJOINT
  *                                  TAMCMC_ERR_BAD_MODEL; either way the chains stay where they were and a later call continues them.
+ *                                  With TAMCMC_OPT_RGB_ADJOINT = 1 (read at every call) TAMCMC_GRADIENT_ADJOINT is accepted by both
+ *                                  engines: the hybrid batch of tamcmc_hip.h (tamcmc_hip_adjoint_table) -- the table-space adjoint for
+ *                                  the perturbed vectors whose rows correspond one to one with the base table's (same count, same l,
+ *                                  every l=1 row within half the distance to its nearest l=1 neighbour), the windowed finite difference
+ *                                  for the others; tolerances there.  A sampler whose options change between two calls continues its
+ *                                  chain from a gradient taken on the new route.
  *                                  Nchains (Nvars + 1) <= 65535.  Host-driven engine: random walk or Langevin, any arithmetic mode
- *                                  (tamcmc_hip_fd_gradient_posterior)
+ *                                  (tamcmc_hip_fd_gradient_posterior; the adjoint routes: FAST / FAST_DIRECT)
  *   Gaussian-envelope models       host-driven engine only (random walk or Langevin); engine = 1 -> TAMCMC_ERR_BAD_MODEL at
  *     (ids 0/1)                    tamcmc_sampler_create
  *   tamcmc_sampler_seed_proposal   models 3, 11, 12, 13, 14, 23 on a FAST or FAST_DIRECT context (tamcmc_hip_fisher's refusals: ids 0, 1, 25,

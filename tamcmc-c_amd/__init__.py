@@ -29,6 +29,7 @@ PRECISION_STRICT, PRECISION_FAST, PRECISION_FAST_DIRECT = 0, 1, 2
 OPT_PRECISION, OPT_TIMING, OPT_BINS_PER_THREAD, OPT_WORKGROUP, OPT_FD_WINDOWED, OPT_STEP_SCHEME, OPT_ARMM_DENSE_SCAN = 1, 2, 3, 4, 5, 6, 7
 OPT_GRADIENT, GRADIENT_FD, GRADIENT_ADJOINT = 9, 0, 1  # gradient batches: finite differences (default) / table-space adjoint, frozen windows
 OPT_RGB_DEVICE_LANGEVIN = 11  # 1: Sampler(use_drift=1, engine="device") is built for the red-giant ids 25 / 27 (default 0: ERR_BAD_MODEL); read at creation
+OPT_RGB_ADJOINT = 12  # 1: under GRADIENT_ADJOINT the red-giant ids 25 / 27 take the hybrid adjoint batch (default 0: ERR_BAD_MODEL); read at every call
 OPT_FISHER_WORKSPACE_MB = 10  # MiB of model rows HipContext.fisher keeps on the device per pass (default 2048)
 FISHER_SLAB = 2048  # bins per workgroup of the Gram kernel (TAMCMC_FISHER_SLAB)
 OPT_QUICK_DECIDE = 8  # test facility: 1 = the fused step's decision shortcut always falls back to the exact evaluation
@@ -75,6 +76,10 @@ ABI = [
     ("tamcmc_hip_reset_kernel_stats", C.c_int, [_vp]),
     ("tamcmc_hip_get_fd_stats", C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("tamcmc_hip_get_fd_full_tables", C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    ("tamcmc_hip_rgb_batch_tables", C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int64, _ip, _ip, C.c_int, _dp, _vp, _ip, _dp, _ip, _ip, _ip,
+                                             C.POINTER(C.c_int)]),
+    ("tamcmc_hip_get_rgb_adjoint_stats", C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("tamcmc_hip_get_rgb_adjoint_times", C.c_int, [_vp, _dp]),
 ]
 
 _lib = None
@@ -255,7 +260,8 @@ class HipContext:
 
     def adjoint_table(self, model_id, params, plength, Tcoefs=None, p=1.0):
         """Table-space adjoint of the un-tempered sum S at each row of params (tamcmc_hip_adjoint_table): (G [C x rows x 17], Gn [C x nnoise]),
-        fields of G in the order nu[7], hv[7], gamma, asym, fc."""
+        fields of G in the order nu[7], hv[7], gamma, asym, fc.  Red giants (ids 25 / 27, with OPT_RGB_ADJOINT): rows = the rows reserved
+        per table, zeros beyond a table's own."""
         params = _f64(params)
         if params.ndim == 1:
             params = params[None, :]
@@ -270,6 +276,42 @@ class HipContext:
         self._chk(self._L.tamcmc_hip_adjoint_table(self._h, int(model_id), Cn, _p(params), Np, _p(plength, _ip), _p(T), float(p), _p(G), _p(Gn),
                                                    C.byref(n)))
         return G, Gn
+
+    def rgb_batch_tables(self, model_id, params, plength, index_to_relax, hstep):
+        """The tables of a red-giant gradient batch as its own builder leaves them (tamcmc_hip_rgb_batch_tables), in batch order: slot
+        c (Nvars + 1) is chain c's vector, slot c (Nvars + 1) + 1 + k the same with hstep[k] added to index_to_relax[k].  Returns
+        (tables, noise, nharvey, status): tables[slot] = that slot's rows (MULT_DTYPE), noise[slot] = its |noise| row (nnoise values)."""
+        params = _f64(params)
+        if params.ndim == 1:
+            params = params[None, :]
+        Cn, Np = params.shape
+        plength, idx, h = _i32(plength), _i32(index_to_relax), _f64(hstep)
+        assert h.size == idx.size
+        per = C.c_int(0)
+        args = (int(model_id), _p(params), Np, _p(plength, _ip), _p(idx, _ip), idx.size, _p(h))
+        self._chk(self._L.tamcmc_hip_rgb_batch_tables(self._h, args[0], 0, *args[1:], None, None, None, None, None, None, C.byref(per)))
+        B, stride = Cn * (idx.size + 1), max(int(plength[8]), 1)
+        rows = np.zeros((B, per.value), dtype=MULT_DTYPE)
+        n, nh, nn, status = (np.zeros(B, dtype=np.int32) for _ in range(4))
+        noise = np.zeros((B, stride))
+        st = self._L.tamcmc_hip_rgb_batch_tables(self._h, args[0], Cn, *args[1:], rows.ctypes.data, _p(n, _ip), _p(noise), _p(nh, _ip),
+                                                 _p(nn, _ip), _p(status, _ip), C.byref(per))
+        # a per-vector table failure comes back as the call's code AND in status[slot] (that slot's table is empty): not an exception
+        self._chk(st, tolerate=((int(st),) if (status != OK).any() else ()))
+        return [rows[s, :n[s]].copy() for s in range(B)], [noise[s, :max(nn[s], 0)].copy() for s in range(B)], nh, status
+
+    def rgb_adjoint_stats(self):
+        """(linearised slots, fallback slots) of the hybrid red-giant adjoint batches since the last reset (timing on)."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._chk(self._L.tamcmc_hip_get_rgb_adjoint_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def rgb_adjoint_times(self):
+        """HIP-event split of the last hybrid batch of a host entry, ms (timing on): table build, base launch, row pass, noise pass +
+        folds, fallback delta launches, contraction."""
+        t = np.zeros(6)
+        self._chk(self._L.tamcmc_hip_get_rgb_adjoint_times(self._h, _p(t)))
+        return tuple(t)
 
     def fisher(self, model_id, params, plength, index_to_relax, hstep, Tcoefs=None, p=1.0):
         """Expected (Fisher) information F [C x Nvars x Nvars] of the likelihood at each row of params (tamcmc_hip_fisher): central

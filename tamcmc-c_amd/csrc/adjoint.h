@@ -31,10 +31,17 @@ struct AdjArgs {
     double *Gn;              // [C x stride]
     double *npart;           // [C x ntn x stride] per-tile partials of Gn
     int ntn;                 // ceil(Nx / ADJ_NTILE)
+    // Red giants (the hybrid batch of fd_batch.hip), all nullptr / 0 for the fixed-length models:
+    //   cls [slots]: the batch's d_flags; a perturbed slot without ADJ_RGB_FLAG_LINEAR (adj_rgb_match.h) is a fallback slot, whose
+    //   difference k_adj_contract copies from fall [slots] (the DELTA launch's sums) instead of contracting
+    const int *cls = nullptr;
+    const double *fall = nullptr;
+    unsigned long long *counts = nullptr;  // (optional) [2]: perturbed slots k_adj_contract contracted / took from `fall`, added up over the launches
 };
 
-// G and Gn of the C base tables (k_adj_rows, k_adj_noise and the fixed-order sums of their segments / tiles)
-hipError_t launch_adjoint(const AdjArgs &a, hipStream_t st);
+// G and Gn of the C base tables (k_adj_rows, k_adj_noise and the fixed-order sums of their segments / tiles).  ev (optional, 2 events):
+// recorded after the row pass and after the noise pass + fold
+hipError_t launch_adjoint(const AdjArgs &a, hipStream_t st, hipEvent_t *ev = nullptr);
 // dS[slot] = sum_rows sum_f G (T_slot.f - T_base.f) + sum_j Gn (noise_slot[j] - noise_base[j]) for every slot of the batch (0 for a base
 // slot, NaN where either table failed): what the DELTA launch of the windowed route leaves in the same place
 hipError_t launch_adjoint_contract(const AdjArgs &a, double *dS, hipStream_t st);

@@ -1,11 +1,13 @@
 // adjoint.hip -- the three kernels of the adjoint gradient (adjoint.h): k_adj_rows, k_adj_noise (+ k_adj_fold, the ordered sum of their
 // segments and tiles) and k_adj_contract.  No atomics: every sum has one fixed order (lane-strided bins, a wave64 __shfl_down tree, the waves in order
 // through LDS, segments and tiles in order), so two calls give the same bits and a chain's result does not depend on the batch around it.
+// (The one atomicAdd, in k_adj_contract, counts slots for the hybrid red-giant batch's statistics: integers, read by the host only.)
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "adjoint.h"
+#include "adj_rgb_match.h"
 
 namespace tamcmc {
 namespace {
@@ -182,6 +184,14 @@ __global__ void __launch_bounds__(64) k_adj_contract(const AdjArgs a, double *dS
         if (lane == 0) dS[slot] = NAN;
         return;
     }
+    if (a.cls) {
+        const bool lin = a.cls[slot] & ADJ_RGB_FLAG_LINEAR;
+        if (a.counts && lane == 0) atomicAdd(&a.counts[lin ? 0 : 1], 1ull);  // (integers: the order does not matter)
+        if (!lin) {  // red giants, a fallback slot: the DELTA launch's difference, as it is
+            if (lane == 0) dS[slot] = a.fall[slot];
+            return;
+        }
+    }
     const int n = min(a.pairs[2 * base + 1] - a.pairs[2 * base], a.per);
     const tamcmc_multiplet *Te = a.mults + (size_t)slot * a.per, *T0 = a.mults + (size_t)base * a.per;
     double s = 0.0;
@@ -210,13 +220,15 @@ __global__ void __launch_bounds__(64) k_adj_contract(const AdjArgs a, double *dS
 
 }  // namespace
 
-hipError_t launch_adjoint(const AdjArgs &a, hipStream_t st) {
+hipError_t launch_adjoint(const AdjArgs &a, hipStream_t st, hipEvent_t *ev) {
     if (a.C <= 0 || a.C > 65535 || a.per <= 0 || a.per > 65535 || a.stride <= 0 || a.stride > 3 * 16 + 4 || a.ntn <= 0 || a.nseg <= 0 || !a.G ||
         !a.Gpart || !a.Gn || !a.npart || !a.planes)
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_adj_rows, dim3(a.nseg, a.per, a.C), dim3(AB), 0, st, a);
+    if (ev && hipEventRecord(ev[0], st) != hipSuccess) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_adj_noise, dim3(a.ntn, a.C), dim3(AB), 0, st, a);
     hipLaunchKernelGGL(k_adj_fold, dim3(a.C), dim3(AB), 0, st, a);
+    if (ev && hipEventRecord(ev[1], st) != hipSuccess) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

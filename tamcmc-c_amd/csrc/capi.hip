@@ -71,6 +71,8 @@ void tamcmc_hip_destroy(tamcmc_hip_ctx *c) {
     c->d_rgb.release(); c->h_rgb.release(); c->d_bg.release(); c->d_env.release(); c->d_fisher.release();
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
+    for (hipEvent_t e : c->ev_split)
+        if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -113,6 +115,10 @@ int tamcmc_hip_set_option(tamcmc_hip_ctx *c, int option, int64_t value) {
     case TAMCMC_OPT_RGB_DEVICE_LANGEVIN:
         if (value < 0 || value > 1) return TAMCMC_ERR_BAD_ARG;
         c->rgb_device_langevin = (int)value;
+        return TAMCMC_OK;
+    case TAMCMC_OPT_RGB_ADJOINT:
+        if (value < 0 || value > 1) return TAMCMC_ERR_BAD_ARG;
+        c->rgb_adjoint = (int)value;
         return TAMCMC_OK;
     case TAMCMC_OPT_WORKGROUP:  // sets the workgroup size AND its default bins per thread
         if (value != 64 && value != 256) return TAMCMC_ERR_BAD_ARG;
@@ -402,8 +408,23 @@ int tamcmc_hip_get_fd_full_tables(tamcmc_hip_ctx *c, int64_t *full_table_evaluat
     return TAMCMC_OK;
 }
 
+int tamcmc_hip_get_rgb_adjoint_stats(tamcmc_hip_ctx *c, int64_t *linearised_slots, int64_t *fallback_slots) {
+    if (!c) return TAMCMC_ERR_BAD_ARG;
+    if (linearised_slots) *linearised_slots = c->rgb_adj_lin;
+    if (fallback_slots) *fallback_slots = c->rgb_adj_fallback;
+    return TAMCMC_OK;
+}
+
+int tamcmc_hip_get_rgb_adjoint_times(tamcmc_hip_ctx *c, double *ms6) {
+    if (!c || !ms6) return TAMCMC_ERR_BAD_ARG;
+    for (int i = 0; i < 6; i++) ms6[i] = c->rgb_adj_ms[i];
+    return TAMCMC_OK;
+}
+
 int tamcmc_hip_reset_kernel_stats(tamcmc_hip_ctx *c) {
     if (!c) return TAMCMC_ERR_BAD_ARG;
+    c->rgb_adj_lin = 0;
+    c->rgb_adj_fallback = 0;
     c->kernel_ms = 0;
     c->launches = 0;
     c->evals = 0;

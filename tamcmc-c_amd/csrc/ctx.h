@@ -57,6 +57,7 @@ struct tamcmc_hip_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t ev_split[7] = {};  // stage boundaries of a hybrid red-giant batch (fd_batch.hip; created at the first timed one)
     std::string err;
     // options
     int precision = TAMCMC_PRECISION_STRICT;
@@ -72,6 +73,7 @@ struct tamcmc_hip_ctx {
     int64_t fisher_ws_mb = 2048;  // tamcmc_hip_fisher: budget of the model rows kept on the device per pass, MiB (fd_rgb_chunk.h: fisher_chunk)
     int gradient = TAMCMC_GRADIENT_FD;  // gradient batches: finite differences, or the table-space adjoint with frozen windows (adjoint.h)
     int rgb_device_langevin = 0;  // 1: the device-resident engine builds its Langevin sampler for the red-giant ids (read at sampler creation)
+    int rgb_adjoint = 0;  // 1: under TAMCMC_GRADIENT_ADJOINT the red-giant ids take the hybrid batch (fd_batch.hip; read at every call)
     // resident spectrum
     int64_t Nx = 0;
     std::vector<double> hx;  // host copy of x (table builders need x[0], x[Nx-1], step)
@@ -102,6 +104,8 @@ struct tamcmc_hip_ctx {
     int64_t launches = 0, evals = 0;
     int64_t fd_full_evals = 0;                // ... of which "full table" evaluations (fd_batch.hip)
     int64_t fd_bins = 0, fd_delta_evals = 0;  // windowed finite differences (timing on): bins inside the affected ranges, delta evaluations
+    int64_t rgb_adj_lin = 0, rgb_adj_fallback = 0;  // hybrid red-giant batches (timing on): perturbed slots contracted / sent through the DELTA launch
+    double rgb_adj_ms[6] = {0, 0, 0, 0, 0, 0};  // last hybrid batch of a host entry with timing on: tables, base launch, row pass, noise pass + fold, fallback delta, contraction
 };
 
 namespace tamcmc {

@@ -1061,6 +1061,8 @@ int DevSampler::run_mala(long it0, long n_iter, const char *learn, double *sampl
     }
     FdBatch &fd = I.fd;
     unsigned char *db = I.fd_block.p;
+    fd.count_slots = c->timing && fd.hybrid();  // (hybrid red-giant batches: linearised / fallback slots of this call, counted on the device)
+    if (fd.count_slots) DCHK(hipMemsetAsync(db + fd.o_adjcount, 0, 16, st));
     MalaArgs M = I.mala;
     M.S = I.fd_S.p; M.lpp = (const double *)(db + fd.o_lpp); M.lpm = (const double *)(db + fd.o_lpm); M.st = (const int *)(db + fd.o_st);
     M.h = (double *)(db + fd.o_h); M.E = fd.E; M.deltas = fd.deltas() ? 1 : 0; M.fd_step_rel = I.fd_step_rel; M.delta = I.delta;
@@ -1131,6 +1133,12 @@ int DevSampler::run_mala(long it0, long n_iter, const char *learn, double *sampl
     DCHK(hipGetLastError());
     DCHK(copy_records(samples, stats, a, (size_t)n_iter, st));
     DCHK(hipStreamSynchronize(st));
+    if (fd.count_slots) {
+        long lin = 0, fall = 0;
+        DCHK(fd.hybrid_stats(c, db, &lin, &fall));
+        c->rgb_adj_lin += lin;
+        c->rgb_adj_fallback += fall;
+    }
     if (n_timed) {  // (the sampled batches stand for all of them)
         c->kernel_ms += kernel_ms / n_timed * n_iter;
         c->launches += n_iter;

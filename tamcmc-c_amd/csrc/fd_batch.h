@@ -18,6 +18,12 @@ struct FdBatch {
     int64_t Np = 0;
     Route route = Route::Brute;
     bool deltas() const { return route == Route::Windowed || route == Route::Adjoint; }  // S = C base sums, then B differences against them
+    // Red giants on the adjoint route (TAMCMC_OPT_RGB_ADJOINT): the hybrid batch.  Windowed's layout and launches -- k_fd_compare also
+    // classifies every slot (adj_rgb_match.h) and leaves an empty delta entry for a linearisable one --, then the adjoint of the C base
+    // tables; k_adj_contract is the one writer of S[C + slot]: its contraction for a linearisable slot, the DELTA launch's sum (folded
+    // into S[C + B + slot], scratch) for a fallback slot, 0 for a base slot
+    bool hybrid() const { return route == Route::Adjoint && rgb; }
+    bool tables_only = false;  // Request::Tables: enqueue() stops after the batch's table builder
     // Route::Rows: the caller passes 2 N "variables" for its N, idx = [index_to_relax, index_to_relax], h = [+h, -h]: slot c*E + 1 + k is
     // theta + h_k e_k, slot c*E + 1 + N + k is theta - h_k e_k.
     // What enqueue() needs beside the block, in doubles.  part: tile partials; S: the sums; model: the base points' planes 1/M0, y/M0, M0
@@ -39,10 +45,18 @@ struct FdBatch {
     size_t o_tab = 0, o_dtab = 0, o_btab = 0, o_drange = 0, o_dflags = 0, o_drow = 0, o_dnold = 0, total_bytes = 0;
     size_t o_adjG = 0, o_adjGn = 0, o_adjpart = 0, o_adjGpart = 0;  // adjoint workspace inside the block: G [C x per x 17], Gn [C x stride], noise tile partials, row segment partials
     int adj_ntn = 0, adj_nseg = 0;
+    size_t o_adjcount = 0;  // hybrid: two integers, the perturbed slots k_adj_contract contracted / took from the DELTA launch (count_slots)
     int layout(tamcmc_hip_ctx *c, Request request, int model_id, int prior_class, int C, int64_t Nparams, const int32_t *plength, int Nvars);
     // block: the batch's device block (total_bytes), constants in place; d_params: C x Np parameter vectors on the device (nullptr: the
-    // block's own params area); w: reserve()d.  ev0 / ev1 (optional) bracket the likelihood launches
-    int enqueue(tamcmc_hip_ctx *c, unsigned char *block, const double *d_params, const Buffers &w, hipEvent_t ev0, hipEvent_t ev1);
+    // block's own params area); w: reserve()d.  ev0 / ev1 (optional) bracket the likelihood launches.  split (optional, hybrid batches: 7
+    // events) marks the stages: start, tables, base launch, fallback delta, row pass, noise pass + fold, contraction
+    int enqueue(tamcmc_hip_ctx *c, unsigned char *block, const double *d_params, const Buffers &w, hipEvent_t ev0, hipEvent_t ev1,
+                hipEvent_t *split = nullptr);
+    // hybrid: k_adj_contract counts the perturbed slots it contracted / took from the DELTA launch into two integers of the block
+    // (o_adjcount) when count_slots is set.  The caller zeroes them once after laying the block out (hipMemsetAsync); hybrid_stats reads
+    // them and zeroes them again (it synchronises the stream)
+    bool count_slots = false;
+    hipError_t hybrid_stats(tamcmc_hip_ctx *c, unsigned char *block, long *linearised, long *fallback) const;
     // Windowed, after the batch has finished (synchronous copies; roofline bookkeeping): bins the DELTA launch really walked -- the affected
     // ranges less the far-only tiles taken from the base point's moments -- and (full != nullptr) its "full table" evaluations
     hipError_t delta_stats(const unsigned char *block, long *bins, long *full) const;

@@ -14,6 +14,16 @@
 //   Adjoint   (TAMCMC_OPT_GRADIENT = TAMCMC_GRADIENT_ADJOINT; FAST arithmetic, fixed-length tables) k_fd_unpack -> k_adj_base -> k_loglike
 //             on the C base points (planes kept) -> k_finalize -> k_adj_rows, k_adj_noise, k_adj_fold (adjoint.hip: dS/d(table entry) of
 //             each base point) -> k_adj_contract (dS of every perturbed table to first order, frozen windows);
+//             Red giants (TAMCMC_OPT_RGB_ADJOINT = 1), the HYBRID batch: a perturbation may change the set of mixed modes, and the rows
+//             after the change then no longer correspond.  Windowed's layout and launches with the adjoint between them and the sums:
+//             k_fd_rgb_perturb -> rgb_device_stage -> k_fd_compare, which first classifies the slot (adj_rgb_match.h: same row count,
+//             same l row by row, every l=1 row within half the distance to its nearest l=1 neighbour) and leaves an EMPTY delta entry
+//             with ADJ_RGB_FLAG_LINEAR in d_flags for a linearisable slot, its normal entry otherwise -> the windowed base launch,
+//             argument for argument -> k_finalize -> k_fd_moments, k_fd_far, k_loglike<DELTA> (all but the fallback slots' tiles leave
+//             at once) -> k_finalize into scratch sums S[C + B ..) -> k_adj_rows, k_adj_noise, k_adj_fold on the C base tables ->
+//             k_adj_contract, the ONE writer of S[C + slot]: the contraction (linearisable), the scratch sum as it is (fallback), 0
+//             (base), NaN (a failed table).  The moments are taken for every chain: which chains have a fallback slot is known on the
+//             device only.  The row pass keeps its (segment, row, chain) grid: see DESIGN section 9 for what a work list cost;
 //   Rows      (tamcmc_hip_fisher) k_fd_unpack -> k_fisher_freeze (every perturbed table gets its base table's windows) -> k_loglike on
 //             all B tables, model rows kept, no sums.
 // Red-giant models (ids 25 / 27): the table of a vector needs the mixed-mode solver, so k_fd_unpack's place is taken by
@@ -32,6 +42,7 @@
 #include "fd_batch.h"
 #include "rgb_prestep.h"
 #include "adjoint.h"
+#include "adj_rgb_match.h"
 #include "fisher.h"
 
 namespace tamcmc {
@@ -62,6 +73,7 @@ struct FdArgs {
     double *d_noise_old;
     TablePtrs Bs;          // base launch (C evaluations): ranges / counts / noise rows indexed by chain
     int full_tables;       // 1: "full table" delta evaluations allowed (the base launch's background series are at hand: FAST arithmetic)
+    int hybrid;            // 1: red giants on the adjoint route -- k_fd_compare classifies the slot first (adj_rgb_match.h)
 };
 
 __global__ void __launch_bounds__(FB) k_fd_unpack(const FdArgs a) {
@@ -212,7 +224,7 @@ __global__ void __launch_bounds__(FB) k_fd_rgb_perturb(const FdArgs a, const rgb
 __global__ void __launch_bounds__(FB) k_fd_compare(const FdArgs a) {
     const int slot = blockIdx.x, c = slot / a.E, e = slot - c * a.E, tid = threadIdx.x;
     const int B = a.C * a.E, per = a.desc.per, stride = a.desc.stride;
-    __shared__ int s_lo, s_hi, s_noise_chg, s_nrows, s_wtot[FB / 64];
+    __shared__ int s_lo, s_hi, s_noise_chg, s_nrows, s_wtot[FB / 64], s_moved;
     if (e == 0) {
         // base evaluation of chain c: the base launch (B = C, model rows written) reads the SAME table rows
         if (tid == 0) {
@@ -230,6 +242,26 @@ __global__ void __launch_bounds__(FB) k_fd_compare(const FdArgs a) {
     // ---- delta table: the multiplets whose row differs from the base row, +new / -old, and the affected bin range ----
     const int bs = a.base_copies ? B + slot : c * a.E;  // the slot holding the base table
     const int n_new = a.T.pairs[2 * slot + 1] - a.T.pairs[2 * slot], n_old = a.T.pairs[2 * bs + 1] - a.T.pairs[2 * bs];
+    if (a.hybrid) {
+        // hybrid batch: a slot whose rows correspond one to one with the base table's is the adjoint's -- an empty delta entry (as e = 0
+        // above) with its class in d_flags, and k_adj_contract writes its difference; every other slot goes on as in the windowed route
+        const bool same = a.status[slot] == TAMCMC_OK && a.status[bs] == TAMCMC_OK && n_new == n_old;  // (uniform)
+        if (tid == 0) s_moved = 0;
+        __syncthreads();
+        if (same) {
+            const tamcmc_multiplet *base = a.T.mults + (size_t)bs * per, *pert = a.T.mults + (size_t)slot * per;
+            for (int j = tid; j < n_old && j < per; j += FB)
+                if (!adj_rgb_row_matches(base, pert, n_old, j)) s_moved = 1;  // (every writer stores the same value)
+        }
+        __syncthreads();
+        if (same && !s_moved) {
+            if (tid == 0) {
+                a.D.pairs[2 * slot] = 0; a.D.pairs[2 * slot + 1] = 0; a.D.nh[slot] = 0; a.D.nn[slot] = 1;
+                a.d_range[2 * slot] = 0; a.d_range[2 * slot + 1] = 0; a.d_flags[slot] = ADJ_RGB_FLAG_LINEAR; a.d_row[slot] = c;
+            }
+            return;
+        }
+    }
     if (tid == 0) { s_lo = a.desc.Nx; s_hi = 0; s_noise_chg = 0; s_nrows = 0; }
     __syncthreads();
     const bool ok = (a.status[slot] == TAMCMC_OK) && (n_old > 0);  // (a base table that failed is empty)
@@ -357,7 +389,11 @@ int FdBatch::layout(tamcmc_hip_ctx *c, Request request, int model_id_, int prior
     model_id = model_id_; prior_class = prior_class_; C = C_; Np = Nparams; Nvars = Nvars_;
     rgb = is_rgb_model(model_id);
     E = Nvars + 1; B = C * E;
-    if (int rc = fd_route(request, c->gradient, c->fd_windowed, c->precision, delta_geometry(c->wgs, c->K), Nvars, rgb, &route)) return rc;
+    if (int rc = fd_route(request, c->gradient, c->fd_windowed, c->precision, delta_geometry(c->wgs, c->K), Nvars, rgb, &route, c->rgb_adjoint != 0))
+        return rc;
+    tables_only = request == Request::Tables;
+    // (the hybrid batch's fallback slots go through the DELTA launch, which exists for the default geometries only: 256 x 4, 64 x 8, 64 x 4)
+    if (hybrid() && !delta_geometry(c->wgs, c->K)) return TAMCMC_ERR_BAD_ARG;
     if (rgb) {
         // red giants: the tables come from the device pre-step, whose workspace is ~28 KB per vector (Prep, RowIn, three arrays of
         // rgb::MAXSOL doubles).  Chunk rule: the batch goes through ONE workspace slice of at most FD_RGB_WORKSPACE bytes, in chunks of
@@ -391,7 +427,7 @@ int FdBatch::layout(tamcmc_hip_ctx *c, Request request, int model_id_, int prior
     const StageLayout L(nslots, stride, (size_t)nslots * per);
     o_tab = o; o = al16(o + L.bytes);
     o_dtab = o_btab = o_drange = o_dflags = o_drow = o_dnold = 0;
-    if (route == Route::Windowed) {
+    if (route == Route::Windowed || hybrid()) {
         const StageLayout LD(B, stride, (size_t)B * 2 * per);      // delta launch input block
         const StageLayout LB(C, stride, 0);                        // base launch: ranges / counts / noise rows by chain
         o_dtab = o; o = al16(o + LD.bytes);
@@ -403,15 +439,17 @@ int FdBatch::layout(tamcmc_hip_ctx *c, Request request, int model_id_, int prior
     }
     o_adjG = o_adjGn = o_adjpart = o_adjGpart = 0;
     adj_ntn = adj_nseg = 0;
+    o_adjcount = 0;
     if (route == Route::Adjoint) {
         const StageLayout LB(C, stride, 0);
         adj_ntn = (int)((c->Nx + ADJ_NTILE - 1) / ADJ_NTILE);
-        o_btab = o; o = al16(o + LB.bytes);
+        if (!hybrid()) { o_btab = o; o = al16(o + LB.bytes); }  // (hybrid: Windowed's, above)
         o_adjG = o; o = al16(o + (size_t)C * per * ADJ_F * 8);
         o_adjGn = o; o = al16(o + (size_t)C * stride * 8);
         o_adjpart = o; o = al16(o + (size_t)C * adj_ntn * stride * 8);
         adj_nseg = (int)((c->Nx + ADJ_SEG - 1) / ADJ_SEG);
         o_adjGpart = o; o = al16(o + (size_t)C * per * adj_nseg * ADJ_F * 8);
+        if (hybrid()) { o_adjcount = o; o = al16(o + 16); }
     }
     total_bytes = o;
     const int tbins = tile_bins(c->wgs, c->K);
@@ -419,9 +457,10 @@ int FdBatch::layout(tamcmc_hip_ctx *c, Request request, int model_id_, int prior
     const size_t planes = 3 * (size_t)C * c->Nx;
     ws.S = deltas() ? (size_t)C + B : (size_t)B;
     ws.part = ws.S * ntiles * 2;
+    if (hybrid()) ws.S += (size_t)B;  // (the DELTA launch's sums, before k_adj_contract puts the fallback slots' in place)
     ws.model = 0;
     if (route == Route::Adjoint) ws.model = planes;
-    if (route == Route::Windowed) ws.model = planes + 2 * (size_t)C * ntiles * FD_MOM + ((size_t)B * ntiles + 7) / 8;
+    if (route == Route::Windowed || hybrid()) ws.model = planes + 2 * (size_t)C * ntiles * FD_MOM + ((size_t)B * ntiles + 7) / 8;
     if (route == Route::Rows) ws.model = (size_t)B * c->Nx;
     ws.bg = (deltas() ? (size_t)C : (size_t)B) * ntiles * 8;
     return TAMCMC_OK;
@@ -471,11 +510,12 @@ int build_tables(tamcmc_hip_ctx *c, const FdBatch &b, unsigned char *db, const S
         hipLaunchKernelGGL(k_fd_unpack, dim3(b.B), dim3(FB), lds, st, fa);
         HIPCHK(c, hipGetLastError());
     }
-    if (b.route == FdRoute::Windowed) {
+    if (b.tables_only) return TAMCMC_OK;
+    if (b.route == FdRoute::Windowed || b.hybrid()) {
         hipLaunchKernelGGL(k_fd_compare, dim3(b.B), dim3(FB), 0, st, fa);
         HIPCHK(c, hipGetLastError());
     }
-    if (b.route == FdRoute::Adjoint) {
+    if (b.route == FdRoute::Adjoint && !b.hybrid()) {
         fa.Bs = table_ptrs(db + b.o_btab, StageLayout(b.C, b.stride, 0));
         hipLaunchKernelGGL(k_adj_base, dim3(b.C), dim3(64), 0, st, fa);
         HIPCHK(c, hipGetLastError());
@@ -506,9 +546,11 @@ int evaluate_tables(tamcmc_hip_ctx *c, const FdArgs &fa, const TablePtrs &ix, in
 
 }  // namespace
 
-int FdBatch::enqueue(tamcmc_hip_ctx *c, unsigned char *db, const double *d_params, const Buffers &w, hipEvent_t ev0, hipEvent_t ev1) {
+int FdBatch::enqueue(tamcmc_hip_ctx *c, unsigned char *db, const double *d_params, const Buffers &w, hipEvent_t ev0, hipEvent_t ev1,
+                     hipEvent_t *split) {
     hipStream_t st = c->stream;
-    const bool windowed = route == Route::Windowed;
+    const bool windowed = route == Route::Windowed || hybrid();  // (delta tables, the base launch's arrays by chain)
+    if (!hybrid()) split = nullptr;
     double *const part = w.part.p, *const S = w.S.p, *const model = w.model.p, *const bgbuf = w.bg.p;
     FdArgs fa;
     fa.desc.model_id = model_id; fa.desc.prior_class = prior_class; fa.desc.Np = (int)Np; fa.desc.per = per;
@@ -524,6 +566,7 @@ int FdBatch::enqueue(tamcmc_hip_ctx *c, unsigned char *db, const double *d_param
     fa.logPr_plus = (double *)(db + o_lpp); fa.logPr_minus = (double *)(db + o_lpm); fa.status = (int *)(db + o_st);
     fa.windowed = windowed ? 1 : 0;
     fa.base_copies = rgb ? 0 : 1;
+    fa.hybrid = hybrid() ? 1 : 0;
     fa.full_tables = (windowed && c->precision == TAMCMC_PRECISION_FAST && bgbuf) ? 1 : 0;
     fa.D = fa.T; fa.Bs = fa.T;
     fa.d_range = nullptr; fa.d_flags = nullptr; fa.d_row = nullptr; fa.d_noise_old = nullptr;
@@ -534,7 +577,10 @@ int FdBatch::enqueue(tamcmc_hip_ctx *c, unsigned char *db, const double *d_param
         fa.d_noise_old = (double *)(db + o_dnold);
     }
     if (rgb && c->precision == TAMCMC_PRECISION_STRICT && !h_prep) return TAMCMC_ERR_BAD_ARG;  // (fd_batch.h: STRICT needs the host unpack)
+    if (split) HIPCHK(c, hipEventRecord(split[0], st));
     if (int rc = build_tables(c, *this, db, L, fa)) return rc;
+    if (tables_only) return TAMCMC_OK;
+    if (split) HIPCHK(c, hipEventRecord(split[1], st));
 
     const int Nx = (int)c->Nx;
     LoglikeArgs a;
@@ -543,6 +589,31 @@ int FdBatch::enqueue(tamcmc_hip_ctx *c, unsigned char *db, const double *d_param
     a.noise_stride = stride; a.model = nullptr;
     if (ev0) HIPCHK(c, hipEventRecord(ev0, st));
     d_done = nullptr;
+    // After the base launch (`a` as evaluate_tables left it): moments of the base points per tile, behind the three planes (the delta
+    // launch's far-only tiles take their sums from them), then the B log-likelihood DIFFERENCES from the delta tables, folded into dS
+    auto delta_launches = [&](double *dS) -> int {
+        double *mom = (c->precision == TAMCMC_PRECISION_FAST && c->wgs == 64) ? model + 3 * (size_t)C * Nx : nullptr;
+        double *momT = mom ? mom + (size_t)C * ntiles * FD_MOM : nullptr;
+        if (mom) HIPCHK(c, launch_fd_moments(a, c->wgs, c->K, mom, momT, st));
+        LoglikeArgs d = a;
+        d.fd_mom = mom;
+        d.fd_momT = momT;
+        d.B = B; d.model = nullptr; d.fd_rows = nullptr;
+        d.bg_poly = fa.full_tables ? bgbuf : nullptr;  // (rows by base point: read by the "full table" evaluations only)
+        d.mults = fa.D.mults; d.offsets = fa.D.pairs; d.noise = fa.D.noise; d.nharvey = fa.D.nh; d.nnoise = fa.D.nn;
+        d.partials = part + (size_t)C * ntiles * 2;
+        d.d_range = fa.d_range; d.d_flags = fa.d_flags; d.d_row = fa.d_row; d.d_noise_old = fa.d_noise_old; d.model0 = model;
+        if (mom) {  // the far-only tiles of the light evaluations, one lane per tile; the delta launch skips what this marks done
+            unsigned char *done = (unsigned char *)(momT + (size_t)C * ntiles * FD_MOM);
+            HIPCHK(c, launch_fd_far(d, c->wgs, c->K, done, st));
+            d.d_done = done;
+        }
+        d_done = d.d_done;
+        tile_bins_ = tile_bins(c->wgs, c->K);
+        HIPCHK(c, launch_loglike_delta(d, c->precision, c->wgs, c->K, st));
+        HIPCHK(c, launch_finalize(d.partials, B, ntiles, dS, st));
+        return TAMCMC_OK;
+    };
     switch (route) {
     case Route::Brute:
         if (int rc = evaluate_tables(c, fa, fa.T, B, Keep::Nothing, true, w, a)) return rc;
@@ -554,6 +625,15 @@ int FdBatch::enqueue(tamcmc_hip_ctx *c, unsigned char *db, const double *d_param
     case Route::Adjoint: {
         // (1) the C base points, exactly the windowed route's base launch
         if (int rc = evaluate_tables(c, fa, fa.Bs, C, Keep::Planes, true, w, a)) return rc;
+        if (split) HIPCHK(c, hipEventRecord(split[2], st));
+        // (1b) hybrid: the windowed route's launches on the delta tables -- empty but for the fallback slots -- into the scratch sums.
+        // The moments are taken for every chain: which chains have a fallback slot is known on the device only, and the device engine
+        // enqueues its batches without a synchronisation
+        double *const fall = hybrid() ? S + C + B : nullptr;
+        if (hybrid()) {
+            if (int rc = delta_launches(fall)) return rc;
+        }
+        if (split) HIPCHK(c, hipEventRecord(split[3], st));
         // (2) dS/d(table entry) of each base point, (3) contracted with every perturbed table's difference from it
         AdjArgs g;
         g.x = c->dx.p; g.logx = c->dlogx.p; g.Nx = Nx;
@@ -562,40 +642,33 @@ int FdBatch::enqueue(tamcmc_hip_ctx *c, unsigned char *db, const double *d_param
         g.mults = fa.T.mults; g.pairs = fa.T.pairs; g.nh = fa.T.nh; g.nn = fa.T.nn; g.status = fa.status; g.noise = fa.T.noise;
         g.G = (double *)(db + o_adjG); g.Gn = (double *)(db + o_adjGn); g.npart = (double *)(db + o_adjpart); g.ntn = adj_ntn;
         g.Gpart = (double *)(db + o_adjGpart); g.nseg = adj_nseg;
-        HIPCHK(c, launch_adjoint(g, st));
-        HIPCHK(c, launch_adjoint_contract(g, S + C, st));
-        break;
-    }
-    case Route::Windowed: {
-        // (1) the C base points: full evaluation, planes kept
-        if (int rc = evaluate_tables(c, fa, fa.Bs, C, Keep::Planes, true, w, a)) return rc;
-        // (1b) moments of the base points per tile, behind the three planes: the delta launch's far-only tiles take their sums from them
-        double *mom = (c->precision == TAMCMC_PRECISION_FAST && c->wgs == 64) ? model + 3 * (size_t)C * Nx : nullptr;
-        double *momT = mom ? mom + (size_t)C * ntiles * FD_MOM : nullptr;
-        if (mom) HIPCHK(c, launch_fd_moments(a, c->wgs, c->K, mom, momT, st));
-        // (2) the C*Nvars perturbed points: log-likelihood DIFFERENCES from the delta tables
-        LoglikeArgs d = a;
-        d.fd_mom = mom;
-        d.fd_momT = momT;
-        d.B = B; d.model = nullptr; d.fd_rows = nullptr;
-        d.bg_poly = fa.full_tables ? bgbuf : nullptr;  // (rows by base point: read by the "full table" evaluations only)
-        d.mults = fa.D.mults; d.offsets = fa.D.pairs; d.noise = fa.D.noise; d.nharvey = fa.D.nh; d.nnoise = fa.D.nn;
-        d.partials = part + (size_t)C * ntiles * 2;
-        d.d_range = fa.d_range; d.d_flags = fa.d_flags; d.d_row = fa.d_row; d.d_noise_old = fa.d_noise_old; d.model0 = model;
-        if (mom) {  // (2a) the far-only tiles of the light evaluations, one lane per tile; the delta launch skips what this marks done
-            unsigned char *done = (unsigned char *)(momT + (size_t)C * ntiles * FD_MOM);
-            HIPCHK(c, launch_fd_far(d, c->wgs, c->K, done, st));
-            d.d_done = done;
+        if (hybrid()) {
+            g.cls = fa.d_flags; g.fall = fall;
+            g.counts = count_slots ? (unsigned long long *)(db + o_adjcount) : nullptr;
         }
-        d_done = d.d_done;
-        tile_bins_ = tile_bins(c->wgs, c->K);
-        HIPCHK(c, launch_loglike_delta(d, c->precision, c->wgs, c->K, st));
-        HIPCHK(c, launch_finalize(d.partials, B, ntiles, S + C, st));
+        HIPCHK(c, launch_adjoint(g, st, split ? split + 4 : nullptr));
+        HIPCHK(c, launch_adjoint_contract(g, S + C, st));
+        if (split) HIPCHK(c, hipEventRecord(split[6], st));
         break;
     }
+    case Route::Windowed:
+        // (1) the C base points: full evaluation, planes kept; (2) the C*Nvars perturbed points from the delta tables
+        if (int rc = evaluate_tables(c, fa, fa.Bs, C, Keep::Planes, true, w, a)) return rc;
+        if (int rc = delta_launches(S + C)) return rc;
+        break;
     }
     if (ev1) HIPCHK(c, hipEventRecord(ev1, st));
     return TAMCMC_OK;
+}
+
+hipError_t FdBatch::hybrid_stats(tamcmc_hip_ctx *c, unsigned char *db, long *linearised, long *fallback) const {
+    unsigned long long v[2] = {0, 0};
+    hipError_t e = hipMemcpyAsync(v, db + o_adjcount, sizeof v, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(db + o_adjcount, 0, sizeof v, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    *linearised = (long)v[0];
+    *fallback = (long)v[1];
+    return e;
 }
 
 hipError_t FdBatch::delta_stats(const unsigned char *db, long *bins, long *full) const {
@@ -759,7 +832,15 @@ static int fd_run(tamcmc_hip_ctx *c, int model_id, int prior_class, int C, const
     const FdBatch::Buffers w{c->d_part, c->d_S, c->d_model, c->d_bg};
     HIPCHK(c, fb.reserve(c, w));
     HIPCHK(c, c->h_S.reserve(nS));
-    if ((rc = fb.enqueue(c, db, nullptr, w, c->timing ? c->ev0 : nullptr, c->timing ? c->ev1 : nullptr))) return rc;
+    hipEvent_t *split = nullptr;
+    if (c->timing && fb.hybrid()) {  // slot counters and the stage split of the hybrid batch (tamcmc_hip_get_rgb_adjoint_stats / _times)
+        for (hipEvent_t &e : c->ev_split)
+            if (!e) HIPCHK(c, hipEventCreate(&e));
+        split = c->ev_split;
+        fb.count_slots = true;
+        HIPCHK(c, hipMemsetAsync(db + fb.o_adjcount, 0, 16, st));
+    }
+    if ((rc = fb.enqueue(c, db, nullptr, w, c->timing ? c->ev0 : nullptr, c->timing ? c->ev1 : nullptr, split))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->h_S.p, c->d_S.p, nS * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(hb + fb.in_bytes, db + fb.in_bytes, fb.out_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
@@ -775,6 +856,17 @@ static int fd_run(tamcmc_hip_ctx *c, int model_id, int prior_class, int C, const
             c->fd_bins += bins;
             c->fd_delta_evals += fb.B;
             c->fd_full_evals += full;
+        }
+        if (split) {
+            static const int from[6] = {0, 1, 3, 4, 2, 5};  // tables, base launch, row pass, noise pass + fold, fallback delta, contraction
+            for (int i = 0; i < 6; i++) {
+                HIPCHK(c, hipEventElapsedTime(&ms, split[from[i]], split[from[i] + 1]));
+                c->rgb_adj_ms[i] = ms;
+            }
+            long lin = 0, fall = 0;
+            HIPCHK(c, fb.hybrid_stats(c, db, &lin, &fall));
+            c->rgb_adj_lin += lin;
+            c->rgb_adj_fallback += fall;
         }
     }
     return assemble_gradient(C, Nvars, params, Nparams, index_to_relax, hstep, Tcoefs, p, c->h_S.p, fb.deltas(),
@@ -823,7 +915,8 @@ int tamcmc_hip_fd_gradient_posterior(tamcmc_hip_ctx *c, int model_id, int prior_
 }
 
 // Audit entry of the adjoint route: the batch with no perturbed vector (Nvars = 0) on Route::Adjoint, whatever the context's
-// option says -- unpack, base launch, k_adj_rows, k_adj_noise -- and G / Gn brought back.
+// option says -- unpack, base launch, k_adj_rows, k_adj_noise -- and G / Gn brought back.  Red giants (with TAMCMC_OPT_RGB_ADJOINT): the
+// hybrid batch with no perturbed slot, the row pass over its work list.
 int tamcmc_hip_adjoint_table(tamcmc_hip_ctx *c, int model_id, int C, const double *params, int64_t Nparams, const int32_t *plength,
                              const double *Tcoefs, double p, double *G, double *Gn, int *nrows) {
     (void)Tcoefs; (void)p;  // (the adjoint of the un-tempered sum S: logL = -p S / T)
@@ -857,6 +950,55 @@ int tamcmc_hip_adjoint_table(tamcmc_hip_ctx *c, int model_id, int C, const doubl
     for (int ch = 0; ch < C; ch++)
         if (stt[ch] != TAMCMC_OK) return stt[ch];  // (that chain's G and Gn are zero)
     return TAMCMC_OK;
+}
+
+// Audit entry of the red-giant batches: the tables of the B = C (Nvars + 1) vectors as the batch's own builder leaves them
+// (k_fd_rgb_perturb -> rgb_device_stage; STRICT: the host's long-double unpack uploaded, as fd_run does) and nothing after them.
+int tamcmc_hip_rgb_batch_tables(tamcmc_hip_ctx *c, int model_id, int C, const double *params, int64_t Nparams, const int32_t *plength,
+                                const int32_t *index_to_relax, int Nvars, const double *hstep, tamcmc_multiplet *rows, int32_t *nrows,
+                                double *noise, int32_t *nharvey, int32_t *nnoise, int32_t *status, int *per) {
+    if (!c) return TAMCMC_ERR_BAD_ARG;
+    if (!is_rgb_model(model_id)) return TAMCMC_ERR_BAD_MODEL;
+    int rc = check_gradient_args(c, C, params, Nparams, plength, index_to_relax, Nvars, hstep, true, GA_PLENGTH | GA_VARS);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    FdBatch fb;
+    if ((rc = fb.layout(c, FdBatch::Request::Tables, model_id, 0, C > 0 ? C : 1, Nparams, plength, Nvars))) return rc;
+    if (per) *per = fb.per;
+    if (C == 0) return TAMCMC_OK;
+    if ((rc = fd_ensure_poly(c))) return rc;
+    const size_t Np = (size_t)Nparams, Nv = (size_t)Nvars, B = (size_t)fb.B;
+    HIPCHK(c, c->h_fd.reserve(fb.in_bytes + fb.out_bytes));
+    HIPCHK(c, c->d_fd.reserve(fb.total_bytes));
+    unsigned char *hb = c->h_fd.p, *db = c->d_fd.p;
+    std::memset(hb, 0, fb.in_bytes);
+    std::memcpy(hb + fb.o_params, params, (size_t)C * Np * 8);
+    std::memcpy(hb + fb.o_h, hstep, Nv * 8);
+    std::memcpy(hb + fb.o_pl, plength, 11 * 4);
+    std::memcpy(hb + fb.o_idx, index_to_relax, Nv * 4);
+    HIPCHK(c, hipMemcpyAsync(db, hb, fb.in_bytes, hipMemcpyHostToDevice, st));
+    if (c->precision == TAMCMC_PRECISION_STRICT && (rc = rgb_host_unpack(c, fb, params, plength, index_to_relax, hstep))) return rc;
+    const FdBatch::Buffers w{c->d_part, c->d_S, c->d_model, c->d_bg};
+    if ((rc = fb.enqueue(c, db, nullptr, w, nullptr, nullptr))) return rc;
+    const StageLayout L((int)B, fb.stride, B * fb.per);
+    const unsigned char *tb = db + fb.o_tab;
+    std::vector<int32_t> pairs(2 * B);
+    HIPCHK(c, hipMemcpyAsync(pairs.data(), tb + L.off_pairs, 2 * B * 4, hipMemcpyDeviceToHost, st));
+    if (rows) HIPCHK(c, hipMemcpyAsync(rows, tb + L.off_mults, B * fb.per * sizeof(tamcmc_multiplet), hipMemcpyDeviceToHost, st));
+    if (noise) HIPCHK(c, hipMemcpyAsync(noise, tb + L.off_noise, B * fb.stride * 8, hipMemcpyDeviceToHost, st));
+    if (nharvey) HIPCHK(c, hipMemcpyAsync(nharvey, tb + L.off_nh, B * 4, hipMemcpyDeviceToHost, st));
+    if (nnoise) HIPCHK(c, hipMemcpyAsync(nnoise, tb + L.off_nn, B * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(hb + fb.in_bytes, db + fb.in_bytes, fb.out_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    const int *stt = (const int *)(hb + fb.o_st);
+    rc = TAMCMC_OK;
+    for (size_t s = 0; s < B; s++) {
+        if (nrows) nrows[s] = pairs[2 * s + 1] - pairs[2 * s];
+        if (status) status[s] = stt[s];
+        if (rc == TAMCMC_OK) rc = stt[s];
+    }
+    return rc;
 }
 
 }  // extern "C"
