@@ -39,10 +39,13 @@ TAMCMC_HD Philox4 philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
     return o;
 }
 
-// 53-bit uniform in (0,1): never 0, never 1
+// 53-bit uniform in (0,1): never 0, never 1.  (b + 1/2) 2^-53 is exact for b < 2^52 and rounded to even above; the one word whose
+// rounding reaches 1.0 (b = 2^53 - 1: 2^53 - 1/2 is a tie) is clamped to the largest double below 1, every other word keeps its bits
+// (tests/test_rng.py).
 TAMCMC_HD double u01_from_bits(uint32_t hi, uint32_t lo) {
     const uint64_t b = (((uint64_t)hi << 32) | lo) >> 11;  // 53 bits
-    return ((double)b + 0.5) * (1.0 / 9007199254740992.0);
+    const double u = ((double)b + 0.5) * (1.0 / 9007199254740992.0);
+    return u < 1.0 ? u : 0.99999999999999988897769753748434595763683319091796875;  // 1 - 2^-53
 }
 
 // Draw addressing: (seed) x (purpose, chain) x (iteration, index).
