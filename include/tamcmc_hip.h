@@ -333,6 +333,18 @@ int tamcmc_hip_rgb_batch_tables(tamcmc_hip_ctx *ctx, int model_id, int C, const 
                                 const int32_t *index_to_relax, int Nvars, const double *hstep, tamcmc_multiplet *rows, int32_t *nrows,
                                 double *noise, int32_t *nharvey, int32_t *nnoise, int32_t *status, int *per);
 
+/* The same audit entry for the main-sequence ids (3, 11, 12, 13, 14, 23; red giants and envelope fits: TAMCMC_ERR_BAD_MODEL): the tables
+ * of the slots [0, C x (Nvars + 1)) of a gradient batch as its table kernel (k_fd_unpack -> wg_unpack) leaves them and nothing after it;
+ * the base-table copies the windowed route keeps behind them are not part of it.  prior_class 0: the kernel prepares the unpack alone (the
+ * tamcmc_hip_fd_gradient path; priors, priors_switch, extra_priors may be NULL); 2 or 3: the log-prior is evaluated first and its last
+ * lane prepares the unpack (the tamcmc_hip_fd_gradient_posterior path) -- the table does not depend on what the prior says.  A slot whose
+ * table failed holds the placeholder dev_unpack.h states: no rows, nnoise = 1, noise[0] = 1, nharvey = 0, and its status.
+ * Out as tamcmc_hip_rgb_batch_tables (*per = the rows every table has). */
+int tamcmc_hip_fd_batch_tables(tamcmc_hip_ctx *ctx, int model_id, int prior_class, int C, const double *params, int64_t Nparams,
+                               const int32_t *plength, const int32_t *index_to_relax, int Nvars, const double *hstep, const double *priors,
+                               const int32_t *priors_switch, const double *extra_priors, tamcmc_multiplet *rows, int32_t *nrows,
+                               double *noise, int32_t *nharvey, int32_t *nnoise, int32_t *status, int *per);
+
 /* Expected (Fisher) information of the chi^2(2p) likelihood at each of the C parameter vectors:
  *   F_jk = (p / T_c) sum_i (d_j M_i)(d_k M_i) / M0_i^2,   j, k over the Nvars free variables (index_to_relax), the sum over all bins,
  * M0 the model row at theta, T_c = Tcoefs[c] (NULL -> 1), p truncated to long as in the likelihood.  It is the expectation of the Hessian of

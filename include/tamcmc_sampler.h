@@ -158,6 +158,23 @@ int tamcmc_sampler_get_gradient(const tamcmc_sampler *s, double *grad, double *g
  * pointer may be NULL.  Host-driven engine: everything.  Device-resident engine: use_drift = 1 only (else TAMCMC_ERR_BAD_ARG),
  * vars_prop and grad_prop; stats_prop and lq come back as NaN (those scalars are not kept). */
 int tamcmc_sampler_get_last_test(const tamcmc_sampler *s, double *vars_prop, double *stats_prop, double *lq, double *grad_prop);
+/* Audit entry of the device-resident random-walk engine (models 3, 11, 12, 13, 14, 23; host-driven engine, Langevin step, red giants:
+ * TAMCMC_ERR_BAD_MODEL): the multiplet tables the last stretch of the last tamcmc_sampler_run left in the likelihood kernel's input
+ * block, and the parameter vector each was built from -- both read from the engine's own buffers, nothing is replayed.
+ *   shape[4] = scheme, slots, rows per slot, noise stride (always returned; call with every other pointer NULL for the sizes)
+ *   scheme 0  no stretch has run yet (slots = 0)
+ *   scheme 1  lockstep: slots = Nchains; slot m is the table of chain m's proposal of the last iteration and params[m] is that proposal
+ *             (the engine's params_prop of that iteration's parity); status and logprior are the proposal's.  A proposal whose log-prior
+ *             is not finite is not unpacked, a table that fails is discarded: either way the slot holds the placeholder (no rows,
+ *             nnoise = 1, noise[0] = 1, nharvey = 0)
+ *   scheme 2  fused: slots = 3 (2 Nchains + 8): slot e (2 Nchains + 8) + s is candidate slot s of candidate set e (the candidates of the
+ *             iterations = e mod 3) and params[slot] is the candidate vector the same launch stored for that slot (cand_params); status is
+ *             the status of the slot's table, logprior the candidate's log-prior.  A table that fails leaves an EMPTY slot (no rows,
+ *             nnoise = 0); the table is built whatever the prior says.  written[slot] = 0: no launch has written the slot yet.
+ * Out (any may be NULL): rows [slots x rows per slot] (a slot's first nrows[slot] rows are its table), nrows, nharvey, nnoise, status,
+ * written [slots], noise [slots x stride], logprior [slots], params [slots x Nparams]. */
+int tamcmc_sampler_get_tables(const tamcmc_sampler *s, int32_t *shape, void *rows, int32_t *nrows, double *noise, int32_t *nharvey,
+                              int32_t *nnoise, int32_t *status, int32_t *written, double *logprior, double *params);
 /* moves [Nchains]: for every chain the number of iterations since creation whose record carries moved = 1 -- the flag the reference
  * stores per iteration and chain (MALA.cpp:543-545; a swap exchanges the pair's flags, :436, :446) and its acceptance diagnostic counts
  * per buffer (Outputs::reject_rate / count_accepted_vals, outputs.cpp:1824-1858).  Differences between two calls / the iterations in

@@ -78,6 +78,8 @@ ABI = [
     ("tamcmc_hip_get_fd_full_tables", C.c_int, [_vp, C.POINTER(C.c_int64)]),
     ("tamcmc_hip_rgb_batch_tables", C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int64, _ip, _ip, C.c_int, _dp, _vp, _ip, _dp, _ip, _ip, _ip,
                                              C.POINTER(C.c_int)]),
+    ("tamcmc_hip_fd_batch_tables", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, C.c_int64, _ip, _ip, C.c_int, _dp, _dp, _ip, _dp, _vp, _ip, _dp,
+                                            _ip, _ip, _ip, C.POINTER(C.c_int)]),
     ("tamcmc_hip_get_rgb_adjoint_stats", C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("tamcmc_hip_get_rgb_adjoint_times", C.c_int, [_vp, _dp]),
 ]
@@ -299,6 +301,33 @@ class HipContext:
         # a per-vector table failure comes back as the call's code AND in status[slot] (that slot's table is empty): not an exception
         self._chk(st, tolerate=((int(st),) if (status != OK).any() else ()))
         return [rows[s, :n[s]].copy() for s in range(B)], [noise[s, :max(nn[s], 0)].copy() for s in range(B)], nh, status
+
+    def fd_batch_tables(self, model_id, params, plength, index_to_relax, hstep, star=None):
+        """The tables of a main-sequence gradient batch as its table kernel leaves them (tamcmc_hip_fd_batch_tables), in batch order like
+        rgb_batch_tables.  star: evaluate its log-prior in front of the unpack (the fd_gradient_posterior path); None: no prior class.
+        Returns (tables, noise, nharvey, nnoise, status)."""
+        params = _f64(params)
+        if params.ndim == 1:
+            params = params[None, :]
+        Cn, Np = params.shape
+        plength, idx, h = _i32(plength), _i32(index_to_relax), _f64(hstep)
+        assert h.size == idx.size
+        pc, pri, sw, ex = 0, None, None, None
+        if star is not None:
+            pc, pri, sw, ex = int(star.prior_class), _f64(star.priors), _i32(star.priors_switch), _f64(star.extra_priors)
+        per = C.c_int(0)
+        head = (int(model_id), pc)
+        args = (_p(params), Np, _p(plength, _ip), _p(idx, _ip), idx.size, _p(h), _p(pri), _p(sw, _ip), _p(ex))
+        self._chk(self._L.tamcmc_hip_fd_batch_tables(self._h, *head, 0, *args, None, None, None, None, None, None, C.byref(per)))
+        B, stride = Cn * (idx.size + 1), max(int(plength[8]), 1)
+        rows = np.zeros((B, per.value), dtype=MULT_DTYPE)
+        n, nh, nn, status = (np.zeros(B, dtype=np.int32) for _ in range(4))
+        noise = np.zeros((B, stride))
+        st = self._L.tamcmc_hip_fd_batch_tables(self._h, *head, Cn, *args, rows.ctypes.data, _p(n, _ip), _p(noise), _p(nh, _ip), _p(nn, _ip),
+                                                _p(status, _ip), C.byref(per))
+        # a per-vector table failure comes back as the call's code AND in status[slot] (that slot holds the placeholder): not an exception
+        self._chk(st, tolerate=((int(st),) if (status != OK).any() else ()))
+        return [rows[s, :n[s]].copy() for s in range(B)], noise, nh, nn, status
 
     def rgb_adjoint_stats(self):
         """(linearised slots, fallback slots) of the hybrid red-giant adjoint batches since the last reset (timing on)."""

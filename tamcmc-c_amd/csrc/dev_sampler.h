@@ -85,6 +85,12 @@ class DevSampler {
     // [9] quick_decide fallbacks taken by the likelihood tiles [10] tile tests decided from a kind-2 record (outside a swap pair)
     // [11] of [5] with two chain groups: iterations run as one joint launch [12] ... run in a window (step_schedule.h: StepPlanner)
     void info(long out[13]) const;
+    // Audit (tamcmc_sampler_get_tables): the tables the last stretch of the last run() left in the likelihood kernel's input block and the
+    // parameter vector each was built from, read from the engine's own buffers.  shape = {scheme, slots, rows per slot, noise stride}.
+    // scheme 1 (lockstep): slot m = chain m's proposal of the last iteration, vector = params_prop of that iteration's parity;
+    // scheme 2 (fused): slot e NS + s = candidate slot s of candidate set e (NS = 2 Nchains + 8), vector = cand_params of the same slot
+    int download_tables(int32_t shape[4], tamcmc_multiplet *rows, int32_t *nrows, double *noise, int32_t *nharvey, int32_t *nnoise,
+                        int32_t *status, int32_t *written, double *logPr, double *params);
     int run(long it0, long n_iter, const char *learn, double *samples, double *stats);
     int run_mala(long it0, long n_iter, const char *learn, double *samples, double *stats);  // use_drift = 1 (dev_mala_impl.h)
 };

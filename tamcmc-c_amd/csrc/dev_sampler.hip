@@ -109,6 +109,7 @@ struct DevSampler::Impl {
     long n_stretch = 0;                  // fused stretches since creation (the first launch of each has nothing to decide)
     long it_joint = 0, it_window = 0;    // of it_fused with two chain groups: iterations run as one launch / as a window (StepPlanner)
     int mala_chol_lds = -1;
+    int last_scheme = 0, last_prop_parity = 0;  // the last stretch run() enqueued: 1 lockstep (and the parity of its last proposals), 2 fused (download_tables)
 
     hipEvent_t gev[8][2];  // fused step with two chain groups: event pairs around sampled launches of the second group (on its stream)
     int n_gev = 0;
@@ -387,6 +388,44 @@ int DevSampler::download_last_proposal(double *vars_prop, double *grad_prop) {
     DCHK(hipStreamSynchronize(c->stream));
     if (vars_prop) DCHK(hipMemcpy(vars_prop, I.a.vars_prop, n * sizeof(double), hipMemcpyDeviceToHost));
     if (grad_prop) DCHK(hipMemcpy(grad_prop, I.mala.grad_prop, n * sizeof(double), hipMemcpyDeviceToHost));
+    return TAMCMC_OK;
+}
+
+int DevSampler::download_tables(int32_t shape[4], tamcmc_multiplet *rows, int32_t *nrows, double *noise, int32_t *nharvey, int32_t *nnoise,
+                                int32_t *status, int32_t *written, double *logPr, double *params) {
+    Impl &I = *impl;
+    tamcmc_hip_ctx *c = I.ctx;
+    const DevSamplerArgs &a = I.a;
+    const FusedArgs &f = I.f;
+    if (I.use_drift || I.rgb || mt::count_multiplets(a.desc.model_id, I.h_plength.data()) < 0) return TAMCMC_ERR_BAD_MODEL;
+    const bool fused = I.last_scheme == 2;
+    const size_t C = (size_t)a.C, NS = (size_t)f.NS, n = fused ? 3 * NS : C, per = (size_t)a.desc.per, stride = (size_t)a.desc.stride, Np = (size_t)a.desc.Np;
+    if (shape) { shape[0] = I.last_scheme; shape[1] = I.last_scheme ? (int32_t)n : 0; shape[2] = (int32_t)per; shape[3] = (int32_t)stride; }
+    if (!I.last_scheme) return TAMCMC_OK;  // (no stretch yet: nothing to read)
+    DCHK(hipSetDevice(c->device));
+    DCHK(hipStreamSynchronize(c->stream));  // (every entry point returns with the sampler's streams idle)
+    const size_t Q = (size_t)I.last_prop_parity;
+    std::vector<int32_t> pairs(2 * n), st(n), nn(n), rej(n, 0);
+    std::vector<double> lp(fused ? 2 * n : n);
+    auto get = [](void *dst, const void *src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
+    DCHK(get(pairs.data(), fused ? f.pairs : a.pairs, 2 * n * 4));
+    DCHK(get(nn.data(), fused ? f.nn : a.nn, n * 4));
+    DCHK(get(st.data(), fused ? f.cand_stR : a.status_prop + Q * C, n * 4));
+    DCHK(get(lp.data(), fused ? f.cand_logPr : a.logPr_prop + Q * C, lp.size() * 8));
+    if (fused) DCHK(get(rej.data(), f.cand_rej, n * 4));
+    if (rows) DCHK(get(rows, fused ? f.mults : a.mults, n * per * sizeof(tamcmc_multiplet)));
+    if (noise) DCHK(get(noise, fused ? f.noise : a.noise, n * stride * 8));
+    if (nharvey) DCHK(get(nharvey, fused ? f.nh : a.nh, n * 4));
+    if (params) DCHK(get(params, fused ? f.cand_params : a.params_prop + Q * C * Np, n * Np * 8));
+    for (size_t s = 0; s < n; s++) {
+        // (fused: a slot no launch has written yet still has the nn = 0 and the status 0 the engine gave it at creation)
+        const bool w = !fused || nn[s] != 0 || st[s] != TAMCMC_OK;
+        if (written) written[s] = w ? 1 : 0;
+        if (nrows) nrows[s] = w ? pairs[2 * s + 1] - pairs[2 * s] : 0;
+        if (nnoise) nnoise[s] = nn[s];
+        if (status) status[s] = st[s];
+        if (logPr) logPr[s] = fused ? (rej[s] ? -INFINITY : lp[2 * s] + lp[2 * s + 1]) : lp[s];
+    }
     return TAMCMC_OK;
 }
 
@@ -820,6 +859,8 @@ struct DevSampler::Impl::RunCall {
                 }
             }
         }
+        I.last_scheme = 1;
+        I.last_prop_parity = P ^ 1;  // (the closing launch read the last proposals from parity P before the flip above)
         // join: the context stream continues after every group
         for (int g = 1; g < G; g++) {
             DCHK(hipEventRecord(I.ev_join[g], I.gst[g]));
@@ -976,6 +1017,7 @@ struct DevSampler::Impl::RunCall {
         P = q;
         I.armed_it = it0 + ib;
         I.armed_q = q;
+        I.last_scheme = 2;
         return TAMCMC_OK;
     }
 

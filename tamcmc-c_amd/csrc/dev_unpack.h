@@ -99,7 +99,7 @@ constexpr Pack make_pack() {
                 p.l |= (unsigned long long)l << (2 * sl);
                 p.i |= (unsigned long long)i << (2 * sl);
                 p.s |= (unsigned long long)s << (2 * sl);
-                if (e > l) p.neg |= 1ull << sl;
+                if (e > l) p.neg |= 1ull << sl;  // (kept for the reference's d(l, 0, 0, -beta); d^l_00 is even in beta, so no test can see this bit flipped)
             }
         }
     return p;

@@ -952,19 +952,19 @@ int tamcmc_hip_adjoint_table(tamcmc_hip_ctx *c, int model_id, int C, const doubl
     return TAMCMC_OK;
 }
 
-// Audit entry of the red-giant batches: the tables of the B = C (Nvars + 1) vectors as the batch's own builder leaves them
-// (k_fd_rgb_perturb -> rgb_device_stage; STRICT: the host's long-double unpack uploaded, as fd_run does) and nothing after them.
-int tamcmc_hip_rgb_batch_tables(tamcmc_hip_ctx *c, int model_id, int C, const double *params, int64_t Nparams, const int32_t *plength,
-                                const int32_t *index_to_relax, int Nvars, const double *hstep, tamcmc_multiplet *rows, int32_t *nrows,
-                                double *noise, int32_t *nharvey, int32_t *nnoise, int32_t *status, int *per) {
-    if (!c) return TAMCMC_ERR_BAD_ARG;
-    if (!is_rgb_model(model_id)) return TAMCMC_ERR_BAD_MODEL;
-    int rc = check_gradient_args(c, C, params, Nparams, plength, index_to_relax, Nvars, hstep, true, GA_PLENGTH | GA_VARS);
+// The audit entries' common body: the tables of the B = C (Nvars + 1) vectors as the batch's own builder leaves them and nothing after them
+// (red giants: k_fd_rgb_perturb -> rgb_device_stage; STRICT: the host's long-double unpack uploaded, as fd_run does.  Others: k_fd_unpack).
+static int batch_tables(tamcmc_hip_ctx *c, int model_id, int prior_class, int C, const double *params, int64_t Nparams, const int32_t *plength,
+                        const int32_t *index_to_relax, int Nvars, const double *hstep, const double *priors, const int32_t *priors_switch,
+                        const double *extra_priors, tamcmc_multiplet *rows, int32_t *nrows, double *noise, int32_t *nharvey,
+                        int32_t *nnoise, int32_t *status, int *per) {
+    int rc = check_gradient_args(c, C, params, Nparams, plength, index_to_relax, Nvars, hstep,
+                                 prior_class == 0 || (priors && priors_switch && extra_priors), GA_PLENGTH | GA_VARS);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     FdBatch fb;
-    if ((rc = fb.layout(c, FdBatch::Request::Tables, model_id, 0, C > 0 ? C : 1, Nparams, plength, Nvars))) return rc;
+    if ((rc = fb.layout(c, FdBatch::Request::Tables, model_id, prior_class, C > 0 ? C : 1, Nparams, plength, Nvars))) return rc;
     if (per) *per = fb.per;
     if (C == 0) return TAMCMC_OK;
     if ((rc = fd_ensure_poly(c))) return rc;
@@ -975,10 +975,15 @@ int tamcmc_hip_rgb_batch_tables(tamcmc_hip_ctx *c, int model_id, int C, const do
     std::memset(hb, 0, fb.in_bytes);
     std::memcpy(hb + fb.o_params, params, (size_t)C * Np * 8);
     std::memcpy(hb + fb.o_h, hstep, Nv * 8);
+    if (prior_class != 0) {
+        std::memcpy(hb + fb.o_pr, priors, 4 * Np * 8);
+        std::memcpy(hb + fb.o_ex, extra_priors, 10 * 8);
+        std::memcpy(hb + fb.o_sw, priors_switch, Np * 4);
+    }
     std::memcpy(hb + fb.o_pl, plength, 11 * 4);
     std::memcpy(hb + fb.o_idx, index_to_relax, Nv * 4);
     HIPCHK(c, hipMemcpyAsync(db, hb, fb.in_bytes, hipMemcpyHostToDevice, st));
-    if (c->precision == TAMCMC_PRECISION_STRICT && (rc = rgb_host_unpack(c, fb, params, plength, index_to_relax, hstep))) return rc;
+    if (fb.rgb && c->precision == TAMCMC_PRECISION_STRICT && (rc = rgb_host_unpack(c, fb, params, plength, index_to_relax, hstep))) return rc;
     const FdBatch::Buffers w{c->d_part, c->d_S, c->d_model, c->d_bg};
     if ((rc = fb.enqueue(c, db, nullptr, w, nullptr, nullptr))) return rc;
     const StageLayout L((int)B, fb.stride, B * fb.per);
@@ -999,6 +1004,28 @@ int tamcmc_hip_rgb_batch_tables(tamcmc_hip_ctx *c, int model_id, int C, const do
         if (rc == TAMCMC_OK) rc = stt[s];
     }
     return rc;
+}
+
+int tamcmc_hip_rgb_batch_tables(tamcmc_hip_ctx *c, int model_id, int C, const double *params, int64_t Nparams, const int32_t *plength,
+                                const int32_t *index_to_relax, int Nvars, const double *hstep, tamcmc_multiplet *rows, int32_t *nrows,
+                                double *noise, int32_t *nharvey, int32_t *nnoise, int32_t *status, int *per) {
+    if (!c) return TAMCMC_ERR_BAD_ARG;
+    if (!is_rgb_model(model_id)) return TAMCMC_ERR_BAD_MODEL;
+    return batch_tables(c, model_id, 0, C, params, Nparams, plength, index_to_relax, Nvars, hstep, nullptr, nullptr, nullptr, rows, nrows, noise,
+                        nharvey, nnoise, status, per);
+}
+
+// Audit entry of the main-sequence batches: the tables k_fd_unpack leaves in the slots [0, B) (the Tables request takes Brute's layout: no
+// base copies behind them), with the log-prior in front of the unpack (prior_class 2, 3) or without it (0).
+int tamcmc_hip_fd_batch_tables(tamcmc_hip_ctx *c, int model_id, int prior_class, int C, const double *params, int64_t Nparams,
+                               const int32_t *plength, const int32_t *index_to_relax, int Nvars, const double *hstep, const double *priors,
+                               const int32_t *priors_switch, const double *extra_priors, tamcmc_multiplet *rows, int32_t *nrows,
+                               double *noise, int32_t *nharvey, int32_t *nnoise, int32_t *status, int *per) {
+    if (!c) return TAMCMC_ERR_BAD_ARG;
+    if (is_rgb_model(model_id) || tamcmc::is_envelope_model(model_id)) return TAMCMC_ERR_BAD_MODEL;
+    if (prior_class != 0 && prior_class != 2 && prior_class != 3) return TAMCMC_ERR_BAD_MODEL;
+    return batch_tables(c, model_id, prior_class, C, params, Nparams, plength, index_to_relax, Nvars, hstep, priors, priors_switch,
+                        extra_priors, rows, nrows, noise, nharvey, nnoise, status, per);
 }
 
 }  // extern "C"

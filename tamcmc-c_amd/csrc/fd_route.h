@@ -16,7 +16,7 @@ namespace tamcmc {
 //   Rows      every perturbed table given its base table's windows, then ONE launch that leaves the B model rows (fisher.h): no sums.
 enum class FdRoute { Brute, Windowed, Adjoint, Rows };
 // Who asks: the gradient entries and the sampler follow the context's options, the audit entry (tamcmc_hip_adjoint_table) and the Fisher
-// information (tamcmc_hip_fisher) name their route whatever the options say; Tables (tamcmc_hip_rgb_batch_tables) asks for the batch's
+// information (tamcmc_hip_fisher) name their route whatever the options say; Tables (tamcmc_hip_rgb_batch_tables, tamcmc_hip_fd_batch_tables) asks for the batch's
 // tables and nothing after them: the smallest layout, Brute's, in every arithmetic mode.
 enum class FdRequest { FromOptions, Adjoint, Rows, Tables };
 

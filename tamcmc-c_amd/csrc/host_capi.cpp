@@ -327,6 +327,13 @@ int tamcmc_sampler_get_last_test(const tamcmc_sampler *s, double *vars_prop, dou
     return TAMCMC_OK;
 }
 
+int tamcmc_sampler_get_tables(const tamcmc_sampler *s, int32_t *shape, void *rows, int32_t *nrows, double *noise, int32_t *nharvey,
+                              int32_t *nnoise, int32_t *status, int32_t *written, double *logprior, double *params) {
+    if (!s || !shape) return TAMCMC_ERR_BAD_ARG;
+    if (!s->dev) return TAMCMC_ERR_BAD_MODEL;
+    return s->dev->download_tables(shape, (tamcmc_multiplet *)rows, nrows, noise, nharvey, nnoise, status, written, logprior, params);
+}
+
 int tamcmc_sampler_get_move_counts(const tamcmc_sampler *s, int64_t *moves) {
     if (!s || !moves) return TAMCMC_ERR_BAD_ARG;
     if (int rc = s->refresh()) return rc;

@@ -2,8 +2,13 @@
 //
 // Host build (mode_tables.cpp, g++/clang x86): `xreal` = long double, i.e. the expression types of the reference
 // (Pslm products, pi used for amplitudes) -> tables bit-identical to the CPU restatement.
-// Device build (dev_sampler.hip, gfx950): `xreal` = double (no 80-bit type on the GPU) -> nu_nlm / H*V differ from the
-// host table by <= 1-2 ulp; window indices are pure double arithmetic and agree bit for bit.
+// Device build (dev_sampler.hip, gfx950): `xreal` = double (no 80-bit type on the GPU) -> nu_nlm differs from the host table by <= 2 ulp,
+// and so does H*V where the heights do not pass through the Wigner sum (ids 12, 13, 14).  Where they do (ids 3, 11, 23) the device
+// evaluates another formula -- x^n by repeated multiplication (up to 2l roundings per term where pow() has one), ocml's sine and cosine
+// where the host has libm's, each entering with its exponent, and the square doubling what the sum carries -- and H*V lies up to
+// 13 ulp of the multiplet's largest component from the host's (measured; 9.9 x 2^-52 of the sum of the term magnitudes, against 53 from
+// counting the roundings: tests/test_gpu_tables.py, which asserts all of this).  Window indices are pure double arithmetic and agree bit
+// for bit.
 //
 // Structure: per parameter vector a small set of SHARED scalars (visibilities, eta0, asymmetry, ...) and then one
 // independent multiplet per index -- the host loops over the index, the device gives each index its own thread.

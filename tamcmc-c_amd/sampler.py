@@ -26,6 +26,7 @@ EXTRA_ABI += [
     ("tamcmc_sampler_nvars", C.c_int64, [_vp]),
     ("tamcmc_sampler_get_info", C.c_int, [_vp, _i64p, C.c_int32]),
     ("tamcmc_sampler_get_move_counts", C.c_int, [_vp, _i64p]),
+    ("tamcmc_sampler_get_tables", C.c_int, [_vp, _ip, _vp, _ip, _dp, _ip, _ip, _ip, _ip, _dp, _dp]),
     ("tamcmc_sampler_get_gradient", C.c_int, [_vp, _dp, _dp, _ip]),
     ("tamcmc_sampler_get_last_test", C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     ("tamcmc_outputs_write_acceptance", C.c_int, [C.c_char_p, C.c_double, _dp, C.c_int32, C.c_int32]),
@@ -178,6 +179,26 @@ class Sampler:
         if rc != OK:
             raise TamcmcError(rc, "tamcmc_sampler_get_last_test")
         return v, st, lq, g
+
+    def tables(self):
+        """tamcmc_sampler_get_tables (device engine, random walk): a dict with scheme (0 none yet, 1 lockstep, 2 fused), tables[slot] (that
+        slot's rows, MULT_DTYPE), noise [slots x stride], nharvey, nnoise, status, written, logprior [slots], params [slots x Nparams]."""
+        from . import MULT_DTYPE
+        shape = np.zeros(4, dtype=np.int32)
+        rc = self._L.tamcmc_sampler_get_tables(self._h, _p(shape, _ip), None, None, None, None, None, None, None, None, None)
+        if rc != OK:
+            raise TamcmcError(rc, "tamcmc_sampler_get_tables")
+        scheme, n, per, stride = (int(v) for v in shape)
+        rows = np.zeros((n, per), dtype=MULT_DTYPE)
+        nr, nh, nn, st, wr = (np.zeros(n, dtype=np.int32) for _ in range(5))
+        noise, lp, par = np.zeros((n, stride)), np.zeros(n), np.zeros((n, self._keep["inputs"].size))
+        if n:
+            rc = self._L.tamcmc_sampler_get_tables(self._h, _p(shape, _ip), rows.ctypes.data, _p(nr, _ip), _p(noise), _p(nh, _ip), _p(nn, _ip),
+                                                   _p(st, _ip), _p(wr, _ip), _p(lp), _p(par))
+            if rc != OK:
+                raise TamcmcError(rc, "tamcmc_sampler_get_tables")
+        return {"scheme": scheme, "tables": [rows[s, :max(nr[s], 0)].copy() for s in range(n)], "noise": noise, "nharvey": nh, "nnoise": nn,
+                "status": st, "written": wr, "logprior": lp, "params": par}
 
     def move_counts(self):
         """Per chain: iterations since creation whose record carries moved = 1 (tamcmc_sampler_get_move_counts)."""
