@@ -29,10 +29,6 @@ __device__ __forceinline__ void static_for(F &&f) {
     static_for_from<0, N>(f);
 }
 
-__global__ void k_fill_poly(mt::PolyTab *t) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) mt::fill_poly(*t);
-}
-
 constexpr int TB = 256;  // threads of k_iterate (one workgroup per chain)
 
 // Outcome of the Metropolis-Hastings test of chain j for the pending iteration (MALA.cpp:490-551): the values the
@@ -472,8 +468,6 @@ __device__ __forceinline__ void Lz_rows_wave(const DevSamplerArgs &a, int chain,
     }
 }
 
-__host__ __device__ inline bool is_rgb_model(int id) { return id == TAMCMC_MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4_ID || id == TAMCMC_MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4_ID; }
-
 // Proposal of iteration `it` for `chain` from the state in LDS (s_vars/s_params): x' = x + L z (MALA.cpp:348-355), L =
 // chol((Sigma+eps2) sigma) stored transposed, same Philox streams as the host engine; log-prior; params' -> multiplet table
 // written into slot `slot` of the likelihood kernel's input block.  Ends without a barrier.  (B): 256 threads.
@@ -497,13 +491,10 @@ __device__ __forceinline__ void propose_common(const DevSamplerArgs &a, const Un
     for (int i = tid; i < Np; i += TB) pp[i] = s_params[i];
     if (rgb) {
         // red-giant models (ids 25 / 27): the table needs the mixed-mode solver -- the kernels enqueued right behind this launch
-        // (rgb_device_stage) build it.  Here: the log-prior (priors_calc.cpp:319-512; generic terms one per lane, summed by lane 0 in the
-        // reference's order) by wave 0 while wave 1 runs the scalar unpack of the proposal (rgb_unpack.h) into the group's workspace slice.
-        __shared__ rgb::Prep sP;
-        __shared__ rgb::RowIn sR;
-        __shared__ double s_w[40], s_noise[3 * TAMCMC_MAX_HARVEY + 4], s_lp;
-        __shared__ int32_t s_hn[2];
-        __shared__ int s_stp;
+        // (rgb_device_stage) build it.  Here: the red-giant front end (rgb_front.h, shared with the gradient batch's k_fd_rgb_perturb) on
+        // this kernel's schedule: the generic prior terms by all 256 lanes, then the serial tail on lane 0 while wave 1 runs the scalar
+        // unpack of the proposal, published into the group's workspace slice.
+        __shared__ rgb::FrontLds F;
         mt::xreal *terms = (mt::xreal *)U.poly;  // (the polynomial tables' LDS is not used by these models; xreal = double on the device)
         const bool spread = a.desc.prior_class == 4 && (size_t)Np * sizeof(mt::xreal) <= sizeof(mt::PolyTab);
         if (tid == 0) *U.status = TAMCMC_OK;
@@ -515,41 +506,20 @@ __device__ __forceinline__ void propose_common(const DevSamplerArgs &a, const Un
                 if (st != TAMCMC_OK) *U.status = st;
             }
         __syncthreads();
-        if (tid == 0) {
-            int st = *U.status;
-            s_lp = (double)pr::prior_serial(a.desc.prior_class, s_params, a.desc.plength, Np, a.desc.priors, a.desc.priors_switch, a.desc.extra, &st,
-                                            spread ? terms : nullptr);
-            s_stp = st;
-        } else if ((tid >> 6) == 1) {
-            rgb::WaveLanes x;
-            x.w = s_w;
-            double fmin;
-            rgb::unpack_vector(x, s_params, a.desc.plength, rs->step, a.desc.model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4_ID, rs->dense, sP, sR, s_noise,
-                               &s_hn[0], &s_hn[1], &fmin);
-        }
+        if (tid == 0) rgb::front_prior_serial(a.desc, s_params, spread ? terms : nullptr, *U.status, F);
+        else if ((tid >> 6) == 1) rgb::front_unpack(a.desc, s_params, *rs, F);
         __syncthreads();
-        const double lp = s_lp;
-        const int stp = s_stp;
+        const double lp = F.lp;
+        const int stp = F.stp;
         if (tid == 0 && (stp != TAMCMC_OK || lp == -INFINITY || isnan(lp))) {  // model_def.cpp:472,476-480 skips the model: nothing to solve
-            sP.Lp = 0; sP.Lg = 0; sP.status = stp != TAMCMC_OK ? stp : TAMCMC_ERR_BAD_ARG;
-            sR.status = sP.status; sR.Nfl0 = sR.Nfl2 = sR.Nfl3 = 0; sR.bias_n = 0;
-            s_noise[0] = 1.0;
-            s_hn[0] = 0; s_hn[1] = 1;
+            F.P.Lp = 0; F.P.Lg = 0; F.P.status = stp != TAMCMC_OK ? stp : TAMCMC_ERR_BAD_ARG;
+            F.R.status = F.P.status; F.R.Nfl0 = F.R.Nfl2 = F.R.Nfl3 = 0; F.R.bias_n = 0;
+            F.noise[0] = 1.0;
+            F.hn[0] = 0; F.hn[1] = 1;
         }
         __syncthreads();
-        static_assert(sizeof(rgb::Prep) % 8 == 0 && sizeof(rgb::RowIn) % 8 == 0, "copied as doubles");
-        const double *src = (const double *)&sP;
-        double *dst = (double *)&rs->preps[rb];
-        for (int i = tid; i < (int)(sizeof(rgb::Prep) / 8); i += TB) dst[i] = src[i];
-        src = (const double *)&sR;
-        dst = (double *)&rs->rows[rb];
-        for (int i = tid; i < (int)(sizeof(rgb::RowIn) / 8); i += TB) dst[i] = src[i];
-        for (int i = tid; i < s_hn[1] && i < a.desc.stride; i += TB) a.noise[(size_t)slot * a.desc.stride + i] = s_noise[i];
+        rgb::front_publish<TB>(F, *rs, rb, slot, a.desc.stride, a.noise, a.nh, a.nn);
         if (tid == 0) {
-            rs->norm_bits[rb] = 0ull;
-            rs->nsol[rb] = 0;
-            a.nh[slot] = s_hn[0];
-            a.nn[slot] = s_hn[1];
             *logPr_out = lp;
             *status_out = stp;
         }

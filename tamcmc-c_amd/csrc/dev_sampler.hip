@@ -54,6 +54,7 @@
 
 #include "ctx.h"
 #include "rgb_prestep.h"
+#include "rgb_front.h"
 #include "dev_sampler.h"
 #include "kernels.h"
 #include "loglike_tile.h"
@@ -319,8 +320,7 @@ int DevSampler::init(tamcmc_hip_ctx *c, const DevSamplerInit &in) {
     // polynomial tables Pslm/Qlm: computed ON the device (its own double arithmetic), read through a uniform pointer
     mt::PolyTab *d_tab;
     DCHK(I.dalloc(&d_tab, 1));
-    hipLaunchKernelGGL(k_fill_poly, dim3(1), dim3(64), 0, st, d_tab);
-    DCHK(hipGetLastError());
+    DCHK(fill_poly_table(d_tab, st));
     a.desc.poly = d_tab;
     for (int i = 0; i < 64; i++) { DCHK(hipEventCreate(&I.ev[i][0])); DCHK(hipEventCreate(&I.ev[i][1])); I.n_ev = i + 1; }
     for (int i = 0; i < 8; i++) { DCHK(hipEventCreate(&I.gev[i][0])); DCHK(hipEventCreate(&I.gev[i][1])); I.n_gev = i + 1; }
@@ -1086,16 +1086,15 @@ int DevSampler::run_mala(long it0, long n_iter, const char *learn, double *sampl
         if (nb.total_bytes != I.fd.total_bytes || nb.route != I.fd.route || nb.ntiles != I.fd.ntiles || nb.rgb != I.fd.rgb ||
             nb.chunk != I.fd.chunk || !I.fd_block.p || need_bg) {
             I.fd = nb;
-            rc = fd_ensure_poly(c);
+            rc = ensure_poly(c);
             if (rc) return rc;
             DCHK(I.fd_block.reserve(nb.total_bytes));
-            std::vector<unsigned char> hb(nb.in_bytes, 0);
-            std::memcpy(hb.data() + nb.o_pr, I.h_priors.data(), 4 * Np * 8);
-            std::memcpy(hb.data() + nb.o_ex, I.h_extra.data(), 10 * 8);
-            std::memcpy(hb.data() + nb.o_sw, I.h_sw.data(), Np * 4);
-            std::memcpy(hb.data() + nb.o_pl, I.h_plength.data(), 11 * 4);
-            std::memcpy(hb.data() + nb.o_idx, I.h_idx.data(), Nv * 4);
-            DCHK(hipMemcpyAsync(I.fd_block.p, hb.data(), nb.in_bytes, hipMemcpyHostToDevice, st));
+            FdInputs in;  // the layout's constants; the vectors come from the device at every enqueue, the steps from k_mala_steps
+            in.priors = I.h_priors.data(); in.extra_priors = I.h_extra.data(); in.priors_switch = I.h_sw.data();
+            in.plength = I.h_plength.data(); in.index_to_relax = I.h_idx.data();
+            std::vector<unsigned char> hb(nb.head.in_bytes);
+            nb.head.stage(hb.data(), in);
+            DCHK(hipMemcpyAsync(I.fd_block.p, hb.data(), nb.head.in_bytes, hipMemcpyHostToDevice, st));
             DCHK(hipStreamSynchronize(st));
             DCHK(nb.reserve(c, fd_ws));
             I.grad_valid = false;
@@ -1104,10 +1103,11 @@ int DevSampler::run_mala(long it0, long n_iter, const char *learn, double *sampl
     FdBatch &fd = I.fd;
     unsigned char *db = I.fd_block.p;
     fd.count_slots = c->timing && fd.hybrid();  // (hybrid red-giant batches: linearised / fallback slots of this call, counted on the device)
-    if (fd.count_slots) DCHK(hipMemsetAsync(db + fd.o_adjcount, 0, 16, st));
+    if (fd.count_slots) DCHK(fd.zero_slot_counts(c, db));
     MalaArgs M = I.mala;
-    M.S = I.fd_S.p; M.lpp = (const double *)(db + fd.o_lpp); M.lpm = (const double *)(db + fd.o_lpm); M.st = (const int *)(db + fd.o_st);
-    M.h = (double *)(db + fd.o_h); M.E = fd.E; M.deltas = fd.deltas() ? 1 : 0; M.fd_step_rel = I.fd_step_rel; M.delta = I.delta;
+    const FdResults res = fd.head.results(db);  // (the device block: read by k_mala_test)
+    M.S = I.fd_S.p; M.lpp = res.lpp; M.lpm = res.lpm; M.st = res.status;
+    M.h = fd.head.hstep(db); M.E = fd.E; M.deltas = fd.deltas() ? 1 : 0; M.fd_step_rel = I.fd_step_rel; M.delta = I.delta;
     if (samples && I.smp_cap < (size_t)n_iter * C * Nv) {
         DCHK(I.dalloc(&a.samples, (size_t)n_iter * C * Nv));
         I.smp_cap = (size_t)n_iter * C * Nv;

@@ -1,13 +1,18 @@
 // fd_batch.h -- one gradient batch (C chains x (Nvars + 1) evaluations) as an object: the route it takes (fd_route.h), the layout of its
 // device block, its workspace, and its launch from parameter vectors already on the device (fd_batch.hip).  Used by the host entry points
 // (tamcmc_hip_fd_gradient*, tamcmc_hip_adjoint_table, tamcmc_hip_fisher) and by the device-resident Langevin step (dev_sampler.hip: run_mala).
+// Who owns what: the head of the block -- the arrays a caller fills and reads back -- is fd_block.h's (FdBlockHead: offsets, stage(),
+// results()); the host entries go through begin() / finish() and never see an offset.  Everything behind the head (tables, delta tables,
+// adjoint workspace) is layout()'s and is read by fd_batch.hip alone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "ctx.h"
+#include "fd_block.h"
 #include "fd_rgb_chunk.h"
 #include "fd_route.h"
+#include "rgb_prestep.h"
 
 namespace tamcmc {
 
@@ -39,9 +44,8 @@ struct FdBatch {
     // unpacks, in double.  STRICT promises the reference's long-double unpack, so under STRICT enqueue() REQUIRES these (it returns
     // TAMCMC_ERR_BAD_ARG without them): a caller whose vectors live on the device only cannot run a STRICT red-giant batch.
     const void *h_prep = nullptr, *h_rows = nullptr, *h_header = nullptr;
-    // offsets inside the device block: host-filled constants [0, in_bytes), results [in_bytes, in_bytes + out_bytes), tables after
-    size_t o_params = 0, o_h = 0, o_pr = 0, o_ex = 0, o_pl = 0, o_idx = 0, o_sw = 0, in_bytes = 0;
-    size_t o_lpp = 0, o_lpm = 0, o_st = 0, out_bytes = 0;
+    // the device block: its head (fd_block.h: host-filled constants [0, in_bytes), results [in_bytes, in_bytes + out_bytes)), tables after
+    FdBlockHead head;
     size_t o_tab = 0, o_dtab = 0, o_btab = 0, o_drange = 0, o_dflags = 0, o_drow = 0, o_dnold = 0, total_bytes = 0;
     size_t o_adjG = 0, o_adjGn = 0, o_adjpart = 0, o_adjGpart = 0;  // adjoint workspace inside the block: G [C x per x 17], Gn [C x stride], noise tile partials, row segment partials
     int adj_ntn = 0, adj_nseg = 0;
@@ -52,10 +56,21 @@ struct FdBatch {
     // events) marks the stages: start, tables, base launch, fallback delta, row pass, noise pass + fold, contraction
     int enqueue(tamcmc_hip_ctx *c, unsigned char *block, const double *d_params, const Buffers &w, hipEvent_t ev0, hipEvent_t ev1,
                 hipEvent_t *split = nullptr);
+    // The host entries' way round enqueue(), on the context's own blocks (h_fd, d_fd) and workspace.  begin: the inputs staged and
+    // uploaded (red giants under STRICT: the host's long-double unpack too), the workspace reserved unless tables_only; *block is what
+    // enqueue() takes.  finish: the results copied back behind whatever the caller enqueued after the batch, the stream synchronised
+    int begin(tamcmc_hip_ctx *c, const FdInputs &in, unsigned char **block);
+    int finish(tamcmc_hip_ctx *c, FdResults *out);
+    // enqueue() as a host entry calls it between the two: the block's own vectors, the workspace begin() reserved
+    int enqueue(tamcmc_hip_ctx *c, unsigned char *block, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, hipEvent_t *split = nullptr) {
+        return enqueue(c, block, nullptr, context_buffers(c), ev0, ev1, split);
+    }
+    static Buffers context_buffers(tamcmc_hip_ctx *c) { return Buffers{c->d_part, c->d_S, c->d_model, c->d_bg}; }
     // hybrid: k_adj_contract counts the perturbed slots it contracted / took from the DELTA launch into two integers of the block
-    // (o_adjcount) when count_slots is set.  The caller zeroes them once after laying the block out (hipMemsetAsync); hybrid_stats reads
-    // them and zeroes them again (it synchronises the stream)
+    // (o_adjcount) when count_slots is set.  The caller zeroes them once after laying the block out (zero_slot_counts); hybrid_stats
+    // reads them and zeroes them again (it synchronises the stream)
     bool count_slots = false;
+    hipError_t zero_slot_counts(tamcmc_hip_ctx *c, unsigned char *block) const { return hipMemsetAsync(block + o_adjcount, 0, 16, c->stream); }
     hipError_t hybrid_stats(tamcmc_hip_ctx *c, unsigned char *block, long *linearised, long *fallback) const;
     // Windowed, after the batch has finished (synchronous copies; roofline bookkeeping): bins the DELTA launch really walked -- the affected
     // ranges less the far-only tiles taken from the base point's moments -- and (full != nullptr) its "full table" evaluations
@@ -64,7 +79,6 @@ struct FdBatch {
     const unsigned char *d_done = nullptr;
     int tile_bins_ = 0;
 };
-int fd_ensure_poly(tamcmc_hip_ctx *c);  // Pslm/Qlm tables in c->d_poly
 
 // The argument checks the gradient entries share, after the context and the model: spectrum, counts, pointers, layout, variables.
 // rest_ok: the entry's own pointers (outputs, priors) are there.  GA_PLENGTH: plength required, and its sum must be Nparams.  GA_VARS:

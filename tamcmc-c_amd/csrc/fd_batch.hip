@@ -29,6 +29,10 @@
 // Red-giant models (ids 25 / 27): the table of a vector needs the mixed-mode solver, so k_fd_unpack's place is taken by
 //   k_fd_rgb_perturb (perturbed vector, class-4 log-prior, scalar unpack into the pre-step workspace) -> rgb_device_stage (solver, rows),
 // in chunks of vectors through ONE workspace slice; everything after the tables is the same.
+// Who owns what.  The head of the device block (inputs, results) is fd_block.h's; the host entries here and in fisher.hip reach it through
+// FdBatch::begin() / finish(), the device sampler through FdBlockHead::stage() / results().  The rest of the block is layout()'s, read
+// by enqueue() and the audit copies of this file.  The red-giant front end inside k_fd_rgb_perturb is rgb_front.h's, shared with the
+// sampler's proposal kernel; the polynomial tables are ensure_poly()'s (rgb_prestep.hip).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -41,6 +45,7 @@
 #include "kernels.h"
 #include "fd_batch.h"
 #include "rgb_prestep.h"
+#include "rgb_front.h"
 #include "adjoint.h"
 #include "adj_rgb_match.h"
 #include "fisher.h"
@@ -49,10 +54,6 @@ namespace tamcmc {
 namespace {
 
 constexpr int FB = 128;
-
-__global__ void k_fill_poly_fd(mt::PolyTab *t) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) mt::fill_poly(*t);
-}
 
 struct FdArgs {
     ModelDesc desc;
@@ -130,9 +131,9 @@ __global__ void __launch_bounds__(FB) k_fd_unpack(const FdArgs a) {
 }
 
 // Red-giant models (ids 25 / 27), the counterpart of k_fd_unpack up to the table: one workgroup per slot of the chunk [slot0, slot0 + gridDim.x).
-// The perturbed vector is staged in LDS; its class-4 log-prior is evaluated as the device sampler's proposal kernel does (generic terms one
-// per lane of the first wave, then pr::prior_serial's constraints, ordered sum and smoothness tail by lane 0) while the second wave runs the scalar unpack
-// (rgb_unpack.h) of the same vector into entry blockIdx.x of the pre-step workspace slice; rgb_device_stage builds the table from there.
+// The perturbed vector is staged in LDS and goes through the red-giant front end (rgb_front.h, shared with the device sampler's proposal
+// kernel) on this kernel's own schedule: the whole class-4 log-prior by the first wave while the second runs the scalar unpack of the
+// same vector, published into entry blockIdx.x of the pre-step workspace slice; rgb_device_stage builds the table from there.
 // The likelihood is evaluated whatever the prior says (the caller combines the parts), so an infinite prior does not empty the entry.
 // host_unpack (STRICT, host entry): the workspace entries, noise rows and counts were filled by the host's long-double unpack and uploaded
 // (fd_run); the kernel then only evaluates the prior and resets the solver's counters.
@@ -141,17 +142,13 @@ __global__ void __launch_bounds__(FB) k_fd_rgb_perturb(const FdArgs a, const rgb
     const int Np = a.desc.Np;
     double *s_params = (double *)s_raw;
     mt::xreal *terms = (mt::xreal *)(s_params + Np);  // [Np] generic prior terms (xreal = double on the device)
-    __shared__ rgb::Prep sP;
-    __shared__ rgb::RowIn sR;
-    __shared__ double s_w[40], s_noise[3 * TAMCMC_MAX_HARVEY + 4], s_lp;
-    __shared__ int32_t s_hn[2];
-    __shared__ int s_stp;
+    __shared__ rgb::FrontLds F;
     const int rb = blockIdx.x, slot = slot0 + rb, c = slot / a.E, e = slot - c * a.E, tid = threadIdx.x;
     const bool with_prior = a.desc.prior_class != 0;
     for (int i = tid; i < Np; i += FB) s_params[i] = a.params[(size_t)c * Np + i];
     const int ip = e > 0 ? a.idx[e - 1] : 0;
     const double x0 = e > 0 ? a.params[(size_t)c * Np + ip] : 0.0, hh = e > 0 ? a.h[e - 1] : 0.0;
-    if (tid == 0) { s_stp = TAMCMC_OK; s_lp = 0.0; }
+    if (tid == 0) { F.stp = TAMCMC_OK; F.lp = 0.0; }
     __syncthreads();
     if (e > 0 && tid == 0) s_params[ip] = x0 + hh;
     __syncthreads();
@@ -162,50 +159,30 @@ __global__ void __launch_bounds__(FB) k_fd_rgb_perturb(const FdArgs a, const rgb
             for (int i = tid; i < Np; i += 64) {
                 int st = TAMCMC_OK;
                 terms[i] = pr::generic_prior_term(s_params, Np, a.desc.priors, a.desc.priors_switch, i, &st);
-                if (st != TAMCMC_OK) s_stp = st;
+                if (st != TAMCMC_OK) F.stp = st;
             }
             WaveSync()();
-            if (tid == 0) {
-                int st = s_stp;
-                s_lp = (double)pr::prior_serial(a.desc.prior_class, s_params, a.desc.plength, Np, a.desc.priors, a.desc.priors_switch, a.desc.extra, &st, terms);
-                s_stp = st;
-            }
+            if (tid == 0) rgb::front_prior_serial(a.desc, s_params, terms, F.stp, F);
         }
         __syncthreads();
-        return s_lp;
+        return F.lp;
     };
-    if ((tid >> 6) == 1 && !host_unpack) {  // wave 1: the scalar unpack (it reads s_params only), while wave 0 is in log_prior() below
-        rgb::WaveLanes x;
-        x.w = s_w;
-        double fmin;
-        rgb::unpack_vector(x, s_params, a.desc.plength, rs.step, a.desc.model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4_ID, rs.dense, sP, sR, s_noise,
-                           &s_hn[0], &s_hn[1], &fmin);
-    }
+    // wave 1: the scalar unpack, while wave 0 is in log_prior() below
+    if ((tid >> 6) == 1 && !host_unpack) rgb::front_unpack(a.desc, s_params, rs, F);
     const double lp = with_prior ? log_prior() : 0.0;
     __syncthreads();
+    // a prior the device cannot evaluate: the slot fails (status, NaN); an infinite one changes nothing here
     if (host_unpack) {
-        if (tid == 0 && s_stp != TAMCMC_OK) { rs.preps[rb].status = s_stp; rs.rows[rb].status = s_stp; }
-    } else {
-        if (tid == 0 && s_stp != TAMCMC_OK) { sP.status = s_stp; sR.status = s_stp; }  // a prior the device cannot evaluate: the slot fails (status, NaN)
-        __syncthreads();
-        static_assert(sizeof(rgb::Prep) % 8 == 0 && sizeof(rgb::RowIn) % 8 == 0, "copied as doubles");
-        const double *src = (const double *)&sP;
-        double *dst = (double *)&rs.preps[rb];
-        for (int i = tid; i < (int)(sizeof(rgb::Prep) / 8); i += FB) dst[i] = src[i];
-        src = (const double *)&sR;
-        dst = (double *)&rs.rows[rb];
-        for (int i = tid; i < (int)(sizeof(rgb::RowIn) / 8); i += FB) dst[i] = src[i];
-        for (int i = tid; i < s_hn[1] && i < a.desc.stride; i += FB) a.T.noise[(size_t)slot * a.desc.stride + i] = s_noise[i];
         if (tid == 0) {
-            a.T.nh[slot] = s_hn[0];
-            a.T.nn[slot] = s_hn[1];
+            if (F.stp != TAMCMC_OK) { rs.preps[rb].status = F.stp; rs.rows[rb].status = F.stp; }
+            rgb::front_reset(rs, rb);
         }
+    } else {
+        if (tid == 0 && F.stp != TAMCMC_OK) { F.P.status = F.stp; F.R.status = F.stp; }
+        __syncthreads();
+        rgb::front_publish<FB>(F, rs, rb, slot, a.desc.stride, a.T.noise, a.T.nh, a.T.nn);
     }
-    if (tid == 0) {
-        rs.norm_bits[rb] = 0ull;
-        rs.nsol[rb] = 0;
-        a.logPr_plus[slot] = lp;
-    }
+    if (tid == 0) a.logPr_plus[slot] = lp;
     // the log-prior at theta - h e_k: only where the forward point lies outside a prior's support (as k_fd_unpack; workgroup-uniform)
     double lp_minus = 0.0;
     if (e > 0 && with_prior && !isfinite(lp)) {
@@ -217,6 +194,26 @@ __global__ void __launch_bounds__(FB) k_fd_rgb_perturb(const FdArgs a, const rgb
     if (tid == 0) a.logPr_minus[slot] = lp_minus;
 }
 
+// The base launch's index (C evaluations, model rows written): chain c's ranges, counts and noise row are those of its base slot c*E --
+// the launch reads the SAME table rows.  By one workgroup of NT lanes.
+template <int NT>
+__device__ __forceinline__ void write_base_index(const FdArgs &a, int c, int tid) {
+    const int slot = c * a.E, stride = a.desc.stride;
+    if (tid == 0) {
+        a.Bs.pairs[2 * c] = a.T.pairs[2 * slot];
+        a.Bs.pairs[2 * c + 1] = a.T.pairs[2 * slot + 1];
+        a.Bs.nh[c] = a.T.nh[slot];
+        a.Bs.nn[c] = a.T.nn[slot];
+    }
+    for (int i = tid; i < stride; i += NT) a.Bs.noise[(size_t)c * stride + i] = a.T.noise[(size_t)slot * stride + i];
+}
+
+// An empty delta entry: no row, no bin, the slot's class in d_flags (0, or ADJ_RGB_FLAG_LINEAR for a slot the adjoint contracts).  One lane.
+__device__ __forceinline__ void write_empty_delta(const FdArgs &a, int slot, int c, int flags) {
+    a.D.pairs[2 * slot] = 0; a.D.pairs[2 * slot + 1] = 0; a.D.nh[slot] = 0; a.D.nn[slot] = 1;
+    a.d_range[2 * slot] = 0; a.d_range[2 * slot + 1] = 0; a.d_flags[slot] = flags; a.d_row[slot] = c;
+}
+
 // Windowed mode, after the tables: one workgroup per slot compares slot e's finished table with the chain's base table row by row and writes
 // the delta launch's input -- it reads two tables and does not care which builder made them.  The tables may differ in length (a red-giant
 // perturbation can change the number of mixed modes: every row after the first difference then differs, and the rows beyond the end of the
@@ -226,17 +223,9 @@ __global__ void __launch_bounds__(FB) k_fd_compare(const FdArgs a) {
     const int B = a.C * a.E, per = a.desc.per, stride = a.desc.stride;
     __shared__ int s_lo, s_hi, s_noise_chg, s_nrows, s_wtot[FB / 64], s_moved;
     if (e == 0) {
-        // base evaluation of chain c: the base launch (B = C, model rows written) reads the SAME table rows
-        if (tid == 0) {
-            a.Bs.pairs[2 * c] = a.T.pairs[2 * slot];
-            a.Bs.pairs[2 * c + 1] = a.T.pairs[2 * slot + 1];
-            a.Bs.nh[c] = a.T.nh[slot];
-            a.Bs.nn[c] = a.T.nn[slot];
-            // no delta work for this slot
-            a.D.pairs[2 * slot] = 0; a.D.pairs[2 * slot + 1] = 0; a.D.nh[slot] = 0; a.D.nn[slot] = 1;
-            a.d_range[2 * slot] = 0; a.d_range[2 * slot + 1] = 0; a.d_flags[slot] = 0; a.d_row[slot] = c;
-        }
-        for (int i = tid; i < stride; i += FB) a.Bs.noise[(size_t)c * stride + i] = a.T.noise[(size_t)slot * stride + i];
+        // base evaluation of chain c: its entry of the base launch's index, and no delta work for this slot
+        write_base_index<FB>(a, c, tid);
+        if (tid == 0) write_empty_delta(a, slot, c, 0);
         return;
     }
     // ---- delta table: the multiplets whose row differs from the base row, +new / -old, and the affected bin range ----
@@ -255,10 +244,7 @@ __global__ void __launch_bounds__(FB) k_fd_compare(const FdArgs a) {
         }
         __syncthreads();
         if (same && !s_moved) {
-            if (tid == 0) {
-                a.D.pairs[2 * slot] = 0; a.D.pairs[2 * slot + 1] = 0; a.D.nh[slot] = 0; a.D.nn[slot] = 1;
-                a.d_range[2 * slot] = 0; a.d_range[2 * slot + 1] = 0; a.d_flags[slot] = ADJ_RGB_FLAG_LINEAR; a.d_row[slot] = c;
-            }
+            if (tid == 0) write_empty_delta(a, slot, c, ADJ_RGB_FLAG_LINEAR);
             return;
         }
     }
@@ -359,17 +345,8 @@ __global__ void __launch_bounds__(FB) k_fd_compare(const FdArgs a) {
     }
 }
 
-// Adjoint route: the base launch's ranges / counts / noise rows by chain -- what k_fd_compare's e = 0 workgroups write in the windowed route.
-__global__ void __launch_bounds__(64) k_adj_base(const FdArgs a) {
-    const int c = blockIdx.x, slot = c * a.E, tid = threadIdx.x;
-    if (tid == 0) {
-        a.Bs.pairs[2 * c] = a.T.pairs[2 * slot];
-        a.Bs.pairs[2 * c + 1] = a.T.pairs[2 * slot + 1];
-        a.Bs.nh[c] = a.T.nh[slot];
-        a.Bs.nn[c] = a.T.nn[slot];
-    }
-    for (int i = tid; i < a.desc.stride; i += 64) a.Bs.noise[(size_t)c * a.desc.stride + i] = a.T.noise[(size_t)slot * a.desc.stride + i];
-}
+// Adjoint route: the base launch's index and nothing else -- there are no delta tables for k_fd_compare to write.
+__global__ void __launch_bounds__(64) k_adj_base(const FdArgs a) { write_base_index<64>(a, blockIdx.x, threadIdx.x); }
 }  // namespace
 }  // namespace tamcmc
 
@@ -382,8 +359,6 @@ using namespace tamcmc;
 // fd_run() is the host entry: upload, enqueue, download, gradient assembly.
 namespace tamcmc {
 
-static size_t al16(size_t v) { return (v + 15) & ~(size_t)15; }
-static bool is_rgb_model(int id) { return id == TAMCMC_MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4_ID || id == TAMCMC_MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4_ID; }
 
 int FdBatch::layout(tamcmc_hip_ctx *c, Request request, int model_id_, int prior_class_, int C_, int64_t Nparams, const int32_t *plength, int Nvars_) {
     model_id = model_id_; prior_class = prior_class_; C = C_; Np = Nparams; Nvars = Nvars_;
@@ -409,20 +384,8 @@ int FdBatch::layout(tamcmc_hip_ctx *c, Request request, int model_id_, int prior
         stride = plength[8] > 0 ? plength[8] : 1;
         if ((stride - 1) / 3 > TAMCMC_MAX_HARVEY) return TAMCMC_ERR_BAD_ARG;
     }
-    const size_t Nv = (size_t)Nvars;
-    size_t o = 0;
-    o_params = o; o = al16(o + (size_t)C * Np * 8);
-    o_h = o; o = al16(o + Nv * 8);
-    o_pr = o; o = al16(o + 4 * (size_t)Np * 8);
-    o_ex = o; o = al16(o + 10 * 8);
-    o_pl = o; o = al16(o + 11 * 4);
-    o_idx = o; o = al16(o + Nv * 4);
-    o_sw = o; o = al16(o + (size_t)Np * 4);
-    in_bytes = o;
-    o_lpp = o; o = al16(o + (size_t)B * 8);
-    o_lpm = o; o = al16(o + (size_t)B * 8);
-    o_st = o; o = al16(o + (size_t)B * 4);
-    out_bytes = o - in_bytes;
+    head = FdBlockHead(C, Np, Nvars);
+    size_t o = head.in_bytes + head.out_bytes;
     const int nslots = table_slots();
     const StageLayout L(nslots, stride, (size_t)nslots * per);
     o_tab = o; o = al16(o + L.bytes);
@@ -556,14 +519,14 @@ int FdBatch::enqueue(tamcmc_hip_ctx *c, unsigned char *db, const double *d_param
     fa.desc.model_id = model_id; fa.desc.prior_class = prior_class; fa.desc.Np = (int)Np; fa.desc.per = per;
     fa.desc.stride = stride; fa.desc.Nx = (int)c->Nx;
     fa.desc.x_first = c->hx[0]; fa.desc.x_last = c->hx[(size_t)c->Nx - 1]; fa.desc.step = c->hx[1] - c->hx[0];
-    fa.desc.plength = (const int *)(db + o_pl); fa.desc.priors_switch = (const int *)(db + o_sw);
-    fa.desc.priors = (const double *)(db + o_pr); fa.desc.extra = (const double *)(db + o_ex); fa.desc.poly = c->d_poly.p;
+    fa.desc.plength = (const int *)(db + head.o_pl); fa.desc.priors_switch = (const int *)(db + head.o_sw);
+    fa.desc.priors = (const double *)(db + head.o_pr); fa.desc.extra = (const double *)(db + head.o_ex); fa.desc.poly = c->d_poly.p;
     const StageLayout L(table_slots(), stride, (size_t)table_slots() * per);
     fa.T = table_ptrs(db + o_tab, L);
     fa.C = C; fa.E = E; fa.Nv = Nvars;
-    fa.params = d_params ? d_params : (const double *)(db + o_params);
-    fa.idx = (const int *)(db + o_idx); fa.h = (const double *)(db + o_h);
-    fa.logPr_plus = (double *)(db + o_lpp); fa.logPr_minus = (double *)(db + o_lpm); fa.status = (int *)(db + o_st);
+    fa.params = d_params ? d_params : (const double *)(db + head.o_params);
+    fa.idx = (const int *)(db + head.o_idx); fa.h = (const double *)(db + head.o_h);
+    fa.logPr_plus = (double *)(db + head.o_lpp); fa.logPr_minus = (double *)(db + head.o_lpm); fa.status = (int *)(db + head.o_st);
     fa.windowed = windowed ? 1 : 0;
     fa.base_copies = rgb ? 0 : 1;
     fa.hybrid = hybrid() ? 1 : 0;
@@ -687,16 +650,6 @@ hipError_t FdBatch::delta_stats(const unsigned char *db, long *bins, long *full)
     return e;
 }
 
-int fd_ensure_poly(tamcmc_hip_ctx *c) {
-    if (!c->poly_ready) {
-        HIPCHK(c, c->d_poly.reserve(sizeof(mt::PolyTab)));
-        hipLaunchKernelGGL(k_fill_poly_fd, dim3(1), dim3(64), 0, c->stream, (mt::PolyTab *)c->d_poly.p);
-        HIPCHK(c, hipGetLastError());
-        c->poly_ready = true;
-    }
-    return TAMCMC_OK;
-}
-
 int check_gradient_args(const tamcmc_hip_ctx *c, int C, const double *params, int64_t Nparams, const int32_t *plength,
                         const int32_t *index_to_relax, int Nvars, const double *hstep, bool rest_ok, unsigned rules) {
     const bool need_pl = rules & GA_PLENGTH, vars = rules & GA_VARS, fisher = rules & GA_FISHER;
@@ -767,8 +720,9 @@ int assemble_gradient(int C, int Nvars, const double *params, int64_t Nparams, c
 // STRICT keeps the reference's arithmetic for a red giant's scalar unpack too: long double on the host, exactly what
 // tamcmc_hip_loglike_params_batch does with the same vector -- a vector's STRICT logL is the same bits from either entry.  Fills the
 // context's pinned h_rgb / h_stage for the B vectors and points the batch at them.
-static int rgb_host_unpack(tamcmc_hip_ctx *c, FdBatch &fb, const double *params, const int32_t *plength, const int32_t *index_to_relax,
-                           const double *hstep) {
+static int rgb_host_unpack(tamcmc_hip_ctx *c, FdBatch &fb, const FdInputs &in) {
+    const double *params = in.params, *hstep = in.hstep;
+    const int32_t *plength = in.plength, *index_to_relax = in.index_to_relax;
     const int E = fb.E, B = fb.B;
     const size_t Np = (size_t)fb.Np;
     const size_t bytes_prep = ((size_t)B * sizeof(rgb::Prep) + 15) & ~(size_t)15;
@@ -801,6 +755,34 @@ static int rgb_host_unpack(tamcmc_hip_ctx *c, FdBatch &fb, const double *params,
     return TAMCMC_OK;
 }
 
+int tamcmc::FdBatch::begin(tamcmc_hip_ctx *c, const FdInputs &in, unsigned char **block) {
+    HIPCHK(c, c->h_fd.reserve(head.in_bytes + head.out_bytes));
+    HIPCHK(c, c->d_fd.reserve(total_bytes));
+    head.stage(c->h_fd.p, in);
+    HIPCHK(c, hipMemcpyAsync(c->d_fd.p, c->h_fd.p, head.in_bytes, hipMemcpyHostToDevice, c->stream));
+    if (rgb && c->precision == TAMCMC_PRECISION_STRICT)
+        if (int rc = rgb_host_unpack(c, *this, in)) return rc;
+    if (!tables_only) HIPCHK(c, reserve(c, context_buffers(c)));
+    *block = c->d_fd.p;
+    return TAMCMC_OK;
+}
+
+int tamcmc::FdBatch::finish(tamcmc_hip_ctx *c, FdResults *out) {
+    HIPCHK(c, hipMemcpyAsync(c->h_fd.p + head.in_bytes, c->d_fd.p + head.in_bytes, head.out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *out = head.results(c->h_fd.p);
+    return TAMCMC_OK;
+}
+
+// What a host entry passes on to the block: the prior's arrays only where there is a prior (no kernel reads them otherwise)
+static FdInputs host_inputs(int prior_class, const double *params, const int32_t *plength, const int32_t *index_to_relax, const double *hstep,
+                            const double *priors, const int32_t *priors_switch, const double *extra_priors) {
+    FdInputs in;
+    in.params = params; in.plength = plength; in.index_to_relax = index_to_relax; in.hstep = hstep;
+    if (prior_class != 0) { in.priors = priors; in.priors_switch = priors_switch; in.extra_priors = extra_priors; }
+    return in;
+}
+
 static int fd_run(tamcmc_hip_ctx *c, int model_id, int prior_class, int C, const double *params, int64_t Nparams,
                   const int32_t *plength, const int32_t *index_to_relax, int Nvars, const double *hstep, const double *Tcoefs,
                   double p, const double *priors, const int32_t *priors_switch, const double *extra_priors, double *logL0,
@@ -813,24 +795,10 @@ static int fd_run(tamcmc_hip_ctx *c, int model_id, int prior_class, int C, const
     hipStream_t st = c->stream;
     FdBatch fb;
     if ((rc = fb.layout(c, FdBatch::Request::FromOptions, model_id, prior_class, C, Nparams, plength, Nvars))) return rc;
-    if ((rc = fd_ensure_poly(c))) return rc;
-    const size_t Np = (size_t)Nparams, Nv = (size_t)Nvars, nS = fb.ws.S;
-    HIPCHK(c, c->h_fd.reserve(fb.in_bytes + fb.out_bytes));
-    HIPCHK(c, c->d_fd.reserve(fb.total_bytes));
-    unsigned char *hb = c->h_fd.p, *db = c->d_fd.p;
-    std::memcpy(hb + fb.o_params, params, (size_t)C * Np * 8);
-    std::memcpy(hb + fb.o_h, hstep, Nv * 8);
-    if (prior_class != 0) {
-        std::memcpy(hb + fb.o_pr, priors, 4 * Np * 8);
-        std::memcpy(hb + fb.o_ex, extra_priors, 10 * 8);
-        std::memcpy(hb + fb.o_sw, priors_switch, Np * 4);
-    }
-    std::memcpy(hb + fb.o_pl, plength, 11 * 4);
-    std::memcpy(hb + fb.o_idx, index_to_relax, Nv * 4);
-    HIPCHK(c, hipMemcpyAsync(db, hb, fb.in_bytes, hipMemcpyHostToDevice, st));
-    if (fb.rgb && c->precision == TAMCMC_PRECISION_STRICT && (rc = rgb_host_unpack(c, fb, params, plength, index_to_relax, hstep))) return rc;
-    const FdBatch::Buffers w{c->d_part, c->d_S, c->d_model, c->d_bg};
-    HIPCHK(c, fb.reserve(c, w));
+    if ((rc = ensure_poly(c))) return rc;
+    const size_t nS = fb.ws.S;
+    unsigned char *db;
+    if ((rc = fb.begin(c, host_inputs(prior_class, params, plength, index_to_relax, hstep, priors, priors_switch, extra_priors), &db))) return rc;
     HIPCHK(c, c->h_S.reserve(nS));
     hipEvent_t *split = nullptr;
     if (c->timing && fb.hybrid()) {  // slot counters and the stage split of the hybrid batch (tamcmc_hip_get_rgb_adjoint_stats / _times)
@@ -838,12 +806,12 @@ static int fd_run(tamcmc_hip_ctx *c, int model_id, int prior_class, int C, const
             if (!e) HIPCHK(c, hipEventCreate(&e));
         split = c->ev_split;
         fb.count_slots = true;
-        HIPCHK(c, hipMemsetAsync(db + fb.o_adjcount, 0, 16, st));
+        HIPCHK(c, fb.zero_slot_counts(c, db));
     }
-    if ((rc = fb.enqueue(c, db, nullptr, w, c->timing ? c->ev0 : nullptr, c->timing ? c->ev1 : nullptr, split))) return rc;
+    if ((rc = fb.enqueue(c, db, c->timing ? c->ev0 : nullptr, c->timing ? c->ev1 : nullptr, split))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->h_S.p, c->d_S.p, nS * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(hb + fb.in_bytes, db + fb.in_bytes, fb.out_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
+    FdResults res;
+    if ((rc = fb.finish(c, &res))) return rc;
     if (c->timing) {
         float ms = 0;
         HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
@@ -870,8 +838,7 @@ static int fd_run(tamcmc_hip_ctx *c, int model_id, int prior_class, int C, const
         }
     }
     return assemble_gradient(C, Nvars, params, Nparams, index_to_relax, hstep, Tcoefs, p, c->h_S.p, fb.deltas(),
-                             prior_class != 0 ? (const double *)(hb + fb.o_lpp) : nullptr, (const double *)(hb + fb.o_lpm),
-                             (const int *)(hb + fb.o_st), logL0, logPr0, grad, grad_prior);
+                             prior_class != 0 ? res.lpp : nullptr, res.lpm, res.status, logL0, logPr0, grad, grad_prior);
 }
 
 extern "C" {
@@ -930,26 +897,15 @@ int tamcmc_hip_adjoint_table(tamcmc_hip_ctx *c, int model_id, int C, const doubl
     if ((rc = fb.layout(c, FdBatch::Request::Adjoint, model_id, 0, C > 0 ? C : 1, Nparams, plength, 0))) return rc;
     if (nrows) *nrows = fb.per;
     if (C == 0) return TAMCMC_OK;
-    if ((rc = fd_ensure_poly(c))) return rc;
-    const size_t Np = (size_t)Nparams;
-    HIPCHK(c, c->h_fd.reserve(fb.in_bytes + fb.out_bytes));
-    HIPCHK(c, c->d_fd.reserve(fb.total_bytes));
-    unsigned char *hb = c->h_fd.p, *db = c->d_fd.p;
-    std::memset(hb, 0, fb.in_bytes);
-    std::memcpy(hb + fb.o_params, params, (size_t)C * Np * 8);
-    std::memcpy(hb + fb.o_pl, plength, 11 * 4);
-    HIPCHK(c, hipMemcpyAsync(db, hb, fb.in_bytes, hipMemcpyHostToDevice, st));
-    const FdBatch::Buffers w{c->d_part, c->d_S, c->d_model, c->d_bg};
-    HIPCHK(c, fb.reserve(c, w));
-    if ((rc = fb.enqueue(c, db, nullptr, w, nullptr, nullptr))) return rc;
+    if ((rc = ensure_poly(c))) return rc;
+    unsigned char *db;
+    if ((rc = fb.begin(c, host_inputs(0, params, plength, nullptr, nullptr, nullptr, nullptr, nullptr), &db))) return rc;
+    if ((rc = fb.enqueue(c, db))) return rc;
     if (G) HIPCHK(c, hipMemcpyAsync(G, db + fb.o_adjG, (size_t)C * fb.per * ADJ_F * 8, hipMemcpyDeviceToHost, st));
     if (Gn) HIPCHK(c, hipMemcpyAsync(Gn, db + fb.o_adjGn, (size_t)C * fb.stride * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(hb + fb.in_bytes, db + fb.in_bytes, fb.out_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    const int *stt = (const int *)(hb + fb.o_st);
-    for (int ch = 0; ch < C; ch++)
-        if (stt[ch] != TAMCMC_OK) return stt[ch];  // (that chain's G and Gn are zero)
-    return TAMCMC_OK;
+    FdResults res;
+    if ((rc = fb.finish(c, &res))) return rc;
+    return res.first_status();  // (a failed chain's G and Gn are zero)
 }
 
 // The audit entries' common body: the tables of the B = C (Nvars + 1) vectors as the batch's own builder leaves them and nothing after them
@@ -967,25 +923,11 @@ static int batch_tables(tamcmc_hip_ctx *c, int model_id, int prior_class, int C,
     if ((rc = fb.layout(c, FdBatch::Request::Tables, model_id, prior_class, C > 0 ? C : 1, Nparams, plength, Nvars))) return rc;
     if (per) *per = fb.per;
     if (C == 0) return TAMCMC_OK;
-    if ((rc = fd_ensure_poly(c))) return rc;
-    const size_t Np = (size_t)Nparams, Nv = (size_t)Nvars, B = (size_t)fb.B;
-    HIPCHK(c, c->h_fd.reserve(fb.in_bytes + fb.out_bytes));
-    HIPCHK(c, c->d_fd.reserve(fb.total_bytes));
-    unsigned char *hb = c->h_fd.p, *db = c->d_fd.p;
-    std::memset(hb, 0, fb.in_bytes);
-    std::memcpy(hb + fb.o_params, params, (size_t)C * Np * 8);
-    std::memcpy(hb + fb.o_h, hstep, Nv * 8);
-    if (prior_class != 0) {
-        std::memcpy(hb + fb.o_pr, priors, 4 * Np * 8);
-        std::memcpy(hb + fb.o_ex, extra_priors, 10 * 8);
-        std::memcpy(hb + fb.o_sw, priors_switch, Np * 4);
-    }
-    std::memcpy(hb + fb.o_pl, plength, 11 * 4);
-    std::memcpy(hb + fb.o_idx, index_to_relax, Nv * 4);
-    HIPCHK(c, hipMemcpyAsync(db, hb, fb.in_bytes, hipMemcpyHostToDevice, st));
-    if (fb.rgb && c->precision == TAMCMC_PRECISION_STRICT && (rc = rgb_host_unpack(c, fb, params, plength, index_to_relax, hstep))) return rc;
-    const FdBatch::Buffers w{c->d_part, c->d_S, c->d_model, c->d_bg};
-    if ((rc = fb.enqueue(c, db, nullptr, w, nullptr, nullptr))) return rc;
+    if ((rc = ensure_poly(c))) return rc;
+    const size_t B = (size_t)fb.B;
+    unsigned char *db;
+    if ((rc = fb.begin(c, host_inputs(prior_class, params, plength, index_to_relax, hstep, priors, priors_switch, extra_priors), &db))) return rc;
+    if ((rc = fb.enqueue(c, db))) return rc;
     const StageLayout L((int)B, fb.stride, B * fb.per);
     const unsigned char *tb = db + fb.o_tab;
     std::vector<int32_t> pairs(2 * B);
@@ -994,16 +936,13 @@ static int batch_tables(tamcmc_hip_ctx *c, int model_id, int prior_class, int C,
     if (noise) HIPCHK(c, hipMemcpyAsync(noise, tb + L.off_noise, B * fb.stride * 8, hipMemcpyDeviceToHost, st));
     if (nharvey) HIPCHK(c, hipMemcpyAsync(nharvey, tb + L.off_nh, B * 4, hipMemcpyDeviceToHost, st));
     if (nnoise) HIPCHK(c, hipMemcpyAsync(nnoise, tb + L.off_nn, B * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(hb + fb.in_bytes, db + fb.in_bytes, fb.out_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    const int *stt = (const int *)(hb + fb.o_st);
-    rc = TAMCMC_OK;
+    FdResults res;
+    if ((rc = fb.finish(c, &res))) return rc;
     for (size_t s = 0; s < B; s++) {
         if (nrows) nrows[s] = pairs[2 * s + 1] - pairs[2 * s];
-        if (status) status[s] = stt[s];
-        if (rc == TAMCMC_OK) rc = stt[s];
+        if (status) status[s] = res.status[s];
     }
-    return rc;
+    return res.first_status();
 }
 
 int tamcmc_hip_rgb_batch_tables(tamcmc_hip_ctx *c, int model_id, int C, const double *params, int64_t Nparams, const int32_t *plength,

@@ -173,15 +173,14 @@ extern "C" {
 int tamcmc_hip_fisher(tamcmc_hip_ctx *c, int model_id, int C, const double *params, int64_t Nparams, const int32_t *plength,
                       const int32_t *index_to_relax, int Nvars, const double *hstep, const double *Tcoefs, double p, double *F) {
     if (!c) return TAMCMC_ERR_BAD_ARG;
-    if (is_envelope_model(model_id) || model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4 || model_id == TAMCMC_MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4)
-        return TAMCMC_ERR_BAD_MODEL;  // (no table / tables of variable length)
+    if (is_envelope_model(model_id) || is_rgb_model(model_id)) return TAMCMC_ERR_BAD_MODEL;  // (no table / tables of variable length)
     int rc = check_gradient_args(c, C, params, Nparams, plength, index_to_relax, Nvars, hstep, F != nullptr, GA_PLENGTH | GA_VARS | GA_FISHER);
     if (rc) return rc;
     if (c->precision == TAMCMC_PRECISION_STRICT) return TAMCMC_ERR_BAD_ARG;  // (as the adjoint route)
     if (C == 0) return TAMCMC_OK;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    rc = fd_ensure_poly(c);
+    rc = ensure_poly(c);
     if (rc) return rc;
     const size_t Np = (size_t)Nparams, N = (size_t)Nvars, Nx = (size_t)c->Nx;
     const int NP = fisher_padded(Nvars), nslab = fisher_slabs((long)c->Nx);
@@ -207,23 +206,20 @@ int tamcmc_hip_fisher(tamcmc_hip_ctx *c, int model_id, int C, const double *para
         c->fisher_ms[0] = c->fisher_ms[1] = c->fisher_ms[2] = 0.0;
     }
     int first_err = TAMCMC_OK;
+    std::vector<double> h2(2 * N);  // [+h, -h]
+    std::vector<int32_t> idx2(2 * N);  // [index_to_relax, index_to_relax]
+    for (size_t k = 0; k < N; k++) {
+        h2[k] = hstep[k]; h2[N + k] = -hstep[k];
+        idx2[k] = idx2[N + k] = index_to_relax[k];
+    }
     auto pass = [&](int c0, int cp) -> int {
         FdBatch fb;
         int r = fb.layout(c, FdBatch::Request::Rows, model_id, 0, cp, Nparams, plength, 2 * Nvars);
         if (r) return r;
-        HIPCHK(c, c->h_fd.reserve(fb.in_bytes + fb.out_bytes));
-        HIPCHK(c, c->d_fd.reserve(fb.total_bytes));
-        unsigned char *hb = c->h_fd.p, *db = c->d_fd.p;
-        std::memset(hb, 0, fb.in_bytes);
-        std::memcpy(hb + fb.o_params, params + (size_t)c0 * Np, (size_t)cp * Np * 8);
-        double *h2 = (double *)(hb + fb.o_h);
-        int32_t *idx2 = (int32_t *)(hb + fb.o_idx);
-        for (size_t k = 0; k < N; k++) {
-            h2[k] = hstep[k]; h2[N + k] = -hstep[k];
-            idx2[k] = idx2[N + k] = index_to_relax[k];
-        }
-        std::memcpy(hb + fb.o_pl, plength, 11 * 4);
-        HIPCHK(c, hipMemcpyAsync(db, hb, fb.in_bytes, hipMemcpyHostToDevice, st));
+        FdInputs in;  // (Route::Rows: the doubled arrays h2, idx2)
+        in.params = params + (size_t)c0 * Np; in.hstep = h2.data(); in.index_to_relax = idx2.data(); in.plength = plength;
+        unsigned char *db;
+        if ((r = fb.begin(c, in, &db))) return r;
         // 1 / h_applied (the difference of the two perturbed doubles as stored; the device adds the same doubles) and the temperatures
         const size_t n_rh = (size_t)cp * N, n_F = (size_t)cp * N * N, n_part = (size_t)cp * nslab * NP * NP;
         HIPCHK(c, c->h_S.reserve(n_rh + cp));
@@ -238,21 +234,19 @@ int tamcmc_hip_fisher(tamcmc_hip_ctx *c, int model_id, int C, const double *para
         HIPCHK(c, c->d_fisher.reserve(n_rh + cp + n_F + n_part));
         double *d_rh = c->d_fisher.p, *d_T = d_rh + n_rh, *d_F = d_T + cp, *d_part = d_F + n_F;
         HIPCHK(c, hipMemcpyAsync(d_rh, c->h_S.p, (n_rh + cp) * 8, hipMemcpyHostToDevice, st));
-        const FdBatch::Buffers w{c->d_part, c->d_S, c->d_model, c->d_bg};
-        HIPCHK(c, fb.reserve(c, w));
         if (c->timing) HIPCHK(c, hipEventRecord(ev[0], st));
-        r = fb.enqueue(c, db, nullptr, w, c->timing ? c->ev0 : nullptr, c->timing ? c->ev1 : nullptr);
+        r = fb.enqueue(c, db, c->timing ? c->ev0 : nullptr, c->timing ? c->ev1 : nullptr);
         if (r) return r;
         GramArgs g;
         g.M0 = c->d_model.p; g.P = g.M0 + Nx; g.Mn = g.M0 + (1 + N) * Nx; g.rh = d_rh;
         g.set = (size_t)fb.E * Nx;
         g.C = cp; g.N = Nvars; g.NP = NP; g.nslab = nslab; g.K = (long)c->Nx;
-        g.part = d_part; g.T = d_T; g.p = (double)(long)p; g.status = (const int *)(db + fb.o_st); g.E = fb.E; g.F = d_F;
+        g.part = d_part; g.T = d_T; g.p = (double)(long)p; g.status = fb.head.results(db).status; g.E = fb.E; g.F = d_F;
         HIPCHK(c, launch_fisher_gram(g, st));
         if (c->timing) HIPCHK(c, hipEventRecord(ev[1], st));
         HIPCHK(c, hipMemcpyAsync(F + (size_t)c0 * N * N, d_F, n_F * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(hb + fb.in_bytes, db + fb.in_bytes, fb.out_bytes, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
+        FdResults res;
+        if ((r = fb.finish(c, &res))) return r;
         if (c->timing) {
             float ms[3] = {0, 0, 0};
             HIPCHK(c, hipEventElapsedTime(&ms[0], ev[0], c->ev0));
@@ -260,9 +254,7 @@ int tamcmc_hip_fisher(tamcmc_hip_ctx *c, int model_id, int C, const double *para
             HIPCHK(c, hipEventElapsedTime(&ms[2], c->ev1, ev[1]));
             for (int i = 0; i < 3; i++) c->fisher_ms[i] += ms[i];
         }
-        const int *stt = (const int *)(hb + fb.o_st);
-        for (int s = 0; s < fb.B && first_err == TAMCMC_OK; s++)
-            if (stt[s] != TAMCMC_OK) first_err = stt[s];
+        if (first_err == TAMCMC_OK) first_err = res.first_status();
         return TAMCMC_OK;
     };
     for (int c0 = 0; c0 < C && rc == TAMCMC_OK; c0 += chunk) rc = pass(c0, C - c0 < chunk ? C - c0 : chunk);

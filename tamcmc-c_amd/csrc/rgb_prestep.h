@@ -11,6 +11,12 @@
 #define TAMCMC_MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4_ID 27
 
 namespace tamcmc {
+// the models whose table needs the mixed-mode solver (constexpr: host and device)
+constexpr bool is_rgb_model(int id) { return id == TAMCMC_MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4_ID || id == TAMCMC_MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4_ID; }
+// Pslm/Qlm polynomial tables, computed ON the device (its own double arithmetic).  fill_poly_table: into d_poly (an mt::PolyTab in device
+// memory), on st.  ensure_poly: the context's table c->d_poly, once (shared by the red-giant pre-step and the gradient batches)
+hipError_t fill_poly_table(void *d_poly, hipStream_t st);
+int ensure_poly(tamcmc_hip_ctx *c);
 // Builds the B variable-length tables in the DEVICE staging block c->d_stage (layout StageLayout(B, stride, B*per)); status[b] per vector;
 // tile_rot = launch-order hint for k_loglike.
 int rgb_stage_params(tamcmc_hip_ctx *c, int model_id, int B, const double *params, int64_t Nparams, const int32_t *plength, int32_t *status,

@@ -507,12 +507,26 @@ __global__ void __launch_bounds__(WG) k_rgb_finish(const Prep *preps, const RowI
     }
 }
 
-__global__ void k_fill_poly_rgb(mt::PolyTab *t) {
+__global__ void k_fill_poly(mt::PolyTab *t) {
     if (threadIdx.x == 0 && blockIdx.x == 0) mt::fill_poly(*t);
 }
 
 }  // namespace
 }  // namespace rgb
+
+hipError_t fill_poly_table(void *d_poly, hipStream_t st) {
+    hipLaunchKernelGGL(rgb::k_fill_poly, dim3(1), dim3(64), 0, st, (mt::PolyTab *)d_poly);
+    return hipGetLastError();
+}
+
+int ensure_poly(tamcmc_hip_ctx *c) {
+    if (!c->poly_ready) {
+        HIPCHK(c, c->d_poly.reserve(sizeof(mt::PolyTab)));
+        HIPCHK(c, fill_poly_table(c->d_poly.p, c->stream));
+        c->poly_ready = true;
+    }
+    return TAMCMC_OK;
+}
 
 // Builds the B tables of model 25 / 27 in the DEVICE staging block c->d_stage (layout StageLayout(B, stride, B*per), the one run_staged
 // launches on); only the small header (counts, noise rows) goes through the host block.  One stream synchronisation (for the
@@ -566,11 +580,7 @@ int rgb_stage_params(tamcmc_hip_ctx *c, int model_id, int B, const double *param
     double *d_fl1 = d_sols + nsolbuf, *d_ksi = d_fl1 + nsolbuf;
     unsigned long long *d_norm = (unsigned long long *)(d_ksi + nsolbuf);
     int *d_nsol = (int *)(d_norm + B), *d_status = d_nsol + B;
-    if (!c->poly_ready) {  // Pslm/Qlm tables in device memory (shared with the finite-difference builder)
-        HIPCHK(c, c->d_poly.reserve(sizeof(mt::PolyTab)));
-        hipLaunchKernelGGL(k_fill_poly_rgb, dim3(1), dim3(64), 0, st, (mt::PolyTab *)c->d_poly.p);
-        c->poly_ready = true;
-    }
+    if (int rc = ensure_poly(c)) return rc;
     HIPCHK(c, hipMemcpyAsync(c->d_stage.p, c->h_stage.p, L.off_mults, hipMemcpyHostToDevice, st));  // header only
     HIPCHK(c, hipMemcpyAsync(d_prep, P, bytes_prep + bytes_rows, hipMemcpyHostToDevice, st));  // Prep and RowIn arrays, contiguous on both sides
     HIPCHK(c, hipMemsetAsync(d_norm, 0, (size_t)B * (sizeof(unsigned long long) + 2 * sizeof(int)), st));
@@ -608,11 +618,7 @@ int rgb_device_prepare(tamcmc_hip_ctx *c, int Bmax, int slices, const int32_t *p
     if ((stride - 1) / 3 > TAMCMC_MAX_HARVEY) return TAMCMC_ERR_BAD_ARG;
     if (plength[2] > MAXL || plength[4] > MAXL || plength[5] > MAXL || plength[2] < 2) return TAMCMC_ERR_BAD_ARG;
     HIPCHK(c, c->d_rgb.reserve(rgb_slice_bytes(Bmax) * (size_t)slices));
-    if (!c->poly_ready) {
-        HIPCHK(c, c->d_poly.reserve(sizeof(mt::PolyTab)));
-        hipLaunchKernelGGL(k_fill_poly_rgb, dim3(1), dim3(64), 0, c->stream, (mt::PolyTab *)c->d_poly.p);
-        c->poly_ready = true;
-    }
+    if (int rc = ensure_poly(c)) return rc;
     *per_out = plength[2] + plength[4] + plength[5] + CAP1;
     *stride_out = stride;
     return TAMCMC_OK;
