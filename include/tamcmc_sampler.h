@@ -122,7 +122,9 @@ int64_t tamcmc_sampler_nvars(const tamcmc_sampler *s);
                                           on the moved boundary of a window) */
 #define TAMCMC_INFO_ITER_WINDOW 13     /* ... and iterations run as two launches with the boundary between the groups moved by one chain
                                           (the iteration of a swap pair that straddles the groups, and the next) */
-#define TAMCMC_SAMPLER_INFO_N 14
+#define TAMCMC_INFO_QUICK_MISMATCH 14  /* tests that the decision shortcut decided OTHERWISE than the exact evaluation: every commit
+                                          workgroup asks both.  0 -- anything else is a defect of the shortcut */
+#define TAMCMC_SAMPLER_INFO_N 15
 int tamcmc_sampler_get_info(const tamcmc_sampler *s, int64_t *info, int32_t n);
 
 /* Advances all chains by n_iter iterations.  Optional outputs, one record per iteration after the swap step

@@ -84,7 +84,8 @@ class DevSampler {
     // [5] iterations run fused [6] iterations run by the lockstep kernels [7] chains [8] fused stretches
     // [9] quick_decide fallbacks taken by the likelihood tiles [10] tile tests decided from a kind-2 record (outside a swap pair)
     // [11] of [5] with two chain groups: iterations run as one joint launch [12] ... run in a window (step_schedule.h: StepPlanner)
-    void info(long out[13]) const;
+    // [13] tests that quick_decide decided otherwise than the exact decide() (counted by the commit workgroups: 0, or a bug)
+    void info(long out[14]) const;
     // Audit (tamcmc_sampler_get_tables): the tables the last stretch of the last run() left in the likelihood kernel's input block and the
     // parameter vector each was built from, read from the engine's own buffers.  shape = {scheme, slots, rows per slot, noise stride}.
     // scheme 1 (lockstep): slot m = chain m's proposal of the last iteration, vector = params_prop of that iteration's parity;

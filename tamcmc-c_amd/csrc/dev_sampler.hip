@@ -11,7 +11,8 @@
 //         iteration i-1's test, and EVERY WORKGROUP DECIDES THAT FOR ITSELF at its start from what launch i-1 left in memory
 //         (quick_decide: the test as a threshold on the sum of the previous launch's partial sums; decide(), the test as written --
 //         MALA.cpp:397-461,490-551 -- when the sum is within rounding of the threshold).  Same inputs, same code in every workgroup: the
-//         same answer everywhere, no hand-off.  The tiles leave their two partial sums for launch i+1;
+//         same answer everywhere, no hand-off.  The tiles leave their two partial sums for launch i+1, and add their sum into their chain's
+//         accumulators (FusedArgs::qacc), which is what quick_decide reads;
 //       * commit workgroups, one wave per chain: the exact decide() of iteration i-1, then the chain's state of iteration i, the
 //         sample/stat record of iteration i-1, move flags and counters, and for launch i+1 the slot, prior, status and threshold
 //         record of the chain's proposal.  A launch of commit workgroups alone closes a stretch;
@@ -96,7 +97,7 @@ struct DevSampler::Impl {
     FdBatch fd;
     DevBuf<unsigned char> fd_block;
     DevBuf<double> fd_part, fd_S, fd_model, fd_bg;
-    DevBuf<double> fused_bg, fused_part, fused_psum;  // (A): the candidates' background series, the tiles' partial sums by parity and their per-tile sums (see run())
+    DevBuf<double> fused_bg, fused_part;  // (A): the candidates' background series, the tiles' partial sums by parity (see run())
     MalaArgs mala{};
     bool grad_valid = false;
     int prior_class = 0, model_id = 0;
@@ -204,7 +205,7 @@ DevSampler::~DevSampler() {
     }
 #endif
     for (void *p : impl->allocs) (void)hipFree(p);
-    impl->fd_block.release(); impl->fd_part.release(); impl->fd_S.release(); impl->fd_model.release(); impl->fd_bg.release(); impl->fused_bg.release(); impl->fused_part.release(); impl->fused_psum.release();
+    impl->fd_block.release(); impl->fd_part.release(); impl->fd_S.release(); impl->fd_model.release(); impl->fd_bg.release(); impl->fused_bg.release(); impl->fused_part.release();
     if (impl->h_pack) (void)hipHostFree(impl->h_pack);
     for (int i = 0; i < impl->n_ev; i++) { (void)hipEventDestroy(impl->ev[i][0]); (void)hipEventDestroy(impl->ev[i][1]); }
     for (int i = 0; i < impl->n_gev; i++) { (void)hipEventDestroy(impl->gev[i][0]); (void)hipEventDestroy(impl->gev[i][1]); }
@@ -349,15 +350,20 @@ int DevSampler::init(tamcmc_hip_ctx *c, const DevSamplerInit &in) {
         DCHK(I.dalloc(&f.mults, 3 * NS * (size_t)a.desc.per + 1)); DCHK(I.dalloc(&f.pairs, 6 * NS)); DCHK(I.dalloc(&f.nh, 3 * NS)); DCHK(I.dalloc(&f.nn, 3 * NS));
         DCHK(I.dalloc(&f.noise, 3 * NS * (size_t)a.desc.stride));
         DCHK(I.dalloc(&f.slot, 2 * C)); DCHK(I.dalloc(&f.prop_logPr, 2 * C)); DCHK(I.dalloc(&f.prop_st, 2 * C)); DCHK(I.dalloc(&f.quick, 2 * C * QN)); DCHK(I.dalloc(&f.lz, 2 * C * Nv));
-        DCHK(I.dalloc(&f.qcount, 2));
-        DCHK(hipMemsetAsync(f.qcount, 0, 2 * sizeof(unsigned long long), st));
+        DCHK(I.dalloc(&f.qcount, 3));
+        DCHK(hipMemsetAsync(f.qcount, 0, 3 * sizeof(unsigned long long), st));
+        // the tiles' per-chain accumulators: one 128-byte line per (set, chain) on a 128-byte boundary, zero between stretches -- once
+        // here, then by the commit workgroups (commit_chain); their size does not follow the tile geometry
+        static_assert(2 * QK * sizeof(double) == 128, "one line per (set, chain)");
+        DCHK(I.dalloc(&f.qacc, 3 * C * 2 * QK));
+        if (((uintptr_t)f.qacc & 127) != 0) return TAMCMC_ERR_HIP;
+        DCHK(hipMemset(f.qacc, 0, 3 * C * 2 * QK * sizeof(double)));
         f.qmargin = 1e-11;
         DCHK(hipMemsetAsync(f.nn, 0, 3 * NS * sizeof(int), st));
         DCHK(hipMemsetAsync(f.cand_stP, 0, 6 * NS * sizeof(int), st));
         DCHK(hipMemsetAsync(f.cand_rej, 0, 3 * NS * sizeof(int), st));
         DCHK(hipMemsetAsync(f.cand_stR, 0, 3 * NS * sizeof(int), st));
         f.part = nullptr;
-        f.psum = nullptr;
         f.bg = nullptr;
         // the candidate roles borrow the tile workgroup's LDS: a parameter vector too long for it keeps the lockstep scheme
         const size_t role_lds = (Np + 2 * Nv + 1) * sizeof(double) + unpack_lds_bytes() + 32;
@@ -429,11 +435,11 @@ int DevSampler::download_tables(int32_t shape[4], tamcmc_multiplet *rows, int32_
     return TAMCMC_OK;
 }
 
-void DevSampler::info(long out[13]) const {
+void DevSampler::info(long out[14]) const {
     const Impl &I = *impl;
-    unsigned long long qc[2] = {0, 0};  // (every entry point returns with the sampler's streams idle)
+    unsigned long long qc[3] = {0, 0, 0};  // (every entry point returns with the sampler's streams idle)
     if (I.f.qcount && hipSetDevice(I.ctx->device) == hipSuccess) (void)hipMemcpy(qc, I.f.qcount, sizeof qc, hipMemcpyDeviceToHost);
-    out[8] = I.n_stretch; out[9] = (long)qc[0]; out[10] = (long)qc[1];
+    out[8] = I.n_stretch; out[9] = (long)qc[0]; out[10] = (long)qc[1]; out[13] = (long)qc[2];
     out[0] = I.a.Nv; out[1] = I.a.desc.Np;
     out[2] = I.use_drift ? I.mala_chol_lds : I.a.chol_in_lds;
     out[3] = (I.fused_ok && !I.use_drift) ? 1 : 0;
@@ -732,8 +738,6 @@ struct DevSampler::Impl::RunCall {
         if (use_fused) {  // (A): the tiles' partial sums by iteration parity (launch i writes one half and reads the other)
             DCHK(I.fused_part.reserve(2 * C * (size_t)a.ntiles * 2));
             I.f.part = I.fused_part.p;
-            DCHK(I.fused_psum.reserve(2 * C * (size_t)a.ntiles));  // (written and read with `part`, tile by tile: valid wherever it is)
-            I.f.psum = I.fused_psum.p;
         }
         // (two groups pay once one launch no longer fits the GPU's resident waves -- 20 chains x 196 tiles: 27.7 -> 23.9 us, x 782 tiles:
         // 59.8 -> 49.6 us -- and cost below that: 8 chains x 196 tiles 20.5 -> 23.7 us, 20 chains x 20 tiles 33.5 -> 35.6 us;

@@ -27,15 +27,21 @@ struct FusedArgs {
     int *prop_st;                      // [2][C]   ... and status (prior role's, else rows role's)
     double *quick;                     // [2][C][QN] that iteration's MH and swap tests as thresholds on the sums of the partials (quick_decide)
     double *part;                      // [2][C][ntiles][2] the tiles' partial sums of that iteration
-    double *psum;                      // [2][C][ntiles]    part[..][0] + part[..][1], stored by the same lane beside them (quick_decide)
     double *lz;                        // [2][C][Nv] L z of chain m for the iteration of that parity, computed one launch ahead
+    // per chain, by the iteration mod 3 (like the candidate sets): the tiles of launch i ADD c = part[..][0] + part[..][1] and |c| into
+    // set i mod 3, launch i+1 reads that set (quick_decide), the chain's commit workgroup of launch i zeroes set (i+1) mod 3 -- last read
+    // by launch i-1 -- and the closing launch of a stretch all three.  128 bytes per (set, chain), 128-byte aligned: no two chains share a
+    // cache line.  QK keys only spread the atomics over as many addresses (the tile workgroup's id & 7); every reader sums all of them
+    double *qacc;                      // [3][C][QK][2] sum of c, sum of |c|
     // quick_decide's safety margin (1e-11; +inf under TAMCMC_OPT_QUICK_DECIDE = 1: every margin test answers "undecided") and what the
     // tests read back (tamcmc_sampler_get_info): [0] fallbacks to decide() taken by the likelihood tiles, counted by each chain's tile 0;
-    // [1] tests of chains outside a swap pair that those tiles decided from a kind-2 record, counted by the chain's commit workgroup
+    // [1] tests of chains outside a swap pair that those tiles decided from a kind-2 record, counted by the chain's commit workgroup;
+    // [2] tests that the shortcut decided OTHERWISE than the exact decide(), counted by the commit workgroup, which has both (0, or a bug)
     double qmargin;
     unsigned long long *qcount;
 };
 
+constexpr int QK = 8;  // keys per (set, chain) of FusedArgs::qacc
 constexpr int QN = 8;  // doubles per quick record (quick_decide): S*, kind, -pl/T, logL held, [pair's first chain: log u_swap, TA/TB - 1, TB/TA - 1], slot
 constexpr int ST_L = 1, ST_BR = 2, ST_ENTRY = 4, ST_LZ = 8, ST_FIRST = 16, ST_COMMIT = 32;
 
@@ -153,10 +159,47 @@ __device__ __attribute__((noinline)) int decide(const DevSamplerArgs *ga, const 
 // for the launch of iteration it+1, the slot, prior and status of the chain's proposal at iteration `it`.  With ST_COMMIT alone (after the
 // last iteration of a stretch) the launch holds nothing else.
 // (tiles: the launch holds the likelihood tiles of iteration `it`, which decided iteration it-1 themselves -- quick_decide)
+//
+// The chain's accumulators (FusedArgs::qacc) are this workgroup's too.  It asks the shortcut what the tiles of this launch asked it -- same
+// function, same records, same accumulators -- and counts an answer that is not decide()'s (qcount[2]; the slot names the outcome of the
+// test and of the swap as the chain sees them).  And it zeroes: launch `it` adds into set it mod 3 and reads set (it-1) mod 3, so set
+// (it+1) mod 3, last read by the chain's launch it-1, is free -- 16 lanes, one store each, also in the first launch of a stretch.  The
+// closing launch zeroes all three sets, for a next stretch that may start at any iteration; there the set it has just read is among
+// them, and for a swap pair BOTH chains' workgroups would read both chains' sets: the pair's first chain asks for itself and zeroes both, the
+// second does neither (nothing in a launch waits for anything else in it; the second chain's view of a stretch's LAST test is the one
+// answer of the shortcut that goes unasked).
+// (a function of its own that calls the leaf alone: what a caller keeps across a call lies above the callee's registers, and with a
+// second decide() below commit_chain -- for the pair's second chain -- the kernel needs 180 of them and loses its third wave per SIMD)
+__device__ int quick_decide_leaf(const DevSamplerArgs *ga, const FusedArgs *gf, int m, int q, int es, int pairA, Decided *out);
+__device__ __attribute__((noinline)) void commit_sums(const DevSamplerArgs *ga, const FusedArgs *gf, int m, long it, int q, int settled, int tiles,
+                                                      int slot, int swap_first) {
+    const ConstArgs &a = *(const ConstArgs *)uniform_ptr(ga);
+    const ConstFused &f = *(const ConstFused *)uniform_ptr(gf);
+    const int lane = threadIdx.x, C = a.C;
+    const int pairA = settled ? -1 : __builtin_amdgcn_readfirstlane(swap_first);
+    const bool second = !tiles && pairA >= 0 && pairA != m;  // (closing launch: the pair's first chain does this chain's part)
+    int differs = 0;
+    if (!settled && !second) {
+        const int es = (int)((it + 2) % 3);
+        const int qs = quick_decide_leaf(ga, gf, m, q, es, pairA, nullptr);
+        differs = (qs >= 0 && qs != slot) ? 1 : 0;
+        if (lane == 0 && differs) atomicAdd(f.qcount + 2, 1ull);
+    }
+    // (after the reads above: in the closing launch the set they name is among those zeroed)
+    const int z = lane;
+    if (tiles) {
+        if (z < 2 * QK) f.qacc[((size_t)((it + 1) % 3) * C + m) * (2 * QK) + z] = 0.0;
+    } else if (!second && z < 3 * 2 * QK) {
+        const size_t e = (size_t)(z / (2 * QK)) * C + m;
+        f.qacc[e * (2 * QK) + z % (2 * QK)] = 0.0;
+        if (pairA == m) f.qacc[(e + 1) * (2 * QK) + z % (2 * QK)] = 0.0;
+    }
+}
 __device__ __attribute__((noinline)) void commit_chain(const DevSamplerArgs *ga, const FusedArgs *gf, int m, long it, int q, int settled, long rec,
                                                        int tiles, Decided *dec) {
     const int slot = decide(ga, gf, m, it, q, settled, dec);
     __syncthreads();
+    commit_sums(ga, gf, m, it, q, settled, tiles, slot, dec->swap_first);
     const ConstArgs &a = *(const ConstArgs *)uniform_ptr(ga);
     const ConstFused &f = *(const ConstFused *)uniform_ptr(gf);
     const int lane = threadIdx.x, C = a.C, Nv = a.Nv, Np = a.desc.Np;
@@ -241,61 +284,56 @@ __device__ __attribute__((noinline)) void commit_chain(const DevSamplerArgs *ga,
 // post-test likelihoods from the approximate sums.  Otherwise -- about once in 1e5 tests -- decide() evaluates everything as written.
 // A decide() of ~2000 dependent instructions costs a lone wave 5 us at the head of the launch's longest chains; this one ~0.5 us.
 //
-// The sums come from FusedArgs::psum, ONE value per tile, c_t = fl(p_t[0] + p_t[1]), instead of the two of FusedArgs::part: half the loads,
-// and the magnitude is sum|c_t|.  Why the margin still covers it: the pre-addition adds one rounding of relative size eps to each term,
-// |c_t - (p_t[0] + p_t[1])| <= eps (|p_t[0]| + |p_t[1]|), which is one more unit in the n of "n eps sum|v|" above; and sum|c_t| <= sum|p_t[0]| +
-// sum|p_t[1]|, so the margin can only be the smaller of the two -- by the factor to which the two partials of a tile cancel.  They do not
+// The sums come from FusedArgs::qacc: every tile of launch it-1 has added ONE value, c_t = fl(p_t[0] + p_t[1]), and |c_t| into its chain's
+// accumulators (StepTiles::store_sums: 8 keys x 2 doubles per chain, set (it-1) mod 3), so what is left to do here does not grow with the
+// number of tiles: one load of the chain's 16 doubles by 16 lanes, three rotate-and-add rounds within that row of lanes, and the two sums
+// and the record's fields are read from their lanes (v_readlane, constant lanes) -- no LDS round trip anywhere.  (Not scalar loads into
+// 48 SGPRs, or 96 for a pair: the tile path has no SGPRs to spare -- the kernel then spills ~170 of them to VGPR lanes in every wave.)
+// Why the margin still covers it.  The order in which the atomics arrive is not fixed, and need not be: S is the sum of the same n values
+// c_t in SOME order -- whichever, each key's in its arrival order and the keys after one another, it is a chain of n-1 rounded additions,
+// and "n eps sum|v|" above bounds every such chain.  The pre-addition adds one rounding of relative size eps to each term,
+// |c_t - (p_t[0] + p_t[1])| <= eps (|p_t[0]| + |p_t[1]|), which is one more unit in that n; the magnitude is sum|c_t| (summed with the
+// same n eps of relative error, which the margin does not feel), and sum|c_t| <= sum|p_t[0]| + sum|p_t[1]|, so the margin can only be the
+// smaller of the two -- by the factor to which the two partials of a tile cancel.  They do not
 // cancel to speak of: p_t[0] = sum y/M is ~ the tile's bin count with a chi-square scatter of its square root, p_t[1] = sum ln M moves
 // with the units of the spectrum; even where ln M ~ -1 on every bin, |c_t| stays ~ sqrt(bins) = 1/50 of the magnitude.  1e-11 sum|c_t|
-// against ~2e-14 (sum|p_t[0]| + sum|p_t[1]|) leaves three orders of magnitude, one and a half in that worst case.  (The exact decide(), the
-// commit workgroups and the records keep reading `part`, in k_finalize's order.)
+// against ~2e-14 (sum|p_t[0]| + sum|p_t[1]|) leaves three orders of magnitude, one and a half in that worst case.  A NaN or an infinite
+// partial makes its accumulator NaN or infinite: every comparison below fails and the answer is "undecided".  (The exact decide(), the
+// commit workgroups and the records keep reading `part`, in k_finalize's order; the commit workgroup also asks this shortcut and counts a
+// decided answer that is not decide()'s -- FusedArgs::qcount[2].)
 
-// The lane's share of the per-tile values of chain j0 (PAIR: and of chain j0 + 1, both chains' loads in flight together), summed in any
-// order: four loads per lane and round (C3's 196 tiles: one round), then a butterfly.  A chain outside the swap pair pays for one chain.
-template <bool PAIR>
-__device__ __forceinline__ void quick_sums(const double *c0, int n, int lane, double &s0, double &a0, double &s1, double &a1) {
-    for (int t0 = 0; t0 < n; t0 += 256) {
-        double v[4], w[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int t = t0 + k * 64 + lane;
-            v[k] = t < n ? c0[t] : 0.0;
-            if (PAIR) w[k] = t < n ? c0[n + t] : 0.0;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            s0 += v[k]; a0 += fabs(v[k]);
-            if (PAIR) { s1 += w[k]; a1 += fabs(w[k]); }
-        }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        s0 += __shfl_xor(s0, off, 64); a0 += __shfl_xor(a0, off, 64);
-        if (PAIR) { s1 += __shfl_xor(s1, off, 64); a1 += __shfl_xor(a1, off, 64); }
-    }
+// x of every lane of the same parity in the lane's row of 16 added up (rotations by 8, 4 and 2 lanes within the row: register moves, no LDS
+// round trip).  Every lane of a row ends with the same three additions of the same values in another order -- lanes 0 and 1 are read.
+__device__ __forceinline__ double row_sum_by_parity(double x) {
+#define TAMCMC_ROW_ROR(x, n)                                                                                                     \
+    __longlong_as_double(((long long)__builtin_amdgcn_update_dpp(0, (int)(__double_as_longlong(x) >> 32), 0x120 + (n), 0xf, 0xf, false) << 32) | \
+                         (unsigned int)__builtin_amdgcn_update_dpp(0, (int)(__double_as_longlong(x) & 0xffffffffll), 0x120 + (n), 0xf, 0xf, false))
+    x += TAMCMC_ROW_ROR(x, 8);
+    x += TAMCMC_ROW_ROR(x, 4);
+    x += TAMCMC_ROW_ROR(x, 2);
+#undef TAMCMC_ROW_ROR
+    return x;
 }
-// (the shortcut itself: -1 = undecided.  Inlined at the head of a likelihood tile, whose own first loads are in flight beside these --
-// StepTiles::head; a leaf function for the candidate roles)
-__device__ __forceinline__ int quick_decide_core(const DevSamplerArgs *ga, const FusedArgs *gf, int m, int q, int pairA, Decided *out) {
+
+// (the shortcut itself: -1 = undecided.  es: the accumulator set of the iteration to decide.  Inlined at the head of a likelihood tile,
+// whose own first loads are in flight beside these -- StepTiles::head; a leaf function for the candidate roles and the commit workgroups)
+__device__ __forceinline__ int quick_decide_core(const DevSamplerArgs *ga, const FusedArgs *gf, int m, int q, int es, int pairA, Decided *out) {
     const ConstArgs &a = *(const ConstArgs *)uniform_ptr(ga);
     const ConstFused &f = *(const ConstFused *)uniform_ptr(gf);
     const int lane = threadIdx.x & 63, C = a.C;
-    const int p = q ^ 1, n = a.ntiles;
+    const int p = q ^ 1;
     const bool in_pair = pairA >= 0 && (m == pairA || m == pairA + 1);
     const int j0 = in_pair ? pairA : m;
-    const double *c0 = f.psum + ((size_t)p * C + j0) * n;
     const double *r0 = f.quick + ((size_t)p * C + j0) * QN;
-    // every load first: the records (lane k < QN: field k of chain j0, lane QN + k: of chain j0 + 1), the tiles' sums
-    double rec, s0 = 0, a0 = 0, s1 = 0, a1 = 0;
-    if (in_pair) {  // (wave-uniform)
-        rec = lane < 2 * QN ? r0[lane] : 0.0;
-        quick_sums<true>(c0, n, lane, s0, a0, s1, a1);
-    } else {
-        rec = lane < QN ? r0[lane] : 0.0;
-        quick_sums<false>(c0, n, lane, s0, a0, s1, a1);
-    }
-    const double St0 = __shfl(rec, 0, 64), ok0 = __shfl(rec, 1, 64);
-    const int ps0 = (int)__shfl(rec, 7, 64);
+    const double *g0 = f.qacc + ((size_t)es * C + j0) * (2 * QK);
+    // two loads: the records (lane k < QN: field k of chain j0, lane QN + k: of chain j0 + 1) and the accumulators (lane k < 16: chain j0's,
+    // lane 16 + k: chain j0 + 1's, which lie right behind -- one row of 16 lanes per chain, the sums of c in its even lanes, of |c| in its odd)
+    const double rec = lane < (in_pair ? 2 * QN : QN) ? r0[lane] : 0.0;
+    const double acc = lane < (in_pair ? 4 * QK : 2 * QK) ? g0[lane] : 0.0;
+    const double sums = row_sum_by_parity(acc);
+    double s0 = lane_value<0>(sums), a0 = lane_value<1>(sums);
+    const double St0 = lane_value<0>(rec), ok0 = lane_value<1>(rec);
+    const int ps0 = (int)lane_value<7>(rec);
     const double mg = f.qmargin;
     // kind 1: threshold test; kind 2: the proposal cannot be accepted (outside a prior's support, or its table failed: r = 0 and u > 0) --
     // its partial sums may be anything (an empty slot's tiles are skipped)
@@ -308,15 +346,16 @@ __device__ __forceinline__ int quick_decide_core(const DevSamplerArgs *ga, const
     d.o.acc = 0; d.o.r = 0; d.o.logL = 0; d.o.logPr = 0; d.o.logPost = 0;  // (the scalars are the commit workgroup's business: decide())
     if (!in_pair) { d.slot = 2 * m + acc0; d.src = m; d.src_acc = acc0; d.src_ps = ps0; }
     else {
-        const double St1 = __shfl(rec, QN, 64), ok1 = __shfl(rec, QN + 1, 64);
-        const int ps1 = (int)__shfl(rec, QN + 7, 64);
+        double s1 = lane_value<16>(sums), a1 = lane_value<17>(sums);
+        const double St1 = lane_value<QN>(rec), ok1 = lane_value<QN + 1>(rec);
+        const int ps1 = (int)lane_value<QN + 7>(rec);
         int acc1 = 0;
         if (ok1 == 2.0) { s1 = 0; a1 = 0; }
         else if (ok1 > 0 && fabs(s1 - St1) > mg * (a1 + fabs(St1))) acc1 = s1 < St1 ? 1 : 0;
         else return -1;
-        const double c0 = __shfl(rec, 2, 64), c1 = __shfl(rec, QN + 2, 64);
-        const double LA = acc0 ? c0 * s0 : __shfl(rec, 3, 64), LB = acc1 ? c1 * s1 : __shfl(rec, QN + 3, 64);
-        const double lus = __shfl(rec, 4, 64), x = LA * __shfl(rec, 5, 64) + LB * __shfl(rec, 6, 64);
+        const double c0 = lane_value<2>(rec), c1 = lane_value<QN + 2>(rec);
+        const double LA = acc0 ? c0 * s0 : lane_value<3>(rec), LB = acc1 ? c1 * s1 : lane_value<QN + 3>(rec);
+        const double lus = lane_value<4>(rec), x = LA * lane_value<5>(rec) + LB * lane_value<6>(rec);
         // (written as !(>): a NaN on either side -- a NaN sum, or inf * 0 under the forced margin -- is undecided)
         if (!(fabs(x - lus) > mg * (fabs(c0) * a0 + fabs(c1) * a1 + fabs(LA) + fabs(LB)))) return -1;
         const int swapped = x > lus ? 1 : 0;
@@ -333,14 +372,14 @@ __device__ __forceinline__ int quick_decide_core(const DevSamplerArgs *ga, const
     if (out && lane == 0) *out = d;
     return d.slot;
 }
-__device__ __attribute__((noinline)) int quick_decide_leaf(const DevSamplerArgs *ga, const FusedArgs *gf, int m, int q, int pairA, Decided *out) {
-    return quick_decide_core(ga, gf, m, q, pairA, out);
+__device__ __attribute__((noinline)) int quick_decide_leaf(const DevSamplerArgs *ga, const FusedArgs *gf, int m, int q, int es, int pairA, Decided *out) {
+    return quick_decide_core(ga, gf, m, q, es, pairA, out);
 }
 
 __device__ __forceinline__ int quick_decide(const DevSamplerArgs *ga, const FusedArgs *gf, int m, long it, int q, int settled, int pairA,
                                             Decided *out) {
     if (settled) return decide(ga, gf, m, it, q, 1, out);
-    const int s = quick_decide_leaf(ga, gf, m, q, pairA, out);
+    const int s = quick_decide_leaf(ga, gf, m, q, (int)((it + 2) % 3), pairA, out);
     return s >= 0 ? s : decide(ga, gf, m, it, q, 0, out);
 }
 
@@ -369,16 +408,21 @@ struct StepTiles {
         const bool lone = a.per > 0 && !(pairA >= 0 && (m == pairA || m == pairA + 1));
         tile::SlotWords w0{}, w1{};
         if (lone) { w0 = tile::slot_words(a, 2 * m); w1 = tile::slot_words(a, 2 * m + 1); }
-        int s = quick_decide_core(ga, gf, m, q, pairA, nullptr);
+        int s = quick_decide_core(ga, gf, m, q, (int)((it + 2) % 3), pairA, nullptr);
         if (s < 0) s = decide_counted(ga, gf, m, it, q, tile);
         if (lone && (s >> 1) == m) return (s & 1) ? w1 : w0;
         return tile::slot_words(a, s);
     }
-    // (lane 0, beside the stores of the two sums: the one value quick_decide reads of this tile)
-    __device__ __forceinline__ void store_sums(int b, int tile, double s0, double s1) const {
+    // (lane 0, beside the stores of the two sums: what quick_decide reads of this tile, added to the chain's accumulators of this
+    // iteration's set.  Two atomics whose result nobody waits for; the key -- the workgroup's id & 7, as loglike_tile counts it: the roles'
+    // and the L z blocks' workgroups before the tiles come in eights -- only spreads them over eight pairs of addresses)
+    __device__ __forceinline__ void store_sums(int b, int /*tile*/, double s0, double s1) const {
         const ConstArgs &a = *(const ConstArgs *)uniform_ptr(ga);
         const ConstFused &f = *(const ConstFused *)uniform_ptr(gf);
-        f.psum[((size_t)q * a.C + first + b) * a.ntiles + tile] = s0 + s1;
+        const double c = s0 + s1;
+        double *g = f.qacc + (((size_t)(it % 3) * a.C + first + b) * QK + (blockIdx.x & 7)) * 2;
+        atomicAdd(g, c);
+        atomicAdd(g + 1, fabs(c));
     }
 };
 

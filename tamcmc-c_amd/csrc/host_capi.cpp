@@ -170,8 +170,9 @@ int tamcmc_sampler_get_info(const tamcmc_sampler *s, int64_t *info, int32_t n) {
     v[TAMCMC_INFO_NCHAINS] = s->cfg.MALA.Nchains;
     v[TAMCMC_INFO_ADAPT_IN_LDS] = -1;
     if (s->dev) {
-        long d[13];
+        long d[14];
         s->dev->info(d);
+        v[TAMCMC_INFO_QUICK_MISMATCH] = d[13];
         v[TAMCMC_INFO_ADAPT_IN_LDS] = d[2];
         v[TAMCMC_INFO_FUSED_AVAILABLE] = d[3];
         v[TAMCMC_INFO_CHAIN_GROUPS] = d[4];

@@ -153,12 +153,12 @@ class Sampler:
 
     def info(self):
         """tamcmc_sampler_get_info as a dict (engine, sizes, which side of the size limits, iterations per scheme)."""
-        v = np.zeros(14, dtype=np.int64)
-        rc = self._L.tamcmc_sampler_get_info(self._h, _p(v, _i64p), 14)
+        v = np.zeros(15, dtype=np.int64)
+        rc = self._L.tamcmc_sampler_get_info(self._h, _p(v, _i64p), 15)
         if rc != OK:
             raise TamcmcError(rc, "tamcmc_sampler_get_info")
         keys = ("engine", "nvars", "nparams", "nchains", "adapt_in_lds", "fused_available", "chain_groups", "iter_fused", "iter_lockstep",
-                "fused_stretches", "quick_fallbacks", "quick_sure", "iter_joint", "iter_window")
+                "fused_stretches", "quick_fallbacks", "quick_sure", "iter_joint", "iter_window", "quick_mismatch")
         return dict(zip(keys, (int(x) for x in v)))
 
     def gradient(self):
