@@ -144,6 +144,12 @@ extern "C" {
 #define TAMCMC_OPT_RGB_ADJOINT 12     /* value: 0/1 (default 0) -- 1: with TAMCMC_OPT_GRADIENT = TAMCMC_GRADIENT_ADJOINT the red-giant models, ids 25
                                         and 27, take the hybrid adjoint batch (see tamcmc_hip_adjoint_table) instead of being refused.  Read at
                                         every call, like TAMCMC_OPT_GRADIENT; nothing else changes with it.  Any other value: TAMCMC_ERR_BAD_ARG */
+#define TAMCMC_OPT_ENVELOPE_DEVICE_ENGINE 13 /* value: 0/1 (default 0) -- 1: tamcmc_sampler_create builds the device-resident engine (engine = 1,
+                                        use_drift = 0) for the Gaussian-envelope models, ids 0 and 1; 0: it refuses them with
+                                        TAMCMC_ERR_BAD_MODEL.  Read when the sampler is created: changing it afterwards does not affect an
+                                        existing sampler.  The Langevin step of these ids stays on the host-driven engine (engine = 1 with
+                                        use_drift = 1: TAMCMC_ERR_BAD_MODEL whatever this option says); see tamcmc_sampler.h.  Any other
+                                        value: TAMCMC_ERR_BAD_ARG */
 #define TAMCMC_FISHER_SLAB 2048     /* bins per workgroup (and per partial matrix) of the Gram kernel of tamcmc_hip_fisher / _weighted_gram */
 
 /* One (n,l) multiplet: <=7 Lorentzian m-components on its truncation window.

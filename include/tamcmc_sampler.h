@@ -96,8 +96,18 @@ int64_t tamcmc_sampler_nvars(const tamcmc_sampler *s);
  *                                  chain from a gradient taken on the new route.
  *                                  Nchains (Nvars + 1) <= 65535.  Host-driven engine: random walk or Langevin, any arithmetic mode
  *                                  (tamcmc_hip_fd_gradient_posterior; the adjoint routes: FAST / FAST_DIRECT)
- *   Gaussian-envelope models       host-driven engine only (random walk or Langevin); engine = 1 -> TAMCMC_ERR_BAD_MODEL at
- *     (ids 0/1)                    tamcmc_sampler_create
+ *   Gaussian-envelope models       host-driven engine: random walk or Langevin.  Device engine (engine = 1): opt-in, random walk only --
+ *     (ids 0/1)                    TAMCMC_ERR_BAD_MODEL at tamcmc_sampler_create unless the context has
+ *                                  TAMCMC_OPT_ENVELOPE_DEVICE_ENGINE = 1 at that moment, and with use_drift = 1 whatever the option says:
+ *                                  the Langevin step of these ids stays on the host-driven engine.  prior_class must equal model_id.
+ *                                  Runs of three or more iterations without adaptation take ONE launch per iteration (k_env_step: every 1024-bin tile of a chain
+ *                                  settles the previous test, proposes and evaluates; counted by TAMCMC_INFO_ITER_FUSED /
+ *                                  _FUSED_STRETCHES) while Nx <= 32768 (id 1) or 6144 (id 0, whose step repeats the xi pass over the whole
+ *                                  spectrum in every tile: the measured crossover) and TAMCMC_OPT_STEP_SCHEME != 1; everything else on the lockstep
+ *                                  kernels (k_iterate -> k_env_ksi / k_env_eval).  Same chains bit for bit either way; a chain's stored
+ *                                  logL is what tamcmc_hip_loglike_params_batch returns for the same EnvRow bits, i.e. within 1e-12 |logL|
+ *                                  of the reference.  TAMCMC_OPT_WORKGROUP / _BINS_PER_THREAD / _PRECISION do not apply.  No tables:
+ *                                  tamcmc_sampler_get_tables -> TAMCMC_ERR_BAD_MODEL; see tamcmc_sampler_get_envelope_rows
  *   tamcmc_sampler_seed_proposal   models 3, 11, 12, 13, 14, 23 on a FAST or FAST_DIRECT context (tamcmc_hip_fisher's refusals: ids 0, 1, 25,
  *     _fisher                      27 -> TAMCMC_ERR_BAD_MODEL, STRICT -> TAMCMC_ERR_BAD_ARG); Nvars <= 16384
  * The host-driven engine has no size-dependent branches (host memory, column Cholesky).
@@ -160,8 +170,8 @@ int tamcmc_sampler_get_gradient(const tamcmc_sampler *s, double *grad, double *g
  * pointer may be NULL.  Host-driven engine: everything.  Device-resident engine: use_drift = 1 only (else TAMCMC_ERR_BAD_ARG),
  * vars_prop and grad_prop; stats_prop and lq come back as NaN (those scalars are not kept). */
 int tamcmc_sampler_get_last_test(const tamcmc_sampler *s, double *vars_prop, double *stats_prop, double *lq, double *grad_prop);
-/* Audit entry of the device-resident random-walk engine (models 3, 11, 12, 13, 14, 23; host-driven engine, Langevin step, red giants:
- * TAMCMC_ERR_BAD_MODEL): the multiplet tables the last stretch of the last tamcmc_sampler_run left in the likelihood kernel's input
+/* Audit entry of the device-resident random-walk engine (models 3, 11, 12, 13, 14, 23; host-driven engine, Langevin step, red giants,
+ * Gaussian-envelope ids 0 / 1 -- they have no table --: TAMCMC_ERR_BAD_MODEL): the multiplet tables the last stretch of the last tamcmc_sampler_run left in the likelihood kernel's input
  * block, and the parameter vector each was built from -- both read from the engine's own buffers, nothing is replayed.
  *   shape[4] = scheme, slots, rows per slot, noise stride (always returned; call with every other pointer NULL for the sizes)
  *   scheme 0  no stretch has run yet (slots = 0)
@@ -177,6 +187,19 @@ int tamcmc_sampler_get_last_test(const tamcmc_sampler *s, double *vars_prop, dou
  * written [slots], noise [slots x stride], logprior [slots], params [slots x Nparams]. */
 int tamcmc_sampler_get_tables(const tamcmc_sampler *s, int32_t *shape, void *rows, int32_t *nrows, double *noise, int32_t *nharvey,
                               int32_t *nnoise, int32_t *status, int32_t *written, double *logprior, double *params);
+/* Audit entry of the device-resident engine for the Gaussian-envelope models (ids 0 / 1; anything else: TAMCMC_ERR_BAD_MODEL; before the
+ * first tamcmc_sampler_run: TAMCMC_ERR_BAD_ARG): for every chain the scalars the LAST iteration's proposal was evaluated from, the
+ * parameter vector they were built from, its log-prior and status -- read from the engine's own buffers, nothing is replayed.
+ *   rows [Nchains x TAMCMC_ENVELOPE_ROW_N], the fields of the engine's row as doubles:
+ *     [0] amp  [1] numax  [2] sigma^2  [3] N0                                   (Gaussian and white noise, both ids)
+ *     [4..5] H_k  [6..7] ln(1e-3 tc_k)  [8..9] p_k                              (id 1: Harvey terms k = 0, 1)
+ *     [10..12] b_k  [13..15] ln b_k  [16..18] c_k  [19..21] a_k^2               (id 0: super-Lorentzians k = 0, 1, 2)
+ *     [22..23] 1.0 where Harvey term k is active (tc_k != 0), else 0.0          (id 1)
+ *     (the fields of the other id are 0)
+ *   params [Nchains x Nparams], logprior [Nchains], status [Nchains].  Any pointer may be NULL.
+ * A proposal whose log-prior is -inf or NaN, or whose status is not TAMCMC_OK, is rejected whatever its row holds. */
+#define TAMCMC_ENVELOPE_ROW_N 24
+int tamcmc_sampler_get_envelope_rows(const tamcmc_sampler *s, double *rows, double *params, double *logprior, int32_t *status);
 /* moves [Nchains]: for every chain the number of iterations since creation whose record carries moved = 1 -- the flag the reference
  * stores per iteration and chain (MALA.cpp:543-545; a swap exchanges the pair's flags, :436, :446) and its acceptance diagnostic counts
  * per buffer (Outputs::reject_rate / count_accepted_vals, outputs.cpp:1824-1858).  Differences between two calls / the iterations in

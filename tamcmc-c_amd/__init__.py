@@ -29,6 +29,7 @@ PRECISION_STRICT, PRECISION_FAST, PRECISION_FAST_DIRECT = 0, 1, 2
 OPT_PRECISION, OPT_TIMING, OPT_BINS_PER_THREAD, OPT_WORKGROUP, OPT_FD_WINDOWED, OPT_STEP_SCHEME, OPT_ARMM_DENSE_SCAN = 1, 2, 3, 4, 5, 6, 7
 OPT_GRADIENT, GRADIENT_FD, GRADIENT_ADJOINT = 9, 0, 1  # gradient batches: finite differences (default) / table-space adjoint, frozen windows
 OPT_RGB_DEVICE_LANGEVIN = 11  # 1: Sampler(use_drift=1, engine="device") is built for the red-giant ids 25 / 27 (default 0: ERR_BAD_MODEL); read at creation
+OPT_ENVELOPE_DEVICE_ENGINE = 13  # 1: Sampler(engine="device", use_drift=0) is built for the Gaussian-envelope ids 0 / 1 (default 0: ERR_BAD_MODEL); read at creation
 OPT_RGB_ADJOINT = 12  # 1: under GRADIENT_ADJOINT the red-giant ids 25 / 27 take the hybrid adjoint batch (default 0: ERR_BAD_MODEL); read at every call
 OPT_FISHER_WORKSPACE_MB = 10  # MiB of model rows HipContext.fisher keeps on the device per pass (default 2048)
 FISHER_SLAB = 2048  # bins per workgroup of the Gram kernel (TAMCMC_FISHER_SLAB)

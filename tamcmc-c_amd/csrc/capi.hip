@@ -53,6 +53,7 @@ int tamcmc_hip_create(tamcmc_hip_ctx **out, int device) {
 
 // (private, host_capi.cpp) a sampler borrows the context for its whole life
 void tamcmc_hip_ctx_attach(tamcmc_hip_ctx *c) { if (c) c->attached++; }
+int tamcmc_hip_envelope_device_engine(const tamcmc_hip_ctx *c) { return c ? c->envelope_device_engine : 0; }
 void tamcmc_hip_ctx_detach(tamcmc_hip_ctx *c) {
     if (!c) return;
     c->attached--;
@@ -115,6 +116,10 @@ int tamcmc_hip_set_option(tamcmc_hip_ctx *c, int option, int64_t value) {
     case TAMCMC_OPT_RGB_DEVICE_LANGEVIN:
         if (value < 0 || value > 1) return TAMCMC_ERR_BAD_ARG;
         c->rgb_device_langevin = (int)value;
+        return TAMCMC_OK;
+    case TAMCMC_OPT_ENVELOPE_DEVICE_ENGINE:
+        if (value < 0 || value > 1) return TAMCMC_ERR_BAD_ARG;
+        c->envelope_device_engine = (int)value;
         return TAMCMC_OK;
     case TAMCMC_OPT_RGB_ADJOINT:
         if (value < 0 || value > 1) return TAMCMC_ERR_BAD_ARG;

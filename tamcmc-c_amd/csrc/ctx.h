@@ -74,6 +74,7 @@ struct tamcmc_hip_ctx {
     int gradient = TAMCMC_GRADIENT_FD;  // gradient batches: finite differences, or the table-space adjoint with frozen windows (adjoint.h)
     int rgb_device_langevin = 0;  // 1: the device-resident engine builds its Langevin sampler for the red-giant ids (read at sampler creation)
     int rgb_adjoint = 0;  // 1: under TAMCMC_GRADIENT_ADJOINT the red-giant ids take the hybrid batch (fd_batch.hip; read at every call)
+    int envelope_device_engine = 0;  // 1: the device-resident engine is built for the Gaussian-envelope ids 0 / 1 (read at sampler creation)
     // resident spectrum
     int64_t Nx = 0;
     std::vector<double> hx;  // host copy of x (table builders need x[0], x[Nx-1], step)

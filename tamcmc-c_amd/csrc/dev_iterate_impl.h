@@ -468,17 +468,11 @@ __device__ __forceinline__ void Lz_rows_wave(const DevSamplerArgs &a, int chain,
     }
 }
 
-// Proposal of iteration `it` for `chain` from the state in LDS (s_vars/s_params): x' = x + L z (MALA.cpp:348-355), L =
-// chol((Sigma+eps2) sigma) stored transposed, same Philox streams as the host engine; log-prior; params' -> multiplet table
-// written into slot `slot` of the likelihood kernel's input block.  Ends without a barrier.  (B): 256 threads.
-__device__ __forceinline__ void propose_common(const DevSamplerArgs &a, const UnpackLds &U, int chain, long it, int slot, double *pv, double *pp,
-                               double *logPr_out, int *status_out, double *s_vars, double *s_params, double *s_z, const double *lz = nullptr,
-                               const rgb::Slice *rs = nullptr, int rb = 0) {
+// x' = x + L z from the state in LDS (s_vars/s_params) and the normals in s_z (or the rows lz computed ahead), scattered into the
+// parameter vector (update_params_with_vars); both also written to pv / pp.  Called after a barrier; ends without one.
+__device__ __forceinline__ void propose_position(const DevSamplerArgs &a, int chain, double *pv, double *pp, double *s_vars, double *s_params,
+                                                 const double *s_z, const double *lz) {
     const int Np = a.desc.Np, Nv = a.Nv, tid = threadIdx.x;
-    const bool rgb = is_rgb_model(a.desc.model_id);
-    if (!lz) normals_into(a, chain, it, s_z);
-    if (!rgb) unpack_begin(a.desc, U);
-    else __syncthreads();
     for (int i = tid; i < Nv; i += TB) {  // lane i owns row i: reads s_vars[i] only, every s_z[k]
         const double s = lz ? lz[i] : Lz_row(a, chain, i, s_z);
         const double v = s_vars[i] + 0.0 + s;
@@ -489,6 +483,37 @@ __device__ __forceinline__ void propose_common(const DevSamplerArgs &a, const Un
     for (int k = tid; k < Nv; k += TB) s_params[a.index_to_relax[k]] = s_vars[k];  // update_params_with_vars
     __syncthreads();
     for (int i = tid; i < Np; i += TB) pp[i] = s_params[i];
+}
+
+// Gaussian-envelope models (ids 0 / 1): the front end of a proposal -- its log-prior by lane 0 (pr::prior_serial in double, what the
+// gradient batch's k_env_prior runs) while the first lane of wave 1 forms the row the evaluation reads (env_row, envelope_row.h).  No
+// table and no unpack; a dead prior or a status that is not OK is mh_outcome's business, whatever the row then holds.  s_params
+// complete (a barrier) before the call; ends without a barrier.
+__device__ __forceinline__ void env_front(const ModelDesc &d, const double *s_params, EnvRow *row, double *logPr_out, int *status_out) {
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        int st = TAMCMC_OK;
+        *logPr_out = (double)pr::prior_serial(d.prior_class, s_params, nullptr, (long)d.Np, d.priors, d.priors_switch, nullptr, &st);
+        *status_out = st;
+    } else if (tid == 64) env_row(d.model_id, s_params, *row);
+}
+
+// Proposal of iteration `it` for `chain` from the state in LDS (s_vars/s_params): x' = x + L z (MALA.cpp:348-355), L =
+// chol((Sigma+eps2) sigma) stored transposed, same Philox streams as the host engine; log-prior; params' -> multiplet table
+// written into slot `slot` of the likelihood kernel's input block.  Ends without a barrier.  (B): 256 threads.
+__device__ __forceinline__ void propose_common(const DevSamplerArgs &a, const UnpackLds &U, int chain, long it, int slot, double *pv, double *pp,
+                               double *logPr_out, int *status_out, double *s_vars, double *s_params, double *s_z, const double *lz = nullptr,
+                               const rgb::Slice *rs = nullptr, int rb = 0) {
+    const int Np = a.desc.Np, tid = threadIdx.x;
+    const bool rgb = is_rgb_model(a.desc.model_id), env = is_envelope_model(a.desc.model_id);
+    if (!lz) normals_into(a, chain, it, s_z);
+    if (!rgb && !env) unpack_begin(a.desc, U);
+    else __syncthreads();
+    propose_position(a, chain, pv, pp, s_vars, s_params, s_z, lz);
+    if (env) {  // ids 0 / 1: the kernels enqueued right behind this launch (envelope_stage_enqueue) evaluate the row
+        env_front(a.desc, s_params, a.env_rows + slot, logPr_out, status_out);
+        return;
+    }
     if (rgb) {
         // red-giant models (ids 25 / 27): the table needs the mixed-mode solver -- the kernels enqueued right behind this launch
         // (rgb_device_stage) build it.  Here: the red-giant front end (rgb_front.h, shared with the gradient batch's k_fd_rgb_perturb) on
@@ -568,6 +593,79 @@ __device__ __forceinline__ int resolve_swap(const AT &a, int A, double u, Accept
     return 1;
 }
 
+// (0) of the lockstep scheme for chain m, by a whole 256-thread workgroup: the MH test of the pending iteration it-1 (own chain; the
+// swap partner's too when chain m is in the swap pair), the adjacent-pair parallel-tempering swap, the chain's new current state into
+// the OTHER parity buffer and into LDS (s_vars / s_params; with learn_pending the chain's own position after the test into s_z), the
+// record.  pending = 0: the state is carried over as it is.  `writer`: this workgroup writes the chain's state, counters and records --
+// every workgroup of k_iterate; of the workgroups that k_env_step (dev_env_step_impl.h) runs per chain, the first tile's only.
+__device__ __forceinline__ void settle_chain(const DevSamplerArgs &a, int m, long it, int P, int pending, long rec, int learn_pending, bool writer,
+                                             double *s_vars, double *s_params, double *s_z, double *s_red, AcceptOut *s_own_p, AcceptOut *s_partner_p) {
+    const int Np = a.desc.Np, Nv = a.Nv, C = a.C, tid = threadIdx.x;
+    const int Q = P ^ 1;
+    AcceptOut &s_own = *s_own_p, &s_partner = *s_partner_p;
+    const double *curv = a.vars_cur + (size_t)P * C * Nv, *curp = a.params_cur + (size_t)P * C * Np;
+    const double *prpv = a.vars_prop + (size_t)P * C * Nv, *prpp = a.params_prop + (size_t)P * C * Np;
+    double *newv = a.vars_cur + (size_t)Q * C * Nv, *newp = a.params_cur + (size_t)Q * C * Np;
+    if (pending) {
+        const long itp = it - 1;
+        accept_result(a, m, itp, P, s_red, &s_own);
+        int src = m;
+        AcceptOut mine = s_own;
+        // parallel tempering (MALA.cpp:397-461): adjacent pair, tempered log-likelihoods after the MH tests
+        if (is_swap_iter(a, itp)) {
+            double u;
+            const int A = swap_first(a, itp, &u);
+            const int B = A + 1;
+            if (m == A || m == B) {  // workgroup-uniform branch
+                const int partner = (m == A) ? B : A;
+                accept_result(a, partner, itp, P, s_red, &s_partner);
+                AcceptOut oA = (m == A) ? s_own : s_partner, oB = (m == A) ? s_partner : s_own;
+                const int swapped = resolve_swap(a, A, u, oA, oB);
+                if (swapped) { src = partner; mine = (m == A) ? oA : oB; }
+                if (m == A && tid == 0 && writer) {  // (chain groups: launches of different iterations may overlap)
+                    atomicAdd((unsigned long long *)&a.counters[2], 1ull);
+                    if (swapped) atomicAdd((unsigned long long *)&a.counters[3], 1ull);
+                }
+            }
+        }
+        const int src_acc = (src == m) ? s_own.acc : s_partner.acc;
+        const double *sv = (src_acc ? prpv : curv) + (size_t)src * Nv;
+        const double *sp = (src_acc ? prpp : curp) + (size_t)src * Np;
+        for (int i = tid; i < Nv; i += TB) { const double v = sv[i]; s_vars[i] = v; if (writer) newv[(size_t)m * Nv + i] = v; }
+        for (int i = tid; i < Np; i += TB) { const double v = sp[i]; s_params[i] = v; if (writer) newp[(size_t)m * Np + i] = v; }
+        if (learn_pending) {  // the adaptation sees the chain's OWN position after the MH test, before the swap
+            const double *ov = (s_own.acc ? prpv : curv) + (size_t)m * Nv;
+            for (int i = tid; i < Nv; i += TB) s_z[i] = ov[i];
+        }
+        if (tid == 0 && writer) {
+            a.logL_cur[Q * C + m] = mine.logL;
+            a.logPr_cur[Q * C + m] = mine.logPr;
+            a.logPost_cur[Q * C + m] = mine.logPost;
+            // a swap exchanges the pair's moved / Pmove entries too (MALA.cpp:425-446): what is recorded is the partner's
+            a.moved[m] = (src == m) ? s_own.acc : s_partner.acc;
+            a.Pmove[m] = (src == m) ? s_own.r : s_partner.r;
+            if (m == 0 && a.moved[0]) a.counters[1] += 1;
+            a.counters[8 + m] += a.moved[m];  // per-chain count of recorded moves (the acceptance diagnostic, outputs.cpp:1824-1858)
+            if (m == 0) a.counters[0] = it;
+            if (a.stats && rec >= 0) {  // update_buffer_stat_criteria (MALA.cpp:708)
+                double *r = a.stats + ((size_t)rec * C + m) * 3;
+                r[0] = mine.logL; r[1] = mine.logPr; r[2] = mine.logPost;
+            }
+        }
+        __syncthreads();
+        if (a.samples && rec >= 0 && writer)  // update_buffer_params (MALA.cpp:710)
+            for (int i = tid; i < Nv; i += TB) a.samples[((size_t)rec * C + m) * Nv + i] = s_vars[i];
+    } else {
+        for (int i = tid; i < Nv; i += TB) { const double v = curv[(size_t)m * Nv + i]; s_vars[i] = v; if (writer) newv[(size_t)m * Nv + i] = v; }
+        for (int i = tid; i < Np; i += TB) { const double v = curp[(size_t)m * Np + i]; s_params[i] = v; if (writer) newp[(size_t)m * Np + i] = v; }
+        if (tid == 0 && writer) {
+            a.logL_cur[Q * C + m] = a.logL_cur[P * C + m];
+            a.logPr_cur[Q * C + m] = a.logPr_cur[P * C + m];
+            a.logPost_cur[Q * C + m] = a.logPost_cur[P * C + m];
+        }
+    }
+}
+
 // ===============================================================================================================
 // (B) LOCKSTEP.  ONE kernel per MCMC iteration besides the likelihood kernel.  Workgroup m:
 //   (0) settles the pending iteration it-1 for chain m: MH test (own chain; the swap partner's too when chain m is in the
@@ -599,74 +697,14 @@ __global__ void __launch_bounds__(TB) k_iterate(const DevSamplerArgs a, const lo
     __shared__ AcceptOut s_own, s_partner;
     __shared__ double s_scal[2];
 
-    const int m = blockIdx.x + c_off, tid = threadIdx.x;  // c_off: first chain of this launch's chain group
+    const int m = blockIdx.x + c_off;  // c_off: first chain of this launch's chain group
     const int Q = P ^ 1;
-    const double *curv = a.vars_cur + (size_t)P * C * Nv, *curp = a.params_cur + (size_t)P * C * Np;
-    const double *prpv = a.vars_prop + (size_t)P * C * Nv, *prpp = a.params_prop + (size_t)P * C * Np;
-    double *newv = a.vars_cur + (size_t)Q * C * Nv, *newp = a.params_cur + (size_t)Q * C * Np;
 
     // ------------------------------------------------------------------ (0) settle the pending iteration
-    if (pending) {
-        const long itp = it - 1;
-        accept_result(a, m, itp, P, s_red, &s_own);
-        int src = m;
-        AcceptOut mine = s_own;
-        // parallel tempering (MALA.cpp:397-461): adjacent pair, tempered log-likelihoods after the MH tests
-        if (is_swap_iter(a, itp)) {
-            double u;
-            const int A = swap_first(a, itp, &u);
-            const int B = A + 1;
-            if (m == A || m == B) {  // workgroup-uniform branch
-                const int partner = (m == A) ? B : A;
-                accept_result(a, partner, itp, P, s_red, &s_partner);
-                AcceptOut oA = (m == A) ? s_own : s_partner, oB = (m == A) ? s_partner : s_own;
-                const int swapped = resolve_swap(a, A, u, oA, oB);
-                if (swapped) { src = partner; mine = (m == A) ? oA : oB; }
-                if (m == A && tid == 0) {  // (chain groups: launches of different iterations may overlap)
-                    atomicAdd((unsigned long long *)&a.counters[2], 1ull);
-                    if (swapped) atomicAdd((unsigned long long *)&a.counters[3], 1ull);
-                }
-            }
-        }
-        const int src_acc = (src == m) ? s_own.acc : s_partner.acc;
-        const double *sv = (src_acc ? prpv : curv) + (size_t)src * Nv;
-        const double *sp = (src_acc ? prpp : curp) + (size_t)src * Np;
-        for (int i = tid; i < Nv; i += TB) { const double v = sv[i]; s_vars[i] = v; newv[(size_t)m * Nv + i] = v; }
-        for (int i = tid; i < Np; i += TB) { const double v = sp[i]; s_params[i] = v; newp[(size_t)m * Np + i] = v; }
-        if (learn_pending) {  // the adaptation sees the chain's OWN position after the MH test, before the swap
-            const double *ov = (s_own.acc ? prpv : curv) + (size_t)m * Nv;
-            for (int i = tid; i < Nv; i += TB) s_z[i] = ov[i];
-        }
-        if (tid == 0) {
-            a.logL_cur[Q * C + m] = mine.logL;
-            a.logPr_cur[Q * C + m] = mine.logPr;
-            a.logPost_cur[Q * C + m] = mine.logPost;
-            // a swap exchanges the pair's moved / Pmove entries too (MALA.cpp:425-446): what is recorded is the partner's
-            a.moved[m] = (src == m) ? s_own.acc : s_partner.acc;
-            a.Pmove[m] = (src == m) ? s_own.r : s_partner.r;
-            if (m == 0 && a.moved[0]) a.counters[1] += 1;
-            a.counters[8 + m] += a.moved[m];  // per-chain count of recorded moves (the acceptance diagnostic, outputs.cpp:1824-1858)
-            if (m == 0) a.counters[0] = it;
-            if (a.stats && rec >= 0) {  // update_buffer_stat_criteria (MALA.cpp:708)
-                double *r = a.stats + ((size_t)rec * C + m) * 3;
-                r[0] = mine.logL; r[1] = mine.logPr; r[2] = mine.logPost;
-            }
-        }
-        __syncthreads();
-        if (a.samples && rec >= 0)  // update_buffer_params (MALA.cpp:710)
-            for (int i = tid; i < Nv; i += TB) a.samples[((size_t)rec * C + m) * Nv + i] = s_vars[i];
-        if (learn_pending) {
-            double *Aw = a.chol_in_lds ? s_A : scratch + (size_t)m * ((size_t)Nv * Nv + Nv);
-            adapt_chain(a, m, itp, s_z, s_own.r, Aw, Aw + (size_t)Nv * Nv, s_red, s_scal);
-        }
-    } else {
-        for (int i = tid; i < Nv; i += TB) { const double v = curv[(size_t)m * Nv + i]; s_vars[i] = v; newv[(size_t)m * Nv + i] = v; }
-        for (int i = tid; i < Np; i += TB) { const double v = curp[(size_t)m * Np + i]; s_params[i] = v; newp[(size_t)m * Np + i] = v; }
-        if (tid == 0) {
-            a.logL_cur[Q * C + m] = a.logL_cur[P * C + m];
-            a.logPr_cur[Q * C + m] = a.logPr_cur[P * C + m];
-            a.logPost_cur[Q * C + m] = a.logPost_cur[P * C + m];
-        }
+    settle_chain(a, m, it, P, pending, rec, learn_pending, true, s_vars, s_params, s_z, s_red, &s_own, &s_partner);
+    if (pending && learn_pending) {
+        double *Aw = a.chol_in_lds ? s_A : scratch + (size_t)m * ((size_t)Nv * Nv + Nv);
+        adapt_chain(a, m, it - 1, s_z, s_own.r, Aw, Aw + (size_t)Nv * Nv, s_red, s_scal);
     }
     if (!PROPOSE) return;
     __syncthreads();

@@ -5,6 +5,7 @@
 #include "../../include/tamcmc_hip.h"
 #if defined(__HIPCC__)
 #include "dev_unpack.h"
+#include "envelope_row.h"
 #endif
 
 #define TAMCMC_MAX_CHAINS 64  // the reference caps at 24 (MALA.cpp:580-587); BASELINE config 5 asks for 40
@@ -43,6 +44,7 @@ struct DevSamplerArgs {
     double *partials;
     double *bg;           // [C x ntiles x 8] background series per (slot, tile), FAST far field only (else nullptr)
     int tile_bins;
+    EnvRow *env_rows;     // [C] Gaussian-envelope models (ids 0 / 1): the row of each chain's proposal, what its evaluation reads (else nullptr)
     // records
     double *samples, *stats;
 };
@@ -92,6 +94,9 @@ class DevSampler {
     // scheme 2 (fused): slot e NS + s = candidate slot s of candidate set e (NS = 2 Nchains + 8), vector = cand_params of the same slot
     int download_tables(int32_t shape[4], tamcmc_multiplet *rows, int32_t *nrows, double *noise, int32_t *nharvey, int32_t *nnoise,
                         int32_t *status, int32_t *written, double *logPr, double *params);
+    // Audit (tamcmc_sampler_get_envelope_rows), ids 0 / 1: per chain the row of the last iteration's proposal (EnvRow as 24 doubles, the
+    // layout of tamcmc_sampler.h), the vector it was built from (params_prop of that iteration's parity), its log-prior and status
+    int download_envelope_rows(double *rows, double *params, double *logPr, int32_t *status);
     int run(long it0, long n_iter, const char *learn, double *samples, double *stats);
     int run_mala(long it0, long n_iter, const char *learn, double *samples, double *stats);  // use_drift = 1 (dev_mala_impl.h)
 };

@@ -32,6 +32,11 @@
 //     adapted after every test (the next proposal needs the new Cholesky factor, so it cannot be prepared ahead):
 //       k_iterate (one workgroup per chain) settles iteration it-1 (MH test, swap, record, Robbins-Monro update MALA.cpp:296-319,
 //       Cholesky of (Sigma+eps2 I) sigma MALA.cpp:348-350) and proposes iteration it; k_loglike evaluates.
+// (C) ENVELOPE STEP (dev_env_step_impl.h), the Gaussian-envelope models (ids 0 / 1, opt-in: TAMCMC_OPT_ENVELOPE_DEVICE_ENGINE).  They have no
+//     table: k_iterate's proposal ends with the log-prior and the row of scalars the evaluation reads (env_front), and the lockstep
+//     route evaluates it with envelope.hip's kernels on the group's stream (envelope_stage_enqueue) in place of k_loglike.  Stretches
+//     without adaptation run as ONE launch per iteration (k_env_step: every tile of a chain settles, proposes and evaluates) for
+//     spectra up to env_step_max_bins() bins (id 1: 32 768; id 0: 6 144, the measured crossover); the fused step (A) is not used.
 // All per-iteration state is double-buffered by parity: a workgroup reads parity P and writes parity P^1, so the swap needs no
 // inter-workgroup synchronisation inside (B) and a launch never overwrites what it still reads in (A).  Both schemes keep the
 // chains' state in the same arrays; a stretch hands over to the next with the parity only.
@@ -53,6 +58,7 @@
 #include <utility>
 #include <vector>
 
+#include "../../include/tamcmc_sampler.h"
 #include "ctx.h"
 #include "rgb_prestep.h"
 #include "rgb_front.h"
@@ -60,6 +66,7 @@
 #include "kernels.h"
 #include "loglike_tile.h"
 #include "dev_unpack.h"
+#include "envelope.h"
 #include "fd_batch.h"
 #include "mode_tables.h"
 #include "rng.h"
@@ -70,6 +77,7 @@ namespace tamcmc {
 namespace {
 
 #include "dev_iterate_impl.h"
+#include "dev_env_step_impl.h"
 #include "dev_step_impl.h"
 #include "dev_mala_impl.h"
 
@@ -97,6 +105,8 @@ struct DevSampler::Impl {
     FdBatch fd;
     DevBuf<unsigned char> fd_block;
     DevBuf<double> fd_part, fd_S, fd_model, fd_bg;
+    DevBuf<double> env_part;  // (C): the tiles' partial sums by launch parity
+    bool env = false;         // ids 0 / 1: no table; rows (a.env_rows), envelope.hip's kernels or k_env_step
     DevBuf<double> fused_bg, fused_part;  // (A): the candidates' background series, the tiles' partial sums by parity (see run())
     MalaArgs mala{};
     bool grad_valid = false;
@@ -205,7 +215,7 @@ DevSampler::~DevSampler() {
     }
 #endif
     for (void *p : impl->allocs) (void)hipFree(p);
-    impl->fd_block.release(); impl->fd_part.release(); impl->fd_S.release(); impl->fd_model.release(); impl->fd_bg.release(); impl->fused_bg.release(); impl->fused_part.release();
+    impl->fd_block.release(); impl->fd_part.release(); impl->fd_S.release(); impl->fd_model.release(); impl->fd_bg.release(); impl->fused_bg.release(); impl->fused_part.release(); impl->env_part.release();
     if (impl->h_pack) (void)hipHostFree(impl->h_pack);
     for (int i = 0; i < impl->n_ev; i++) { (void)hipEventDestroy(impl->ev[i][0]); (void)hipEventDestroy(impl->ev[i][1]); }
     for (int i = 0; i < impl->n_gev; i++) { (void)hipEventDestroy(impl->gev[i][0]); (void)hipEventDestroy(impl->gev[i][1]); }
@@ -240,10 +250,18 @@ int DevSampler::init(tamcmc_hip_ctx *c, const DevSamplerInit &in) {
     DevSamplerArgs &a = I.a;
     a.desc.model_id = in.model_id; a.desc.prior_class = in.prior_class; a.C = in.C; a.desc.Np = in.Np; a.Nv = in.Nv;
     I.rgb = is_rgb_model(in.model_id);
+    I.env = is_envelope_model(in.model_id);
+    if (I.env) {
+        // opt-in (TAMCMC_OPT_ENVELOPE_DEVICE_ENGINE at creation: tamcmc_sampler_create has refused already, before building anything); the
+        // Langevin step of these ids stays on the host engine
+        if (!c->envelope_device_engine || in.use_drift) return TAMCMC_ERR_BAD_MODEL;
+        if (in.prior_class != in.model_id) return TAMCMC_ERR_BAD_MODEL;  // priors_ctrl.list pairs class 0 with id 0, class 1 with id 1
+        if (in.Np < envelope_nparams(in.model_id) || c->Nx > 0x7fffffff / 2) return TAMCMC_ERR_BAD_ARG;
+    }
 #ifdef TAMCMC_PROBE
     if (const char *ep = getenv("TAMCMC_PROBE_ADAPT")) a.probe = atoi(ep);
 #endif
-    a.desc.per = I.rgb ? 0 : mt::count_multiplets(in.model_id, in.plength);
+    a.desc.per = (I.rgb || I.env) ? 0 : mt::count_multiplets(in.model_id, in.plength);  // (ids 0 / 1: no table)
     I.h_plength.assign(in.plength, in.plength + 11);
     I.use_drift = in.use_drift != 0; I.delta = in.delta; I.fd_step_rel = in.fd_step_rel > 0 ? in.fd_step_rel : 1e-7;
     I.prior_class = in.prior_class; I.model_id = in.model_id;
@@ -305,6 +323,11 @@ int DevSampler::init(tamcmc_hip_ctx *c, const DevSamplerInit &in) {
     DCHK(I.dalloc(&a.lz, 2 * C * Nv)); DCHK(I.dalloc(&a.LT, C * Nv * Nv)); DCHK(I.dalloc(&a.cov, C * Nv * Nv)); DCHK(I.dalloc(&a.mu, C * Nv)); DCHK(I.dalloc(&a.sigma, C));
     DCHK(I.dalloc(&a.mults, CD * (size_t)a.desc.per + 1)); DCHK(I.dalloc(&a.pairs, 2 * CD)); DCHK(I.dalloc(&a.nh, CD)); DCHK(I.dalloc(&a.nn, CD));
     DCHK(I.dalloc(&a.noise, CD * (size_t)a.desc.stride));
+    a.env_rows = nullptr;
+    if (I.env) {
+        DCHK(I.dalloc(&a.env_rows, C));
+        DCHK(hipMemsetAsync(a.env_rows, 0, C * sizeof(EnvRow), st));
+    }
     DCHK(hipMemsetAsync(a.counters, 0, (8 + C + 64) * sizeof(long), st));
     DCHK(hipMemsetAsync(a.moved, 0, C * sizeof(int), st));
     DCHK(hipMemsetAsync(a.Pmove, 0, C * sizeof(double), st));
@@ -367,7 +390,7 @@ int DevSampler::init(tamcmc_hip_ctx *c, const DevSamplerInit &in) {
         f.bg = nullptr;
         // the candidate roles borrow the tile workgroup's LDS: a parameter vector too long for it keeps the lockstep scheme
         const size_t role_lds = (Np + 2 * Nv + 1) * sizeof(double) + unpack_lds_bytes() + 32;
-        I.fused_ok = !I.rgb && role_lds <= sizeof(tile::TileLds<tile::M_FAST_DIRECT, 64>);
+        I.fused_ok = !I.rgb && !I.env && role_lds <= sizeof(tile::TileLds<tile::M_FAST_DIRECT, 64>);
     }
     DCHK(hipStreamSynchronize(st));
     return TAMCMC_OK;
@@ -435,6 +458,32 @@ int DevSampler::download_tables(int32_t shape[4], tamcmc_multiplet *rows, int32_
     return TAMCMC_OK;
 }
 
+int DevSampler::download_envelope_rows(double *rows, double *params, double *logPr, int32_t *status) {
+    Impl &I = *impl;
+    tamcmc_hip_ctx *c = I.ctx;
+    const DevSamplerArgs &a = I.a;
+    if (!I.env) return TAMCMC_ERR_BAD_MODEL;
+    if (!I.last_scheme) return TAMCMC_ERR_BAD_ARG;  // (no iteration yet: no proposal)
+    DCHK(hipSetDevice(c->device));
+    DCHK(hipStreamSynchronize(c->stream));  // (every entry point returns with the sampler's streams idle)
+    const size_t C = (size_t)a.C, Np = (size_t)a.desc.Np, Q = (size_t)I.last_prop_parity;
+    if (rows) {
+        std::vector<EnvRow> h(C);
+        DCHK(hipMemcpy(h.data(), a.env_rows, C * sizeof(EnvRow), hipMemcpyDeviceToHost));
+        for (size_t m = 0; m < C; m++) {  // the layout of tamcmc_sampler.h
+            const EnvRow &R = h[m];
+            double *r = rows + m * TAMCMC_ENVELOPE_ROW_N;
+            r[0] = R.amp; r[1] = R.numax; r[2] = R.sig2; r[3] = R.N0;
+            for (int k = 0; k < 2; k++) { r[4 + k] = R.H[k]; r[6 + k] = R.lna[k]; r[8 + k] = R.pw[k]; r[22 + k] = R.hon[k] ? 1.0 : 0.0; }
+            for (int k = 0; k < 3; k++) { r[10 + k] = R.b[k]; r[13 + k] = R.lnb[k]; r[16 + k] = R.c[k]; r[19 + k] = R.a2[k]; }
+        }
+    }
+    if (params) DCHK(hipMemcpy(params, a.params_prop + Q * C * Np, C * Np * 8, hipMemcpyDeviceToHost));
+    if (logPr) DCHK(hipMemcpy(logPr, a.logPr_prop + Q * C, C * 8, hipMemcpyDeviceToHost));
+    if (status) DCHK(hipMemcpy(status, a.status_prop + Q * C, C * 4, hipMemcpyDeviceToHost));
+    return TAMCMC_OK;
+}
+
 void DevSampler::info(long out[14]) const {
     const Impl &I = *impl;
     unsigned long long qc[3] = {0, 0, 0};  // (every entry point returns with the sampler's streams idle)
@@ -442,7 +491,7 @@ void DevSampler::info(long out[14]) const {
     out[8] = I.n_stretch; out[9] = (long)qc[0]; out[10] = (long)qc[1]; out[13] = (long)qc[2];
     out[0] = I.a.Nv; out[1] = I.a.desc.Np;
     out[2] = I.use_drift ? I.mala_chol_lds : I.a.chol_in_lds;
-    out[3] = (I.fused_ok && !I.use_drift) ? 1 : 0;
+    out[3] = I.env ? (I.a.desc.Nx <= env_step_max_bins(I.model_id) ? 1 : 0) : (I.fused_ok && !I.use_drift) ? 1 : 0;  // (ids 0 / 1: k_env_step)
     out[4] = I.G; out[5] = I.it_fused; out[6] = I.it_lockstep; out[7] = I.a.C;
     out[11] = I.it_joint; out[12] = I.it_window;
 }
@@ -468,7 +517,8 @@ int DevSampler::upload_state(const double *vars, const double *params, const dou
         int n = 0, nh = 0, nn = 0;
         const int tb = tile_bins(c->wgs, c->K);
         I.tile_rot = 0;
-        if (I.rgb) {  // a little below the lowest radial mode (rgb_stage_params' rule)
+        if (I.env) I.tile_rot = 0;  // (no table, and k_loglike's launch order is not used)
+        else if (I.rgb) {  // a little below the lowest radial mode (rgb_stage_params' rule)
             const double *fl0 = params + I.h_plength[0] + I.h_plength[1];
             const double fmin = *std::min_element(fl0, fl0 + I.h_plength[2]);
             const int ntiles = (int)((c->Nx + tb - 1) / tb);
@@ -698,6 +748,8 @@ struct DevSampler::Impl::RunCall {
     int goff[5];                 // chain groups [goff[g], goff[g+1]) of the lockstep scheme
     double *zc_smp = nullptr, *zc_st = nullptr;  // the caller's record buffers as the device sees them (Impl::device_view), else null
     bool use_fused = false;
+    bool env_step = false;       // (C): quiet stretches run as k_env_step launches
+    int env_nchunk = 0;
     bool split_ok = false;       // fused stretches run as two chain groups [0, f.xsplit), [f.xsplit, C)
     int P;                       // parity of the state buffers that hold the chains' current state
     // (A) the stretch being enqueued
@@ -721,10 +773,22 @@ struct DevSampler::Impl::RunCall {
         a.tile_bins = tb;
         a.bg = nullptr;
         use_fused = I.fused_ok && c->step_scheme != 1 && c->wgs == 64 && (c->K == 4 || c->K == 8 || c->K == 16);
+        if (I.env) {
+            // (C): envelope.hip's 1024-bin tiles whatever the context's geometry options say; the xi partials (id 0) and the tile
+            // partials are indexed by chain, so chain groups on different streams never share a slot
+            a.ntiles = (a.desc.Nx + ETILE - 1) / ETILE;
+            a.tile_bins = ETILE;
+            env_nchunk = (a.desc.Nx + ECHUNK - 1) / ECHUNK;
+            DCHK(c->d_part.reserve(C * (size_t)a.ntiles * 2));
+            a.partials = c->d_part.p;
+            DCHK(c->d_env.reserve(C * (size_t)env_nchunk * 3));
+            env_step = c->step_scheme != 1 && a.desc.Nx <= env_step_max_bins(I.model_id);
+            if (env_step) DCHK(I.env_part.reserve(2 * C * (size_t)a.ntiles * 2));
+        }
         I.f.qmargin = c->quick_decide == 1 ? (double)INFINITY : 1e-11;  // (TAMCMC_OPT_QUICK_DECIDE: a test facility)
         const size_t NS = (size_t)I.f.NS;
         I.f.bg = nullptr;
-        if (c->precision == TAMCMC_PRECISION_FAST) {
+        if (c->precision == TAMCMC_PRECISION_FAST && !I.env) {
             // background series per (slot, tile).  (B): C slots in the context's scratch (rewritten every iteration).  (A): 2 x NS slots of
             // the sampler's OWN -- the candidates prepared by the last launch of a call are carried over to the next call, and anything else
             // that runs on the context in between (another sampler, a batched evaluation) rewrites the context's scratch
@@ -858,7 +922,14 @@ struct DevSampler::Impl::RunCall {
                 for (int g = 0; g < G; g++) {
                     hipEvent_t *pair = g == 0 ? T.lockstep_pair(i - ia, ev_every) : nullptr;
                     if (pair) DCHK(hipEventRecord(pair[0], I.gst[g]));
-                    DCHK(launch_loglike(la[g], c->precision, c->wgs, c->K, false, I.gst[g]));
+                    if (I.env) {  // the rows k_iterate has just written -> the partials the next k_iterate's accept_result sums
+                        const size_t first = (size_t)goff[g];
+                        if (int rc = envelope_stage_enqueue(c, I.model_id, goff[g + 1] - goff[g], a.env_rows + first, c->d_env.p + first * env_nchunk * 3,
+                                                            a.partials + first * a.ntiles * 2, I.gst[g]))
+                            return rc;
+                    } else {
+                        DCHK(launch_loglike(la[g], c->precision, c->wgs, c->K, false, I.gst[g]));
+                    }
                     if (pair) DCHK(hipEventRecord(pair[1], I.gst[g]));
                 }
             }
@@ -1025,6 +1096,43 @@ struct DevSampler::Impl::RunCall {
         return TAMCMC_OK;
     }
 
+    // ---- (C) k_env_step over [ia, ib) (no adaptation inside): one launch per iteration on the context stream, then a settle-only launch
+    template <int KIND>
+    int run_env_step_kind(long ia, long ib) {
+        const long len = ib - ia;
+        if (KIND == 0 && env_nchunk > ENV_STEP_MAX_CHUNKS) return TAMCMC_ERR_BAD_ARG;  // (k_env_step's chunk partials in LDS; prepare() never routes this here)
+        I.armed_it = -1;
+        I.it_fused += len;
+        I.n_stretch += 1;
+        const size_t half = (size_t)a.C * a.ntiles * 2;
+        const size_t lds = env_step_lds_bytes((size_t)a.desc.Np, (size_t)a.Nv);
+        EnvStepArgs e;
+        e.x = c->dx.p; e.y = c->dy.p; e.logx = c->dlogx.p;
+        e.h = c->hx[1] - c->hx[0]; e.xmax = c->xmax; e.nchunk = env_nchunk;
+        T.begin_fused(len);
+        if (T.stretch_pair()) DCHK(hipEventRecord(T.stretch_pair()[0], st));
+        int pending = 0;
+        for (long i = ia; i <= ib; i++) {
+            const long rec = (pending && (samples || stats)) ? i - 1 : (long)-1;
+            DevSamplerArgs la_ = args;
+            la_.partials = I.env_part.p + (size_t)P * half;  // what the previous launch of the stretch wrote
+            e.part_wr = I.env_part.p + (size_t)(P ^ 1) * half;
+            if (i < ib) hipLaunchKernelGGL((k_env_step<KIND, true>), dim3(a.ntiles, a.C), dim3(TB), lds, st, la_, e, it0 + i, P, pending, rec);
+            else hipLaunchKernelGGL((k_env_step<KIND, false>), dim3(1, a.C), dim3(TB), lds, st, la_, e, it0 + i, P, pending, rec);
+            P ^= 1;
+            pending = 1;
+        }
+        DCHK(hipGetLastError());
+        if (T.stretch_pair()) DCHK(hipEventRecord(T.stretch_pair()[1], st));  // (read after the call's final synchronisation)
+        T.end_fused(len, false, 0);
+        I.last_scheme = 2;
+        I.last_prop_parity = P ^ 1;  // (the closing launch read the last proposals from parity P before the flip above)
+        return TAMCMC_OK;
+    }
+    int run_env_step(long ia, long ib) {
+        return I.model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN ? run_env_step_kind<0>(ia, ib) : run_env_step_kind<1>(ia, ib);
+    }
+
     // every launch is enqueued: the records, the wait for the streams, the kernel times
     int finish() {
         I.parity = P;
@@ -1058,8 +1166,8 @@ int DevSampler::run(long it0, long n_iter, const char *learn, double *samples, d
     tl.mark();  // (set-up of the call done: buffers, argument blocks)
     for (long i = 0, end = 0; i < n_iter; i = end) {
         bool is_fused;
-        next_stretch(learn, n_iter, i, r.use_fused, &end, &is_fused);
-        if (int rc = is_fused ? r.run_fused(i, end) : r.run_lockstep(i, end)) return rc;
+        next_stretch(learn, n_iter, i, r.use_fused || r.env_step, &end, &is_fused);
+        if (int rc = !is_fused ? r.run_lockstep(i, end) : r.env_step ? r.run_env_step(i, end) : r.run_fused(i, end)) return rc;
     }
     return r.finish();
 }

@@ -11,7 +11,7 @@
 
 namespace tamcmc {
 
-inline bool is_envelope_model(int model_id) {
+__host__ __device__ inline bool is_envelope_model(int model_id) {
     return model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN || model_id == TAMCMC_MODEL_HARVEY_GAUSSIAN;
 }
 // parameters each model reads: [H1, tc1, p1, H2, tc2, p2, B0, Amax, numax, Gauss_sigma] / 14 noise, Amax, numax, sigma, mu_numax, omega_numax
@@ -21,6 +21,11 @@ inline int64_t envelope_nparams(int model_id) { return model_id == TAMCMC_MODEL_
 // depend on the batch it sits in).  model (device pointer or nullptr): B x Nx rows.  Enqueued on the context stream; S_dev is the
 // context's d_S (B doubles); the caller copies it back.
 int envelope_enqueue(tamcmc_hip_ctx *c, int model_id, int B, const double *params, int64_t Nparams, double *model_dev);
+
+// The device-resident sampler's lockstep route (dev_sampler.hip): k_env_ksi (id 0) and k_env_eval for `cnt` chains whose rows (EnvRow,
+// envelope_row.h) k_iterate has left on the device, enqueued on `st`.  rows_dev, ksi_part (cnt x chunks x 3) and partials (cnt x tiles x
+// 2) point at the FIRST of these chains' entries: every buffer is indexed by chain, so chain groups on different streams share no slot.
+int envelope_stage_enqueue(tamcmc_hip_ctx *c, int model_id, int cnt, const void *rows_dev, double *ksi_part, double *partials, hipStream_t st);
 
 // tamcmc_hip_loglike_params_batch for ids 0 and 1
 int envelope_loglike_params_batch(tamcmc_hip_ctx *c, int model_id, int B, const double *params, int64_t Nparams, const double *Tcoefs,

@@ -14,6 +14,9 @@
 // The chunk and tile sizes depend on Nx only, never on B, and every sum runs in a fixed order: a vector's logL is bit-identical whatever
 // batch it sits in and whatever its position there.
 //
+// The bodies of the two passes and the row builder are in envelope_row.h: the device-resident sampler's one-launch step (k_env_step,
+// dev_env_step_impl.h) evaluates its tiles through the same statements.
+//
 // One arithmetic mode (TAMCMC_OPT_PRECISION does not apply): double, the reference's order of operations per bin except for the power laws
 // taken through exp/log and the trapezoid sums taken as a tree instead of a left-to-right loop.
 #include <hip/hip_runtime.h>
@@ -25,6 +28,7 @@
 #include "../../include/tamcmc_hip.h"
 #include "ctx.h"
 #include "envelope.h"
+#include "envelope_row.h"
 #include "fd_batch.h"
 #include "kernels.h"
 #include "priors_impl.h"
@@ -33,68 +37,11 @@ namespace tamcmc {
 
 namespace {
 
-constexpr int EWG = 256;          // workgroup of both passes: four waves
-constexpr int EK = 4;             // k_env_eval: bins per thread -> 1024-bin tiles
-constexpr int EK1 = 16;           // k_env_ksi: bins per thread -> 4096-bin chunks
-constexpr int ETILE = EWG * EK;
-constexpr int ECHUNK = EWG * EK1;
-
-// what the host forms once per parameter vector (double, the reference's expressions)
-struct EnvRow {
-    double amp, numax, sig2;  // Gaussian: amp * exp((-0.5 (x - numax)^2) / sig2)       (id 0: amp * eta^2 first)
-    double N0;                // white noise
-    double H[2], lna[2], pw[2];  // id 1: H_k / (1 + exp(pw_k (lna_k + ln x))), lna_k = ln(1e-3 tc_k), term skipped when tc_k == 0
-    double b[3], lnb[3], c[3], a2[3];  // id 0: (xi_k a_k^2 / b_k) / (1 + exp(c_k (ln x - ln b_k))), xi_k from the trapezoid sums
-    int32_t hon[2];
-    int32_t pad[2];
-};
-
-// t^p as the reference's pow(t, p) for t >= 0, from ln t: pow(t, 0) = 1 also at t = 0 (exp(0 * -inf) would be NaN)
-__device__ __forceinline__ double pow_from_log(double p, double lt) { return p == 0.0 ? 1.0 : exp(p * lt); }
-
-template <int NV>
-__device__ __forceinline__ void env_block_reduce(double (&v)[NV], double *s_red, double *out) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < NV; i++) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v[i] = v[i] + __shfl_down(v[i], off, 64);
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < NV; i++) s_red[wave * NV + i] = v[i];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int i = 0; i < NV; i++) {
-            double s = s_red[i];
-            for (int w = 1; w < EWG / 64; w++) s = s + s_red[w * NV + i];
-            out[i] = s;
-        }
-    }
-}
-
 __global__ void __launch_bounds__(EWG) k_env_ksi(const double *logx, int Nx, int nchunk, const EnvRow *rows, double *part) {
     __shared__ double s_red[3 * (EWG / 64)];
     const int chunk = blockIdx.x, b = blockIdx.y;
-    const EnvRow &R = rows[b];
-    const double lnb0 = R.lnb[0], lnb1 = R.lnb[1], lnb2 = R.lnb[2], c0 = R.c[0], c1 = R.c[1], c2 = R.c[2];
-    double s[3] = {0.0, 0.0, 0.0};
-    const int base = chunk * ECHUNK + threadIdx.x;
-#pragma unroll 4
-    for (int k = 0; k < EK1; k++) {
-        const int i = base + k * EWG;
-        if (i < Nx) {
-            const double lx = logx[i];
-            const double w = (i == 0 || i == Nx - 1) ? 0.5 : 1.0;
-            s[0] = s[0] + w * (1.0 / (1.0 + pow_from_log(c0, lx - lnb0)));
-            s[1] = s[1] + w * (1.0 / (1.0 + pow_from_log(c1, lx - lnb1)));
-            s[2] = s[2] + w * (1.0 / (1.0 + pow_from_log(c2, lx - lnb2)));
-        }
-    }
     double out[3];
-    env_block_reduce<3>(s, s_red, out);
+    env_ksi_chunk(logx, Nx, chunk, rows[b], s_red, out);
     if (threadIdx.x == 0) {
         double *p = part + ((size_t)b * nchunk + chunk) * 3;
         p[0] = out[0];
@@ -111,64 +58,9 @@ __global__ void __launch_bounds__(EWG) k_env_eval(const double *x, const double 
     __shared__ double s_coef[3];
     const int tile = blockIdx.x, b = blockIdx.y;
     const EnvRow &R = rows[b];
-    if (KIND == 0) {
-        // xi_k = b_k / (h * sum_k): get_ksinorm (noise_models.cpp:70-89), the chunk partials summed in a fixed order
-        double s[3] = {0.0, 0.0, 0.0};
-        for (int ch = threadIdx.x; ch < nchunk; ch += EWG) {
-            const double *p = ksi_part + ((size_t)b * nchunk + ch) * 3;
-            s[0] = s[0] + p[0];
-            s[1] = s[1] + p[1];
-            s[2] = s[2] + p[2];
-        }
-        double out[3];
-        env_block_reduce<3>(s, s_red, out);
-        if (threadIdx.x == 0) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                const double integral = out[k] * h;
-                const double ksi = R.b[k] / integral;
-                s_coef[k] = ksi * R.a2[k] / R.b[k];
-            }
-        }
-        __syncthreads();
-    }
-    const double amp = R.amp, numax = R.numax, sig2 = R.sig2, N0 = R.N0;
-    double acc[2] = {0.0, 0.0};
-    const int base = tile * ETILE + threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < EK; k++) {
-        const int i = base + k * EWG;
-        if (i < Nx) {
-            const double xi = x[i], yi = y[i], lx = logx[i];
-            const double d = xi - numax;
-            const double g = exp((-0.5 * (d * d)) / sig2);
-            double M;
-            if (KIND == 0) {
-                // eta^2 = sinc^2(pi x / (2 x_max)), 1 at a first bin x = 0 (eta_squared_Kallinger2014)
-                double eta2 = 1.0;
-                if (!(i == 0 && xi == 0.0)) {
-                    const double a = 0.5 * M_PI * xi / xmax;  // ((0.5 pi) x) / x_max, the reference's grouping
-                    const double sn = sin(a) / a;
-                    eta2 = sn * sn;
-                }
-                M = (amp * eta2) * g;
-                M = M + N0;  // Kallinger2014: Power = y + white noise, then the three super-Lorentzians, unfiltered (see tamcmc_hip.h)
-#pragma unroll
-                for (int q = 0; q < 3; q++) M = M + s_coef[q] * (1.0 / (pow_from_log(R.c[q], lx - R.lnb[q]) + 1.0));
-            } else {
-                M = amp * g;
-#pragma unroll
-                for (int q = 0; q < 2; q++)
-                    if (R.hon[q]) M = M + R.H[q] * (1.0 / (pow_from_log(R.pw[q], R.lna[q] + lx) + 1.0));
-                M = M + N0;
-            }
-            if (WRITE_MODEL) model[(size_t)b * Nx + i] = M;
-            acc[0] = acc[0] + yi / M;
-            acc[1] = acc[1] + log(M);
-        }
-    }
+    if (KIND == 0) env_ksi_coef(ksi_part + (size_t)b * nchunk * 3, nchunk, h, R, s_red, s_coef);
     double out[2];
-    env_block_reduce<2>(acc, s_red, out);
+    env_tile<KIND, WRITE_MODEL>(x, y, logx, Nx, tile, xmax, R, s_coef, WRITE_MODEL ? model + (size_t)b * Nx : nullptr, s_red, out);
     if (threadIdx.x == 0) {
         double *p = part + ((size_t)b * ntiles + tile) * 2;
         p[0] = out[0];
@@ -184,45 +76,6 @@ __global__ void __launch_bounds__(64) k_env_prior(int prior_class, int n, const 
     int st = TAMCMC_OK;
     lp[v] = (double)pr::prior_serial(prior_class, P + (size_t)v * Np, nullptr, Np, pp, sw, nullptr, &st);
     status[v] = st;
-}
-
-// EnvRow of one vector: the scalar part of the model functions
-void env_row(int model_id, const double *p, EnvRow &R) {
-    std::memset(&R, 0, sizeof R);
-    if (model_id == TAMCMC_MODEL_HARVEY_GAUSSIAN) {
-        R.amp = std::fabs(p[7]);
-        R.numax = p[8];  // (not taken in absolute value by model_Harvey_Gaussian)
-        R.sig2 = std::pow(std::fabs(p[9]), 2);
-        for (int q = 0; q < 2; q++) {  // harvey_like(|params[0:7]|, ...): [H, tc, p] x 2, then B0
-            const double H = std::fabs(p[3 * q]), tc = std::fabs(p[3 * q + 1]), pw = std::fabs(p[3 * q + 2]);
-            R.hon[q] = (tc != 0) ? 1 : 0;
-            R.H[q] = H;
-            R.lna[q] = std::log((1e-3) * tc);
-            R.pw[q] = pw;
-        }
-        R.N0 = std::fabs(p[6]);
-        return;
-    }
-    // model_Kallinger2014_Gaussian + Kallinger2014(numax, mu_numax, params[0:14], ...)
-    const double Amax = std::fabs(p[14]), numax = std::fabs(p[15]), sig = std::fabs(p[16]), mu_numax = p[17];
-    R.amp = std::fabs(Amax);
-    R.numax = numax;
-    R.sig2 = std::pow(std::fabs(sig), 2);
-    const double a0 = std::fabs(p[0] * std::pow(std::fabs(numax), p[1]));
-    const double b0 = std::fabs(p[2] * std::pow(std::fabs(numax + mu_numax), p[3]));
-    const double c0 = std::fabs(p[4]);
-    const double a1 = p[5], a2 = p[6];
-    const double b1 = std::fabs(p[7] * std::pow(std::fabs(numax + mu_numax), p[8]));
-    const double b2 = std::fabs(p[10] * std::pow(std::fabs(numax + mu_numax), p[11]));
-    const double c1 = std::fabs(p[9]), c2 = std::fabs(p[12]);
-    R.N0 = std::fabs(p[13]);
-    const double bb[3] = {b0, b1, b2}, cc[3] = {c0, c1, c2}, aa[3] = {a0, a1, a2};
-    for (int k = 0; k < 3; k++) {
-        R.b[k] = bb[k];
-        R.lnb[k] = std::log(bb[k]);
-        R.c[k] = cc[k];
-        R.a2[k] = std::pow(aa[k], 2);
-    }
 }
 
 }  // namespace
@@ -258,6 +111,23 @@ int envelope_enqueue(tamcmc_hip_ctx *c, int model_id, int B, const double *param
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, launch_finalize(c->d_part.p, B, ntiles, c->d_S.p, st));
     if (c->timing) HIPCHK(c, hipEventRecord(c->ev1, st));
+    return TAMCMC_OK;
+}
+
+// The sampler's lockstep route: the rows are on the device already (written by k_iterate), one per chain
+int envelope_stage_enqueue(tamcmc_hip_ctx *c, int model_id, int cnt, const void *rows_dev, double *ksi_part, double *partials, hipStream_t st) {
+    const int Nx = (int)c->Nx;
+    const int ntiles = (Nx + ETILE - 1) / ETILE, nchunk = (Nx + ECHUNK - 1) / ECHUNK;
+    const EnvRow *rows = (const EnvRow *)rows_dev;
+    const double h = c->hx[1] - c->hx[0];
+    const dim3 grid(ntiles, cnt);
+    if (model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN) {
+        hipLaunchKernelGGL(k_env_ksi, dim3(nchunk, cnt), dim3(EWG), 0, st, c->dlogx.p, Nx, nchunk, rows, ksi_part);
+        hipLaunchKernelGGL((k_env_eval<0, false>), grid, dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, Nx, ntiles, nchunk, h, c->xmax, rows, ksi_part, nullptr, partials);
+    } else {
+        hipLaunchKernelGGL((k_env_eval<1, false>), grid, dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, Nx, ntiles, nchunk, h, c->xmax, rows, nullptr, nullptr, partials);
+    }
+    HIPCHK(c, hipGetLastError());
     return TAMCMC_OK;
 }
 

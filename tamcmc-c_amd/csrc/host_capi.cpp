@@ -17,6 +17,7 @@ using namespace tamcmc;
 extern "C" {
 void tamcmc_hip_ctx_attach(tamcmc_hip_ctx *c);  // capi.hip (private)
 void tamcmc_hip_ctx_detach(tamcmc_hip_ctx *c);
+int tamcmc_hip_envelope_device_engine(const tamcmc_hip_ctx *c);  // the context's TAMCMC_OPT_ENVELOPE_DEVICE_ENGINE
 }
 
 struct tamcmc_sampler {
@@ -68,8 +69,10 @@ int tamcmc_sampler_create(tamcmc_sampler **out, tamcmc_hip_ctx *ctx, const tamcm
     if (!out || !ctx || !c || !c->inputs || !c->relax || !c->plength || !c->priors || !c->priors_switch) return TAMCMC_ERR_BAD_ARG;
     if (c->Nchains < 1 || c->Nparams < 1) return TAMCMC_ERR_BAD_ARG;
     *out = nullptr;
-    // Gaussian-envelope fits (ids 0, 1): host-driven engine only (random walk or Langevin); the device-resident engine has no kernels for them
-    if ((c->model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN || c->model_id == TAMCMC_MODEL_HARVEY_GAUSSIAN) && c->engine == 1)
+    // Gaussian-envelope fits (ids 0, 1) on the device-resident engine: opt-in and random walk only (TAMCMC_OPT_ENVELOPE_DEVICE_ENGINE, read at
+    // this moment); refused before anything is built
+    if ((c->model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN || c->model_id == TAMCMC_MODEL_HARVEY_GAUSSIAN) && c->engine == 1 &&
+        (c->use_drift || !tamcmc_hip_envelope_device_engine(ctx)))
         return TAMCMC_ERR_BAD_MODEL;
     auto s = std::make_unique<tamcmc_sampler>();
     Config &g = s->cfg;
@@ -333,6 +336,12 @@ int tamcmc_sampler_get_tables(const tamcmc_sampler *s, int32_t *shape, void *row
     if (!s || !shape) return TAMCMC_ERR_BAD_ARG;
     if (!s->dev) return TAMCMC_ERR_BAD_MODEL;
     return s->dev->download_tables(shape, (tamcmc_multiplet *)rows, nrows, noise, nharvey, nnoise, status, written, logprior, params);
+}
+
+int tamcmc_sampler_get_envelope_rows(const tamcmc_sampler *s, double *rows, double *params, double *logprior, int32_t *status) {
+    if (!s) return TAMCMC_ERR_BAD_ARG;
+    if (!s->dev) return TAMCMC_ERR_BAD_MODEL;
+    return s->dev->download_envelope_rows(rows, params, logprior, status);
 }
 
 int tamcmc_sampler_get_move_counts(const tamcmc_sampler *s, int64_t *moves) {

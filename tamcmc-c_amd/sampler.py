@@ -27,6 +27,7 @@ EXTRA_ABI += [
     ("tamcmc_sampler_get_info", C.c_int, [_vp, _i64p, C.c_int32]),
     ("tamcmc_sampler_get_move_counts", C.c_int, [_vp, _i64p]),
     ("tamcmc_sampler_get_tables", C.c_int, [_vp, _ip, _vp, _ip, _dp, _ip, _ip, _ip, _ip, _dp, _dp]),
+    ("tamcmc_sampler_get_envelope_rows", C.c_int, [_vp, _dp, _dp, _dp, _ip]),
     ("tamcmc_sampler_get_gradient", C.c_int, [_vp, _dp, _dp, _ip]),
     ("tamcmc_sampler_get_last_test", C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     ("tamcmc_outputs_write_acceptance", C.c_int, [C.c_char_p, C.c_double, _dp, C.c_int32, C.c_int32]),
@@ -199,6 +200,21 @@ class Sampler:
                 raise TamcmcError(rc, "tamcmc_sampler_get_tables")
         return {"scheme": scheme, "tables": [rows[s, :max(nr[s], 0)].copy() for s in range(n)], "noise": noise, "nharvey": nh, "nnoise": nn,
                 "status": st, "written": wr, "logprior": lp, "params": par}
+
+    ENVELOPE_ROW_FIELDS = ("amp", "numax", "sig2", "N0", "H0", "H1", "lna0", "lna1", "pw0", "pw1", "b0", "b1", "b2", "lnb0", "lnb1", "lnb2",
+                           "c0", "c1", "c2", "a2_0", "a2_1", "a2_2", "hon0", "hon1")
+
+    def envelope_rows(self):
+        """tamcmc_sampler_get_envelope_rows (device engine, model ids 0 / 1): a dict with rows [Nchains x 24] (the scalars the last
+        iteration's proposals were evaluated from, columns named by ENVELOPE_ROW_FIELDS), params [Nchains x Nparams] (the vectors they
+        were built from), logprior and status [Nchains]."""
+        nc = self.nchains
+        rows, par = np.zeros((nc, len(self.ENVELOPE_ROW_FIELDS))), np.zeros((nc, self._keep["inputs"].size))
+        lp, st = np.zeros(nc), np.zeros(nc, dtype=np.int32)
+        rc = self._L.tamcmc_sampler_get_envelope_rows(self._h, _p(rows), _p(par), _p(lp), _p(st, _ip))
+        if rc != OK:
+            raise TamcmcError(rc, "tamcmc_sampler_get_envelope_rows")
+        return {"rows": rows, "params": par, "logprior": lp, "status": st}
 
     def move_counts(self):
         """Per chain: iterations since creation whose record carries moved = 1 (tamcmc_sampler_get_move_counts)."""
