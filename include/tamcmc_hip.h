@@ -238,7 +238,12 @@ int tamcmc_hip_rgb_mixed_modes(tamcmc_hip_ctx *ctx, int model_id, const double *
  * Tolerance (FAST arithmetic, windowed differences: TAMCMC_OPT_FD_WINDOWED): the difference is formed term by term against the stored
  * base point -- per bin as the series in u = dM/M0 (five terms, closed form beyond |u| = 0.01), and on tiles where every changed
  * multiplet is in the far field from moments of the base point (first and second order in u; used where max|u| <= 1e-5, what is
- * omitted is below 1e-10 of the leading term).  Against the brute-force difference of two full evaluations it agrees to that
+ * omitted is below 1e-10 of the leading term).  Per slot, the un-tempered difference dS = grad h_applied T / (-p) is within
+ * truncation (first omitted term of the series / of the moment form, per bin) + far-field truncation (tau(rho, n) of each far delta
+ * row's own rho, TAU_ASYM with asymmetry, the background series' budget for a changed noise row) + 332 x 2^-53 sum_i w_i A_i (w_i =
+ * |1 - y_i/M0_i| / M0_i, A_i = the absolute values summed into dM_i) + 1e-12 sum_i |f_i| of the exact difference of the two tables the batch
+ * built (tests/delta_reference.py derives each part; tests/test_gpu_delta_reference.py).  Against the brute-force
+ * difference of two full evaluations it agrees to that
  * difference's own cancellation noise (~5e-15 Nx / h) + 1e-6 of the gradient's scale (tests/test_gpu_parity.py).
  * Ids 0 and 1: every parameter moves every bin, so the batch is brute force -- C x (Nvars+1) full evaluations in one batched launch
  * (C x (Nvars+1) <= 65535), grad = (logL(theta + h e_k) - logL(theta)) / h_applied; plength is not read.
