@@ -221,6 +221,12 @@ int tamcmc_hip_loglike_params_batch(tamcmc_hip_ctx *ctx, int model_id, int B, co
  * (tools/rgb_parity_probe.py, round 3): frequencies <= 3e-13 muHz (1.5e-11 at 2e5 bins with ~170 mixed modes), zeta <= 4e-13 (1.2e-10),
  * rows <= 2e-12 (1.1e-11), logL <= 1e-14.  A mixed mode is as narrow as 0.01 muHz, so a frequency error d nu moves single bins of its
  * profile by ~d nu / Gamma: the per-bin maximum is larger than the row norm (5e-12 typical, 5.5e-10 at the C5 size).
+ * Against the DEFINITION (tests/rgb_reference.py: the same statements at 50 digits, every value with the scale a double evaluation's
+ * rounding is proportional to): every mixed-mode frequency, zeta, h1_h0 and every row field of tamcmc_hip_rgb_mixed_modes and
+ * tamcmc_hip_rgb_batch_tables (STRICT and FAST) lies within 4 x 2^-52 x scale -- ~1e-12 muHz for a frequency near 120 muHz -- and l, flags,
+ * row count and order, nharvey, nnoise, status, i0 and i1 are the definition's.  The point count of the solver's local grid,
+ * long(4 resol / (resol factor)), is an exact integer that a double evaluation rounds to itself or to one less: the definition carries
+ * both results and a root must be one of the two.  Measured on the MI355X: worst ratio 0.6 of the permitted 4.
  *
  * Red-giant models (ids 25, 27): the l=1 mixed modes of ONE parameter vector as the device pre-step computes them for the table
  * (csrc/rgb_prestep.hip) -- what external/ARMM/do_solve.cpp:114-121 prints with the reference's solver:

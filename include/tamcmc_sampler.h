@@ -170,7 +170,8 @@ int tamcmc_sampler_get_gradient(const tamcmc_sampler *s, double *grad, double *g
  * pointer may be NULL.  Host-driven engine: everything.  Device-resident engine: use_drift = 1 only (else TAMCMC_ERR_BAD_ARG),
  * vars_prop and grad_prop; stats_prop and lq come back as NaN (those scalars are not kept). */
 int tamcmc_sampler_get_last_test(const tamcmc_sampler *s, double *vars_prop, double *stats_prop, double *lq, double *grad_prop);
-/* Audit entry of the device-resident random-walk engine (models 3, 11, 12, 13, 14, 23; host-driven engine, Langevin step, red giants,
+/* Audit entry of the device-resident random-walk engine (models 3, 11, 12, 13, 14, 23, and the red giants 25, 27: always scheme 1, rows
+ * per slot = Nfl0 + Nfl2 + Nfl3 + 400, the rows k_rgb_finish left; host-driven engine, Langevin step,
  * Gaussian-envelope ids 0 / 1 -- they have no table --: TAMCMC_ERR_BAD_MODEL): the multiplet tables the last stretch of the last tamcmc_sampler_run left in the likelihood kernel's input
  * block, and the parameter vector each was built from -- both read from the engine's own buffers, nothing is replayed.
  *   shape[4] = scheme, slots, rows per slot, noise stride (always returned; call with every other pointer NULL for the sizes)

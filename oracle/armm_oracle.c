@@ -115,11 +115,11 @@ static void solve_pairs(const double *nu_p, const double *Dnu_loc, long Lp, cons
                         double zone, double resol, double fact, double keep_lo, double keep_hi, orc_eigensols *out) {
     long cap = 1024, n = 0;
     double *all = dalloc(cap);
-    double tmp[64];
+    double tmp[4096];  /* per pair; the reference has no such limit (64 cut a pair's roots short from ~380 mixed modes per vector on) */
     for (long ip = 0; ip < Lp; ip++)
         for (long ig = 0; ig < Lg; ig++) {
             const long k = solver_mm(nu_p[ip], nu_g[ig], Dnu_loc[ip], DPl, q, nu_p[ip] - zone * Dnu_p, nu_p[ip] + zone * Dnu_p, resol, fact, tmp,
-                                     64);
+                                     4096);
             for (long i = 0; i < k; i++)
                 if (tmp[i] >= keep_lo && tmp[i] <= keep_hi) {
                     if (n == cap) { cap *= 2; all = (double *)realloc(all, (size_t)cap * sizeof(double)); }

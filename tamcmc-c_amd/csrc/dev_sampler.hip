@@ -426,7 +426,8 @@ int DevSampler::download_tables(int32_t shape[4], tamcmc_multiplet *rows, int32_
     tamcmc_hip_ctx *c = I.ctx;
     const DevSamplerArgs &a = I.a;
     const FusedArgs &f = I.f;
-    if (I.use_drift || I.rgb || mt::count_multiplets(a.desc.model_id, I.h_plength.data()) < 0) return TAMCMC_ERR_BAD_MODEL;
+    // (ids 25 / 27, random walk: lockstep scheme, the rows k_rgb_finish left in the same block; rows per slot = Nfl0 + Nfl2 + Nfl3 + 400)
+    if (I.use_drift || I.env || (!I.rgb && mt::count_multiplets(a.desc.model_id, I.h_plength.data()) < 0)) return TAMCMC_ERR_BAD_MODEL;
     const bool fused = I.last_scheme == 2;
     const size_t C = (size_t)a.C, NS = (size_t)f.NS, n = fused ? 3 * NS : C, per = (size_t)a.desc.per, stride = (size_t)a.desc.stride, Np = (size_t)a.desc.Np;
     if (shape) { shape[0] = I.last_scheme; shape[1] = I.last_scheme ? (int32_t)n : 0; shape[2] = (int32_t)per; shape[3] = (int32_t)stride; }

@@ -182,7 +182,7 @@ class Sampler:
         return v, st, lq, g
 
     def tables(self):
-        """tamcmc_sampler_get_tables (device engine, random walk): a dict with scheme (0 none yet, 1 lockstep, 2 fused), tables[slot] (that
+        """tamcmc_sampler_get_tables (device engine, random walk; red giants 25 / 27 included, scheme 1): a dict with scheme (0 none yet, 1 lockstep, 2 fused), tables[slot] (that
         slot's rows, MULT_DTYPE), noise [slots x stride], nharvey, nnoise, status, written, logprior [slots], params [slots x Nparams]."""
         from . import MULT_DTYPE
         shape = np.zeros(4, dtype=np.int32)
