@@ -10,9 +10,13 @@
 namespace tamcmc {
 
 template <typename T>
-struct DevBuf {  // grow-only device buffer
+struct DevBuf {  // grow-only device buffer; released with its owner at the latest (the device must be current then)
     T *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
     hipError_t reserve(size_t n) {
         if (n <= cap) return hipSuccess;
         if (p) (void)hipFree(p);
@@ -31,9 +35,13 @@ struct DevBuf {  // grow-only device buffer
 };
 
 template <typename T>
-struct PinBuf {  // grow-only pinned host buffer
+struct PinBuf {  // grow-only pinned host buffer; released with its owner at the latest
     T *p = nullptr;
     size_t cap = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf &) = delete;
+    PinBuf &operator=(const PinBuf &) = delete;
+    ~PinBuf() { release(); }
     hipError_t reserve(size_t n) {
         if (n <= cap) return hipSuccess;
         if (p) (void)hipHostFree(p);

@@ -80,8 +80,8 @@ class DevSampler {
     int download_state(double *vars, double *params, double *logL, double *logPr, double *logPost, double *Pmove,
                        int *moved, long *counters, long *moves_per_chain = nullptr);
     int download_proposal(int m, double *cov, double *mu, double *sigma);
-    int download_gradient(double *grad, double *grad_prior);
-    int download_last_proposal(double *vars_prop, double *grad_prop);  // use_drift: what the last iteration tested  // use_drift: [C x Nv] gradient the engine holds for the chains' positions
+    int download_gradient(double *grad, double *grad_prior);  // use_drift: [C x Nv] gradient the engine holds for the chains' positions
+    int download_last_proposal(double *vars_prop, double *grad_prop);  // use_drift: what the last iteration tested
     // [0] Nvars [1] Nparams [2] adaptation workspace in LDS (1) / global scratch (0) [3] fused step available [4] chain groups
     // [5] iterations run fused [6] iterations run by the lockstep kernels [7] chains [8] fused stretches
     // [9] quick_decide fallbacks taken by the likelihood tiles [10] tile tests decided from a kind-2 record (outside a swap pair)
@@ -98,7 +98,6 @@ class DevSampler {
     // layout of tamcmc_sampler.h), the vector it was built from (params_prop of that iteration's parity), its log-prior and status
     int download_envelope_rows(double *rows, double *params, double *logPr, int32_t *status);
     int run(long it0, long n_iter, const char *learn, double *samples, double *stats);
-    int run_mala(long it0, long n_iter, const char *learn, double *samples, double *stats);  // use_drift = 1 (dev_mala_impl.h)
 };
 
 }  // namespace tamcmc

@@ -43,6 +43,13 @@ struct EnvRow {
     int32_t pad[2];
 };
 
+// EnvRow as the TAMCMC_ENVELOPE_ROW_N = 24 doubles of tamcmc_sampler.h (tamcmc_sampler_get_envelope_rows)
+inline void env_row_as_doubles(const EnvRow &R, double *r) {
+    r[0] = R.amp; r[1] = R.numax; r[2] = R.sig2; r[3] = R.N0;
+    for (int k = 0; k < 2; k++) { r[4 + k] = R.H[k]; r[6 + k] = R.lna[k]; r[8 + k] = R.pw[k]; r[22 + k] = R.hon[k] ? 1.0 : 0.0; }
+    for (int k = 0; k < 3; k++) { r[10 + k] = R.b[k]; r[13 + k] = R.lnb[k]; r[16 + k] = R.c[k]; r[19 + k] = R.a2[k]; }
+}
+
 // EnvRow of one vector: the scalar part of the model functions.  Host: libm's fabs / log / pow; device: the device library's.
 TAMCMC_ENV_HD void env_row(int model_id, const double *p, EnvRow &R) {
     R = EnvRow{};

@@ -643,3 +643,43 @@ def test_move_counts_are_the_moved_flags_the_reference_buffers(pkg, oracle, synt
         assert np.array_equal(h.move_counts(), d.move_counts())
     assert d.state()["swaps"] > 0 and d.move_counts().sum() > 0
     h.close(); d.close()
+
+
+@pytest.mark.parametrize("path", ["lockstep", "one_launch", "two_groups", "langevin"])
+def test_kernel_timing_changes_no_chain_and_counts_what_the_call_launched(pkg, oracle, synth, path):
+    """The context's timing option brackets launches with events (lockstep: sampled likelihood launches and a synchronisation per
+    stretch; fused step: the stretch, or sampled launches of the second chain group; Langevin step: two sampled gradient batches with
+    a synchronisation each) and adds what they stand for to the context's totals.  It must not change a chain -- samples, statistics
+    and final state bit for bit those of a context without timing -- and after one call of 30 quiet iterations (no adaptation, no
+    swap: Nt_learn and dN_mixing beyond the run) the totals are exact.  With C chains in G = 2 chain groups: lockstep kernels
+    30 G likelihood launches; fused step 30 launches, or 60 with one launch per group (no swap, so no joint iteration); Langevin step
+    30 batches of C (Nvars + 1) evaluations; 30 C evaluations otherwise."""
+    scheme, drift, C = {"lockstep": (1, 0, 8), "one_launch": (2, 0, 8), "two_groups": (3, 0, 8), "langevin": (0, 1, 5)}[path]
+    star = _star_with_data(pkg, oracle, synth, nx=2048)
+    n = 30
+    kw = dict(engine="device", nchains=C, lambda_temp=1.4, seed=31, Nt_learn=(10**9, 10**9 + 1), periods_learn=(1,), dN_mixing=10**6,
+              use_drift=drift)
+    out = []
+    for timing in (False, True):
+        c = pkg.HipContext(0, precision=pkg.PRECISION_FAST, timing=timing)
+        c.set_spectrum(star.x, star.y)
+        c.set_option(pkg.OPT_STEP_SCHEME, scheme)
+        s = pkg.Sampler(c, star, **kw)
+        c.reset_kernel_stats()
+        smp, stt = s.run(n, stats=True)
+        out.append((smp, stt, s.state(), s.info(), c.kernel_stats()))
+        s.close(); c.close()
+    (smp0, stt0, st0, _, ks0), (smp1, stt1, st1, info, ks1) = out
+    assert np.array_equal(smp0, smp1) and np.array_equal(stt0, stt1)
+    for k in ("iteration", "swaps", "swap_attempts", "accepted0"):
+        assert st0[k] == st1[k], k
+    for k in ("vars", "logL", "logPrior", "logPost", "Pmove", "sigma"):
+        assert np.array_equal(st0[k], st1[k]), k
+    assert (smp1[:, 0] != smp1[0, 0]).any()
+    print("\n%s: kernel_stats %r (timing off %r), info %r" % (path, ks1, ks0, info))
+    assert info["chain_groups"] == (1 if drift else 2)
+    assert info["iter_fused"] == (0 if scheme < 2 else n)
+    ms, launches, evals = ks1
+    want = {"lockstep": (n * 2, n * C), "one_launch": (n, n * C), "two_groups": (2 * n, n * C), "langevin": (n, n * C * (star.nvars + 1))}[path]
+    assert ms > 0 and (launches, evals) == want, (ks1, want)
+    assert ks0 == (0.0, 0, 0), ks0
