@@ -307,8 +307,16 @@ int tamcmc_hip_fd_gradient_posterior(tamcmc_hip_ctx *ctx, int model_id, int prio
  * base launch leaves), any workgroup geometry; STRICT returns TAMCMC_ERR_BAD_ARG.
  * Tolerance: each G[row][f] / Gn[j] within 1e-11 sum_i |r_i dM_i/df| of a long-double evaluation of the same sum (the FAST tolerance,
  * applied to this sum); the gradient within 3 R of the central difference with frozen windows, R that reference's own uncertainty
- * |g(h) - g(h/2)| (tests/test_gpu_adjoint.py).  Every sum has one fixed order: two calls give the same bits, and a chain's gradient does
- * not depend on the number of chains or on its place in the batch.
+ * |g(h) - g(h/2)| (tests/test_gpu_adjoint.py).  The contraction itself is exact to rounding: with dT the differences of the batch's own
+ * tables (tamcmc_hip_fd_batch_tables) and G, Gn the bits of the audit entry below, the dS of a component lies within
+ *   D 2^-53 sum |G . dT| + 3 x 2^-53 |dS|,   D = 2 + 17 + ceil(rows / 64) + 6 + nnoise,
+ * of the exact sum G . dT -- D the roundings one term can pass (difference, product, the row's running sum, the lane's row loop, the
+ * wave's tree, the noise tail), the 3 those of the division by T and by h_applied (tests/test_gpu_adjoint_exact.py, which also holds G
+ * and Gn to the 1e-11 above against a 50-digit evaluation that differentiates in field space).  Every sum has one fixed order: two calls
+ * give the same bits, and a chain's gradient does not depend on the number of chains or on its place in the batch.
+ * At a base point with asym = 0 the rows carry no asym and fc entries (the model takes its A = 1 branch there), so on this route the
+ * likelihood's share of the asymmetry parameter's component is exactly 0, although dM/dasym = 2 u sum_m hv_m / q does not vanish at
+ * asym = 0: the finite-difference route, which evaluates the model at asym = hstep, reports it.  The two routes differ in this component.
  *
  * The audit entry: G [C x *nrows x 17] and Gn [C x max(plength[8], 1)] of the C parameter vectors, for the UN-tempered S (Tcoefs and p are
  * accepted for symmetry and not read: logL = -p S / T).  *nrows = rows per table.  Runs under the adjoint route whatever the option says;
