@@ -150,6 +150,11 @@ extern "C" {
                                         existing sampler.  The Langevin step of these ids stays on the host-driven engine (engine = 1 with
                                         use_drift = 1: TAMCMC_ERR_BAD_MODEL whatever this option says); see tamcmc_sampler.h.  Any other
                                         value: TAMCMC_ERR_BAD_ARG */
+#define TAMCMC_OPT_FACTOR_REFRESH 14 /* value R: 0 (default) or 1 -- every adapting iteration factors (Sigma + eps2 I) sigma from scratch; 2 ... 65536 --
+                                        the factor follows the Robbins-Monro step by a rank-one update in O(Nvars^2), with a scheduled full
+                                        factorisation every R-th adapting iteration (both engines, both samplers, every model; the law and
+                                        the rule: tamcmc_sampler.h).  Read when the sampler is created: changing it afterwards does not
+                                        affect an existing sampler.  Any other value: TAMCMC_ERR_BAD_ARG */
 #define TAMCMC_FISHER_SLAB 2048     /* bins per workgroup (and per partial matrix) of the Gram kernel of tamcmc_hip_fisher / _weighted_gram */
 
 /* One (n,l) multiplet: <=7 Lorentzian m-components on its truncation window.

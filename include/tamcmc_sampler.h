@@ -134,7 +134,13 @@ int64_t tamcmc_sampler_nvars(const tamcmc_sampler *s);
                                           (the iteration of a swap pair that straddles the groups, and the next) */
 #define TAMCMC_INFO_QUICK_MISMATCH 14  /* tests that the decision shortcut decided OTHERWISE than the exact evaluation: every commit
                                           workgroup asks both.  0 -- anything else is a defect of the shortcut */
-#define TAMCMC_SAMPLER_INFO_N 15
+#define TAMCMC_INFO_FACTOR_UPDATES 15   /* rank-one steps of the proposal factor taken since creation, summed over the chains
+                                          (TAMCMC_OPT_FACTOR_REFRESH >= 2; always 0 otherwise) */
+#define TAMCMC_INFO_FACTOR_REFRESHES 16 /* full factorisations of adapting iterations that were SCHEDULED, summed over the chains: every
+                                          adapting iteration with R < 2, every R-th otherwise */
+#define TAMCMC_INFO_FACTOR_FORCED 17    /* full factorisations in an adapting iteration scheduled as a rank-one step, forced by the rule
+                                          below (gain, rescaled covariance, a factor not marked valid), summed over the chains */
+#define TAMCMC_SAMPLER_INFO_N 18
 int tamcmc_sampler_get_info(const tamcmc_sampler *s, int64_t *info, int32_t n);
 
 /* Advances all chains by n_iter iterations.  Optional outputs, one record per iteration after the swap step
@@ -209,6 +215,31 @@ int tamcmc_sampler_get_move_counts(const tamcmc_sampler *s, int64_t *moves);
 /* proposal law of chain m: mu [Nvars], covarmat [Nvars x Nvars] (restore file content, outputs.cpp:863-1025) */
 int tamcmc_sampler_get_proposal(const tamcmc_sampler *s, int32_t m, double *mu, double *covarmat);
 int tamcmc_sampler_set_proposal(tamcmc_sampler *s, int32_t m, const double *mu, const double *covarmat, double sigma);
+/* The factor IN FORCE for chain m -- what the next proposal is drawn with (and, with use_drift = 1, what its two densities are taken with):
+ * L [Nvars x Nvars], lower triangle, row-major, zeros above.  Both engines, any TAMCMC_OPT_FACTOR_REFRESH.  An audit entry like
+ * tamcmc_sampler_draws.
+ *
+ * TAMCMC_OPT_FACTOR_REFRESH = R >= 2 (opt-in, read at creation): the proposal law of the learning phase.  mu, Sigma and sigma are
+ * updated exactly as with R = 0 -- the same bits, clips included.  With g = c0 / (1 + i), sigma / sigma' the scale before / after its
+ * update and d = x - mu', an adapting iteration is a RANK-ONE STEP iff it is not a scheduled full step (the k-th adapting iteration of
+ * the sampler, k counted from 0, is full when k % R == 0), 0 < g < 1, the covariance was not rescaled to norm A1, and the chain's factor
+ * is marked valid.  It replaces L in place by the Cholesky factor of
+ *     beta^2 L L^T + w w^T,     beta^2 = (1 - g) sigma' / sigma,     w = sqrt(g sigma') d,
+ * in O(Nvars^2).  Otherwise the step is FULL: L = chol((Sigma + eps2 I) sigma) as with R = 0, and the factor is marked valid iff that
+ * matrix was positive definite (if not, the old factor stays in force, as with R = 0, and the next adapting iteration is full again).
+ * A rank-one step whose pivots are not all finite and positive leaves the old factor in force and clears the mark.
+ * The law: in exact arithmetic the factor in force satisfies  L L^T = sigma (Sigma + eps2 rho I),  rho = prod (1 - g_j) over the rank-one
+ * steps since the last full step -- Sigma is exactly the default's, the regulariser decays until the next refresh.  It is a valid
+ * adaptive law: the random walk is symmetric for any L, the Langevin densities are taken with the L that draws, and the drift stays the
+ * deterministic function (1/2) sigma (Sigma + eps2 I) grad it is with R = 0.
+ * Laws from outside: tamcmc_sampler_set_proposal (and through it tamcmc_sampler_read_restore with restore_proposal and
+ * tamcmc_sampler_seed_proposal_fisher) clears the mark: the next adapting iteration is a full step.  A restored run therefore starts with a
+ * full step and does NOT continue a rank-one run bit for bit (the restore file holds Sigma, not the factor with its decayed regulariser). */
+int tamcmc_sampler_get_factor(const tamcmc_sampler *s, int32_t m, double *L);
+/* The rank-one step alone, on the host (no device): L [Nvars x Nvars] lower triangular, row-major, replaced in place by the Cholesky
+ * factor of beta2 L L^T + w w^T (zeros above the diagonal); the arithmetic of both engines (csrc/factor_update.h).  TAMCMC_ERR_BAD_ARG
+ * (L untouched) for a non-finite input, beta2 <= 0 or a pivot that is not finite and positive. */
+int tamcmc_factor_rank_one_update(int32_t Nvars, double *L /* lower, row-major, in place */, const double *w, double beta2);
 /* Seeds every chain's proposal covariance from the curvature of the likelihood at the chain's CURRENT position (tamcmc_hip_fisher, one call
  * per chain with the steps h_k = hstep_rel max(|theta_k|, 1e-2); hstep_rel = 0 means 1e-6): with F_m the expected information at the chain's
  * temperature T_m and E = diag(init_errors),

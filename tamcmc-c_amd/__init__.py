@@ -30,6 +30,7 @@ OPT_PRECISION, OPT_TIMING, OPT_BINS_PER_THREAD, OPT_WORKGROUP, OPT_FD_WINDOWED, 
 OPT_GRADIENT, GRADIENT_FD, GRADIENT_ADJOINT = 9, 0, 1  # gradient batches: finite differences (default) / table-space adjoint, frozen windows
 OPT_RGB_DEVICE_LANGEVIN = 11  # 1: Sampler(use_drift=1, engine="device") is built for the red-giant ids 25 / 27 (default 0: ERR_BAD_MODEL); read at creation
 OPT_ENVELOPE_DEVICE_ENGINE = 13  # 1: Sampler(engine="device", use_drift=0) is built for the Gaussian-envelope ids 0 / 1 (default 0: ERR_BAD_MODEL); read at creation
+OPT_FACTOR_REFRESH = 14  # R: 0 / 1 a full factorisation in every adapting iteration (default); 2 ... 65536 rank-one steps of the proposal factor, a full one every R-th; read at creation
 OPT_RGB_ADJOINT = 12  # 1: under GRADIENT_ADJOINT the red-giant ids 25 / 27 take the hybrid adjoint batch (default 0: ERR_BAD_MODEL); read at every call
 OPT_FISHER_WORKSPACE_MB = 10  # MiB of model rows HipContext.fisher keeps on the device per pass (default 2048)
 FISHER_SLAB = 2048  # bins per workgroup of the Gram kernel (TAMCMC_FISHER_SLAB)

@@ -83,6 +83,7 @@ struct tamcmc_hip_ctx {
     int rgb_device_langevin = 0;  // 1: the device-resident engine builds its Langevin sampler for the red-giant ids (read at sampler creation)
     int rgb_adjoint = 0;  // 1: under TAMCMC_GRADIENT_ADJOINT the red-giant ids take the hybrid batch (fd_batch.hip; read at every call)
     int envelope_device_engine = 0;  // 1: the device-resident engine is built for the Gaussian-envelope ids 0 / 1 (read at sampler creation)
+    int factor_refresh = 0;  // R of TAMCMC_OPT_FACTOR_REFRESH: < 2 a full factorisation per adapting iteration, else rank-one steps (read at sampler creation)
     // resident spectrum
     int64_t Nx = 0;
     std::vector<double> hx;  // host copy of x (table builders need x[0], x[Nx-1], step)

@@ -134,12 +134,119 @@ __device__ __forceinline__ double wave_partial_sum(const double *base, int ntile
     return wave_sum_in_order(s1, s2);
 }
 
+// value of x in lane `lane` (wave-uniform, a run-time value) for every lane
+__device__ __forceinline__ double lane_value_at(double x, int lane) {
+    const long long b = __double_as_longlong(x);
+    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), lane), hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
+    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+
+// The rank-one step of chain m's factor (factor_update.h: solve, then scale): LT <- the transposed Cholesky factor of
+// beta2 L L^T + w w^T, w = wscale x d.  false: refused (a pivot or a coefficient not finite and positive), LT untouched.
+//   IN_LDS   A [Nv x Nv] receives LT as it is stored (row k = column k of L: the substitution reads a column as one run, the sweep's
+//            lanes read a row of L across a run); va, vb [Nv] are LDS vectors of the caller.  Up to 128 variables the substitution runs
+//            in the registers of ONE wave (lane i: rows i and i + 64; p_k handed on by a lane read: no barrier and no memory round trip
+//            per column, reciprocal pivots taken beforehand, all at a time) -- the pattern of k_mala_test's solves.
+//   else     A IS LT (device memory, updated in place: the sweep's lane reads an element, then writes it); va, vb in the scratch.
+// The sweep: lane i owns row i of L, columns i down to 0, with the suffix sum of L_ij p_j; rows are independent, no barrier inside, and
+// every element is written straight to LT (lanes along a run).  d [Nv]: the deviation on entry, p = L^-1 w on exit.
+// Called by all TB threads after a barrier; s_scal[2] is its refusal flag.  Ends with a barrier.
+template <class WP, bool IN_LDS>
+__device__ bool factor_rank_one_as(const DevSamplerArgs &a, int m, double beta2, double wscale, WP A, WP d, WP va, WP vb, double *s_scal) {
+    const int tid = threadIdx.x, Nv = a.Nv;
+    double *LT = a.LT + (size_t)m * Nv * Nv;
+    const double beta = sqrt(beta2);
+    const bool one_wave = IN_LDS && Nv <= 128;
+    if constexpr (!IN_LDS) A = (WP)LT;
+    if (tid == 0) s_scal[2] = (beta2 > 0.0 && beta2 <= 1.7976931348623157e308) ? 0.0 : 1.0;
+    if constexpr (IN_LDS) {
+        for (int e = tid; e < Nv * Nv; e += TB) A[e] = LT[e];
+        if (one_wave)
+            for (int k = tid; k < Nv; k += TB) va[k] = 1.0 / LT[(size_t)k * Nv + k];
+    }
+    for (int k = tid; k < Nv; k += TB) d[k] = d[k] * wscale;
+    __syncthreads();
+    if (one_wave) {
+        if (tid < 64) {
+            const int lane = tid, hi = lane + 64;
+            double f0 = lane < Nv ? d[lane] : 0.0, f1 = hi < Nv ? d[hi] : 0.0;
+            double alpha = beta2, ap0 = beta2, al0 = beta2, ap1 = beta2, al1 = beta2;
+#pragma clang loop unroll(disable)
+            for (int k = 0; k < Nv; k++) {
+                const size_t row = (size_t)k * Nv;
+                const double id = va[k];
+                const double l0 = (lane > k && lane < Nv) ? A[row + lane] : 0.0, l1 = (hi > k && hi < Nv) ? A[row + hi] : 0.0;
+                const double pk = lane_value_at(k < 64 ? f0 : f1, k & 63) * id;
+                const double an = alpha + pk * pk;
+                if (lane == (k & 63)) {
+                    if (k < 64) { f0 = pk; ap0 = alpha; al0 = an; }
+                    else { f1 = pk; ap1 = alpha; al1 = an; }
+                }
+                alpha = an;
+                f0 = f0 - l0 * pk;  // (rows above the column: l = 0, the value stays)
+                f1 = f1 - l1 * pk;
+            }
+            bool ok = true;
+            if (lane < Nv) {
+                double ca, cb;
+                ok = factor_column(beta, ap0, al0, f0, &ca, &cb) && ok;
+                d[lane] = f0; va[lane] = ca; vb[lane] = cb;
+            }
+            if (hi < Nv) {
+                double ca, cb;
+                ok = factor_column(beta, ap1, al1, f1, &ca, &cb) && ok;
+                d[hi] = f1; va[hi] = ca; vb[hi] = cb;
+            }
+            if (!ok) s_scal[2] = 1.0;
+        }
+        __syncthreads();
+    } else {
+        // wide proposals: a column per step -- p_k and its coefficients by one lane, then every row below loses L_ik p_k
+        double alpha = beta2;  // (lane 0's)
+#pragma clang loop unroll(disable)
+        for (int k = 0; k < Nv; k++) {
+            if (tid == 0) {
+                const double pk = d[k] * (1.0 / A[(size_t)k * Nv + k]);
+                const double an = alpha + pk * pk;
+                double ca, cb;
+                if (!factor_column(beta, alpha, an, pk, &ca, &cb)) s_scal[2] = 1.0;
+                alpha = an;
+                d[k] = pk; va[k] = ca; vb[k] = cb;
+            }
+            __syncthreads();
+            const double pk = d[k];
+            for (int i = k + 1 + tid; i < Nv; i += TB) d[i] = d[i] - A[(size_t)k * Nv + i] * pk;
+            __syncthreads();
+        }
+    }
+    if (s_scal[2] != 0.0) {  // every lane leaves together, LT is not touched
+        __syncthreads();
+        return false;
+    }
+#pragma clang loop unroll(disable)
+    for (int i = tid; i < Nv; i += TB) {
+        double s = 0.0;
+#pragma unroll 4
+        for (int k = i; k >= 0; k--) {
+            const size_t e = (size_t)k * Nv + i;
+            const double v = A[e];
+            LT[e] = v * va[k] + s * vb[k];
+            s = s + v * d[k];
+        }
+    }
+    __syncthreads();
+    return true;
+}
+
 // Robbins-Monro adaptation of chain m's proposal law (MALA.cpp:296-319) and Cholesky of (Sigma+eps2 I) sigma
 // (MALA.cpp:348-350); `vars` = the chain's position after the MH test, `Pm` = its move probability.
 // WP: pointer type of the work matrix A and the vector d in their address space (LDS when the matrix fits there: ds_read/ds_write
 // instead of flat accesses, whose latency is several times higher; device memory otherwise); PANELS: the blocked factorisation.
+// fmode: what the factor does (step_schedule.h::factor_step_mode): 1 = today's full factorisation, 2 = a rank-one step of the factor
+// in force where factor_update.h's rule allows it (va, vb: its two coefficient vectors [Nv], in A's address space); s_scal [4].
 template <class WP, bool PANELS>
-__device__ void adapt_chain_as(const DevSamplerArgs &a, int m, long itp, const double *vars, double Pm, WP A, WP d, double *s_red, double *s_scal) {
+__device__ void adapt_chain_as(const DevSamplerArgs &a, int m, long itp, const double *vars, double Pm, WP A, WP d, double *s_red, double *s_scal,
+                               int fmode, WP va, WP vb) {
     const int tid = threadIdx.x, Nv = a.Nv;
     const double g = a.c0 / (1. + (double)itp);
     double *mu = a.mu + (size_t)m * Nv;
@@ -214,14 +321,26 @@ __device__ void adapt_chain_as(const DevSamplerArgs &a, int m, long itp, const d
     if (tid == 0) {
         const double nrm = sqrt(n2);
         s_scal[0] = (nrm <= a.A1) ? 1.0 : a.A1 / nrm;  // p2_fct
-        double v1 = a.sigma[m] + g * (Pm - a.target_acceptance);
+        const double sig_old = a.sigma[m];
+        double v1 = sig_old + g * (Pm - a.target_acceptance);
         if (v1 < a.epsilon1) v1 = a.epsilon1;  // p1_fct
         if (v1 > a.A1) v1 = a.A1;
         a.sigma[m] = v1;
         s_scal[1] = v1;
+        const bool r1 = factor_takes_rank_one(fmode, g, s_scal[0] != 1.0, a.fvalid[m] != 0);
+        s_scal[3] = r1 ? factor_beta2(g, sig_old, v1) : -1.0;
     }
     __syncthreads();
     const double sc = s_scal[0], sig = s_scal[1];
+    if (s_scal[3] >= 0.0) {  // (workgroup-uniform) the rank-one step: Sigma is final (not rescaled), d still holds x - mu'
+        const double beta2 = s_scal[3];
+        const bool done = factor_rank_one_as<WP, PANELS>(a, m, beta2, factor_w_scale(g, sig), A, d, va, vb, s_scal);
+        if (tid == 0) {
+            if (!done) a.fvalid[m] = 0;  // the old factor stays in force; the next adapting iteration is full
+            atomicAdd((unsigned long long *)&a.fcount[done ? 0 : 3], 1ull);
+        }
+        return;
+    }
     for (int i = gi; i < Nv; i += 16)
         for (int j = gk; j < Nv; j += 16) {
             const size_t e = (size_t)i * Nv + j;
@@ -418,14 +537,20 @@ __device__ void adapt_chain_as(const DevSamplerArgs &a, int m, long itp, const d
     if (pd)
         for (int k = gi; k < Nv; k += 16)
             for (int i = gk; i < Nv; i += 16) LT[(size_t)k * Nv + i] = (k <= i) ? A[(size_t)i * Nv + k] : 0.0;
+    if (tid == 0) {  // marked valid iff the matrix was positive definite; a full step in a rank-one slot of the schedule was forced
+        a.fvalid[m] = pd ? 1 : 0;
+        atomicAdd((unsigned long long *)&a.fcount[fmode == 2 ? 2 : 1], 1ull);
+    }
     __syncthreads();
 }
+// A, d: the work matrix [Nv x Nv] and vector [Nv] -- in LDS when a.chol_in_lds (then va, vb are two more LDS vectors [Nv] of the caller),
+// else the chain's slice of the scratch, [Nv^2 + 3 Nv] (va, vb are its tail).
 __device__ __forceinline__ void adapt_chain(const DevSamplerArgs &a, int m, long itp, const double *vars, double Pm, double *A, double *d, double *s_red,
-                            double *s_scal) {
+                            double *s_scal, int fmode, double *va, double *vb) {
     typedef double __attribute__((address_space(3))) *lds_dp_t;
     typedef double __attribute__((address_space(1))) *dev_dp_t;
-    if (a.chol_in_lds) adapt_chain_as<lds_dp_t, true>(a, m, itp, vars, Pm, (lds_dp_t)A, (lds_dp_t)d, s_red, s_scal);
-    else adapt_chain_as<dev_dp_t, false>(a, m, itp, vars, Pm, (dev_dp_t)A, (dev_dp_t)d, s_red, s_scal);
+    if (a.chol_in_lds) adapt_chain_as<lds_dp_t, true>(a, m, itp, vars, Pm, (lds_dp_t)A, (lds_dp_t)d, s_red, s_scal, fmode, (lds_dp_t)va, (lds_dp_t)vb);
+    else adapt_chain_as<dev_dp_t, false>(a, m, itp, vars, Pm, (dev_dp_t)A, (dev_dp_t)d, s_red, s_scal, fmode, (dev_dp_t)(d + a.Nv), (dev_dp_t)(d + 2 * a.Nv));
 }
 
 // z ~ N(0, I) of (chain, iteration) into LDS (ends without a barrier) and row i of L z (MALA.cpp:348-355)
@@ -695,7 +820,7 @@ __global__ void __launch_bounds__(TB) k_iterate(const DevSamplerArgs a, const lo
     double *s_red = U.red;
     double *s_A = (double *)(((uintptr_t)(s_z + Nv + 1) + unpack_lds_bytes() + 15) & ~(uintptr_t)15);  // [Nv*Nv + Nv] when learning in LDS
     __shared__ AcceptOut s_own, s_partner;
-    __shared__ double s_scal[2];
+    __shared__ double s_scal[4];
 
     const int m = blockIdx.x + c_off;  // c_off: first chain of this launch's chain group
     const int Q = P ^ 1;
@@ -703,8 +828,11 @@ __global__ void __launch_bounds__(TB) k_iterate(const DevSamplerArgs a, const lo
     // ------------------------------------------------------------------ (0) settle the pending iteration
     settle_chain(a, m, it, P, pending, rec, learn_pending, true, s_vars, s_params, s_z, s_red, &s_own, &s_partner);
     if (pending && learn_pending) {
-        double *Aw = a.chol_in_lds ? s_A : scratch + (size_t)m * ((size_t)Nv * Nv + Nv);
-        adapt_chain(a, m, it - 1, s_z, s_own.r, Aw, Aw + (size_t)Nv * Nv, s_red, s_scal);
+        double *Aw = a.chol_in_lds ? s_A : scratch + (size_t)m * ((size_t)Nv * Nv + 3 * Nv);
+        // (the rank-one step's vectors: s_z is free once the deviation is formed; the unpack's LDS behind its reduction slots is idle until
+        // the proposal -- (40 + 224) doubles at least, and a work matrix in LDS has Nv <= 138)
+        static_assert(sizeof(mt::PolyTab) >= 160 * sizeof(double), "room for a coefficient vector of a work matrix that fits in LDS");
+        adapt_chain(a, m, it - 1, s_z, s_own.r, Aw, Aw + (size_t)Nv * Nv, s_red, s_scal, learn_pending, s_z, U.w);
     }
     if (!PROPOSE) return;
     __syncthreads();

@@ -108,7 +108,7 @@ __global__ void __launch_bounds__(TB) k_mala_test(const DevSamplerArgs a, const 
     double *sr = sf + Nv;               // [Nv] reverse solve:  L w = (x - x') - drift(x')
     double *s_red = sr + Nv;            // [8]
     double *s_A = (double *)(((uintptr_t)(s_red + 8) + 15) & ~(uintptr_t)15);  // adaptation workspace when it fits in LDS
-    __shared__ double s_scal[2];
+    __shared__ double s_scal[4];
     __shared__ AcceptOut s_o;
     const double *prop_p = a.params_prop + (size_t)m * Np, *prop_v = a.vars_prop + (size_t)m * Nv;
     const double *cur_v = a.vars_cur + ((size_t)P * C + m) * Nv;
@@ -202,8 +202,8 @@ __global__ void __launch_bounds__(TB) k_mala_test(const DevSamplerArgs a, const 
     __syncthreads();
     if (learn) {  // MALA.cpp:656-667: the chain's own position after the test, before any swap
         const double *ov = s_o.acc ? prop_v : cur_v;
-        double *Aw = a.chol_in_lds ? s_A : scratch + (size_t)m * ((size_t)Nv * Nv + Nv);
-        adapt_chain(a, m, it, ov, s_o.r, Aw, Aw + (size_t)Nv * Nv, s_red, s_scal);
+        double *Aw = a.chol_in_lds ? s_A : scratch + (size_t)m * ((size_t)Nv * Nv + 3 * Nv);
+        adapt_chain(a, m, it, ov, s_o.r, Aw, Aw + (size_t)Nv * Nv, s_red, s_scal, learn, sf, sr);  // (the two solves' vectors are free)
     }
 }
 

@@ -35,6 +35,8 @@ struct DevSamplerArgs {
     long *counters;       // [0] iteration, [1] accepted moves of chain 0, [2] swap attempts, [3] swaps accepted, [8 + m] recorded moves of chain m
     // proposal law
     double *LT, *cov, *mu, *sigma;   // LT = transposed Cholesky factor of (cov+eps2)*sigma
+    int *fvalid;          // [C] the chain's factor is marked valid: a condition of the rank-one step (factor_update.h)
+    long *fcount;         // [4] since creation, over all chains: rank-one steps, scheduled full steps, forced full steps, rank-one steps refused
     double *lz;           // [2][C][Nv] L z of the NEXT iteration, computed ahead by spare workgroups while L is frozen
     double *grad_cur, *gradP_cur;  // Langevin step: [2][C][Nv] gradient of the tempered log-posterior at the chains' positions, and the prior's share
     // likelihood-kernel input block written by k_propose_unpack
@@ -60,6 +62,7 @@ struct DevSamplerInit {
     double c0, epsilon1, epsi2, A1, target_acceptance;
     int chain_groups = 0;  // 0 = default (2 from 8 chains on): stream groups of the lockstep scheme
     int swap_rule = 0;     // tamcmc_sampler_config.swap_rule
+    int factor_refresh = 0;  // R of TAMCMC_OPT_FACTOR_REFRESH as the context held it at creation
     int use_drift = 0;     // 1: Langevin step (dev_mala_impl.h)
     double delta = 0, fd_step_rel = 1e-7;  // drift truncation (0 = none), relative forward-difference step
 };
@@ -80,6 +83,7 @@ class DevSampler {
     int download_state(double *vars, double *params, double *logL, double *logPr, double *logPost, double *Pmove,
                        int *moved, long *counters, long *moves_per_chain = nullptr);
     int download_proposal(int m, double *cov, double *mu, double *sigma);
+    int download_factor(int m, double *L_rowmajor);  // the factor in force for chain m, lower triangular (tamcmc_sampler_get_factor)
     int download_gradient(double *grad, double *grad_prior);  // use_drift: [C x Nv] gradient the engine holds for the chains' positions
     int download_last_proposal(double *vars_prop, double *grad_prop);  // use_drift: what the last iteration tested
     // [0] Nvars [1] Nparams [2] adaptation workspace in LDS (1) / global scratch (0) [3] fused step available [4] chain groups
@@ -87,7 +91,8 @@ class DevSampler {
     // [9] quick_decide fallbacks taken by the likelihood tiles [10] tile tests decided from a kind-2 record (outside a swap pair)
     // [11] of [5] with two chain groups: iterations run as one joint launch [12] ... run in a window (step_schedule.h: StepPlanner)
     // [13] tests that quick_decide decided otherwise than the exact decide() (counted by the commit workgroups: 0, or a bug)
-    void info(long out[14]) const;
+    // [14] rank-one steps of the factor [15] scheduled full factorisations [16] forced ones (all over the chains) [17] rank-one steps refused
+    void info(long out[18]) const;
     // Audit (tamcmc_sampler_get_tables): the tables the last stretch of the last run() left in the likelihood kernel's input block and the
     // parameter vector each was built from, read from the engine's own buffers.  shape = {scheme, slots, rows per slot, noise stride}.
     // scheme 1 (lockstep): slot m = chain m's proposal of the last iteration, vector = params_prop of that iteration's parity;

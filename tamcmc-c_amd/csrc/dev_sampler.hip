@@ -73,6 +73,7 @@
 #include "mode_tables.h"
 #include "rng.h"
 #include "step_schedule.h"
+#include "factor_update.h"
 
 namespace tamcmc {
 
@@ -148,6 +149,7 @@ int DevSampler::Impl::validate(const DevSamplerInit &in) {
     a.desc.per = (rgb || env.on) ? 0 : mt::count_multiplets(in.model_id, in.plength);  // (ids 0 / 1: no table)
     h_plength.assign(in.plength, in.plength + 11);
     prior_class = in.prior_class; model_id = in.model_id;
+    factor_refresh = in.factor_refresh;
     lan.use_drift = in.use_drift != 0; lan.delta = in.delta; lan.fd_step_rel = in.fd_step_rel > 0 ? in.fd_step_rel : 1e-7;
     lan.h_priors.assign(in.priors, in.priors + 4 * (size_t)in.Np); lan.h_extra.assign(in.extra_priors, in.extra_priors + 10);
     lan.h_idx.assign(in.index_to_relax, in.index_to_relax + in.Nv); lan.h_sw.assign(in.priors_switch, in.priors_switch + in.Np);
@@ -212,6 +214,9 @@ int DevSampler::Impl::create_chain_state(const DevSamplerInit &in) {
         DCHK(mem.dalloc(&a.env_rows, C));
         DCHK(hipMemsetAsync(a.env_rows, 0, C * sizeof(EnvRow), st));
     }
+    DCHK(mem.dalloc(&a.fvalid, C)); DCHK(mem.dalloc(&a.fcount, 4));
+    DCHK(hipMemsetAsync(a.fvalid, 0, C * sizeof(int), st));
+    DCHK(hipMemsetAsync(a.fcount, 0, 4 * sizeof(long), st));
     DCHK(hipMemsetAsync(a.counters, 0, (8 + C + 64) * sizeof(long), st));
     DCHK(hipMemsetAsync(a.moved, 0, C * sizeof(int), st));
     DCHK(hipMemsetAsync(a.Pmove, 0, C * sizeof(double), st));
@@ -220,7 +225,7 @@ int DevSampler::Impl::create_chain_state(const DevSamplerInit &in) {
     lds_base = (Np + 2 * Nv + 1) * sizeof(double) + unpack_lds_bytes() + 32;
     lds_adapt = (Nv * Nv + Nv) * sizeof(double);
     a.chol_in_lds = (lds_base + lds_adapt <= 150 * 1024) ? 1 : 0;  // (k_iterate also has ~6 KB of static LDS)
-    if (!a.chol_in_lds) { DCHK(mem.dalloc(&adapt_scratch, C * (Nv * Nv + Nv))); lds_adapt = 0; }
+    if (!a.chol_in_lds) { DCHK(mem.dalloc(&adapt_scratch, C * (Nv * Nv + 3 * Nv))); lds_adapt = 0; }
     if (lds_base + lds_adapt > 64 * 1024) {
         DCHK(hipFuncSetAttribute((const void *)k_iterate<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_base + lds_adapt)));
         DCHK(hipFuncSetAttribute((const void *)k_iterate<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_base + lds_adapt)));
@@ -402,10 +407,13 @@ int DevSampler::download_envelope_rows(double *rows, double *params, double *log
     return TAMCMC_OK;
 }
 
-void DevSampler::info(long out[14]) const {
+void DevSampler::info(long out[18]) const {
     const Impl &I = *impl;
     unsigned long long qc[3] = {0, 0, 0};  // (every entry point returns with the sampler's streams idle)
+    long fc[4] = {0, 0, 0, 0};
     if (I.fu.f.qcount && hipSetDevice(I.ctx->device) == hipSuccess) (void)hipMemcpy(qc, I.fu.f.qcount, sizeof qc, hipMemcpyDeviceToHost);
+    if (I.a.fcount && hipSetDevice(I.ctx->device) == hipSuccess) (void)hipMemcpy(fc, I.a.fcount, sizeof fc, hipMemcpyDeviceToHost);
+    out[14] = fc[0]; out[15] = fc[1]; out[16] = fc[2]; out[17] = fc[3];
     out[8] = I.n.n_stretch; out[9] = (long)qc[0]; out[10] = (long)qc[1]; out[13] = (long)qc[2];
     out[0] = I.a.Nv; out[1] = I.a.desc.Np;
     out[2] = I.lan.use_drift ? I.lan.chol_lds : I.a.chol_in_lds;
@@ -468,7 +476,20 @@ int DevSampler::upload_proposal(int m, const double *L_rowmajor, const double *c
     DCHK(up(a.cov + (size_t)m * Nv * Nv, cov, Nv * Nv, st));
     DCHK(up(a.mu + (size_t)m * Nv, mu, Nv, st));
     DCHK(up(a.sigma + m, &sigma, 1, st));
+    DCHK(hipMemsetAsync(a.fvalid + m, 0, sizeof(int), st));  // a law from outside: the next adapting iteration is a full step
     DCHK(hipStreamSynchronize(st));
+    return TAMCMC_OK;
+}
+
+int DevSampler::download_factor(int m, double *L_rowmajor) {
+    Impl &I = *impl;
+    tamcmc_hip_ctx *c = I.ctx;
+    if (int rc = I.ready_to_read()) return rc;
+    const size_t Nv = (size_t)I.a.Nv;
+    std::vector<double> LT(Nv * Nv);
+    DCHK(hipMemcpy(LT.data(), I.a.LT + (size_t)m * Nv * Nv, Nv * Nv * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < Nv; i++)
+        for (size_t k = 0; k < Nv; k++) L_rowmajor[i * Nv + k] = (k <= i) ? LT[k * Nv + i] : 0.0;
     return TAMCMC_OK;
 }
 

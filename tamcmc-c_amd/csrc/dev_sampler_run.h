@@ -344,7 +344,8 @@ struct DevSampler::Impl::RunCall {
         int have_pre = 0;
         for (long i = ia; i <= ib; i++) {
             const long it = it0 + i;
-            const int learn_p = (L.pending && learn && learn[i - 1]) ? 1 : 0;
+            // (0: no adaptation; else what the factor does in this adapting iteration, by the sampler's count of them: step_schedule.h)
+            const int learn_p = (L.pending && learn && learn[i - 1]) ? factor_step_mode(I.factor_refresh, I.n_adapt++) : 0;
             // L z of iteration it+1 can be computed by spare workgroups of THIS launch when no adaptation rewrites L in this
             // launch (learn_p) nor in the next one before its proposal (learn[i])
             const int make_pre = (i + 1 < ib && !learn_p && !(learn && learn[i])) ? 1 : 0;
@@ -633,7 +634,7 @@ struct DevSampler::Impl::RunCall {
         args.chol_in_lds = chol_lds ? 1 : 0;
         V.chol_lds = args.chol_in_lds;
         I.n.it_lockstep += n_iter;
-        if (!chol_lds && !I.adapt_scratch) DCHK(I.mem.dalloc(&I.adapt_scratch, C * (Nv * Nv + Nv)));
+        if (!chol_lds && !I.adapt_scratch) DCHK(I.mem.dalloc(&I.adapt_scratch, C * (Nv * Nv + 3 * Nv)));
         if (lds_test0 + lds_adapt > 64 * 1024 && chol_lds)
             DCHK(hipFuncSetAttribute((const void *)k_mala_test, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_test0 + lds_adapt)));
         return TAMCMC_OK;
@@ -662,7 +663,7 @@ struct DevSampler::Impl::RunCall {
             if (i == n_iter) break;
             hipEvent_t *pair = T.batch_pair(i, n_iter);
             if (int rc = batch(a.params_prop, pair)) return rc;
-            const int learn_i = (learn && learn[i]) ? 1 : 0;
+            const int learn_i = (learn && learn[i]) ? factor_step_mode(I.factor_refresh, I.n_adapt++) : 0;
             hipLaunchKernelGGL(k_mala_test, dim3(a.C), dim3(TB), lds_test, st, args, M, it, P, learn_i, I.adapt_scratch);
             if (pair) {
                 DCHK(hipStreamSynchronize(st));

@@ -64,7 +64,9 @@ struct DevSampler::Impl {
     bool rgb = false;  // ids 25 / 27: k_iterate leaves the table to the pre-step kernels (rgb_device_stage), lockstep scheme; Langevin step: the gradient batch builds the tables
     int rgb_bmax = 0;  // chains per workspace slice (one slice per chain group; Langevin step: unused after init)
     size_t lds_base = 0, lds_adapt = 0;  // k_iterate's dynamic LDS: the iteration's own, the adaptation's work area (0: in adapt_scratch)
-    double *adapt_scratch = nullptr;
+    double *adapt_scratch = nullptr;  // per chain Nv^2 + 3 Nv: the work matrix, the deviation, the rank-one step's two coefficient vectors
+    int factor_refresh = 0;  // R of TAMCMC_OPT_FACTOR_REFRESH (at creation)
+    long n_adapt = 0;        // adapting iterations enqueued since creation: what the factor's schedule counts (step_schedule.h::factor_step_mode)
     size_t smp_cap = 0, stat_cap = 0;  // record buffers a.samples / a.stats, in doubles (reserve_records)
     EventArena events;  // every event of the sampler
     static constexpr int N_EV = 64, N_GEV = 8;

@@ -8,6 +8,7 @@
 
 #include "../../include/tamcmc_sampler.h"
 #include "dev_sampler.h"
+#include "factor_update.h"
 #include "host_sampler.h"
 #include "rng.h"
 #include "step_schedule.h"
@@ -18,6 +19,7 @@ extern "C" {
 void tamcmc_hip_ctx_attach(tamcmc_hip_ctx *c);  // capi.hip (private)
 void tamcmc_hip_ctx_detach(tamcmc_hip_ctx *c);
 int tamcmc_hip_envelope_device_engine(const tamcmc_hip_ctx *c);  // the context's TAMCMC_OPT_ENVELOPE_DEVICE_ENGINE
+int tamcmc_hip_factor_refresh(const tamcmc_hip_ctx *c);          // the context's TAMCMC_OPT_FACTOR_REFRESH
 }
 
 struct tamcmc_sampler {
@@ -121,6 +123,7 @@ int tamcmc_sampler_create(tamcmc_sampler **out, tamcmc_hip_ctx *ctx, const tamcm
     g.MALA.fd_step_rel = c->fd_step_rel > 0 ? c->fd_step_rel : 1e-7;
     g.MALA.swap_rule = c->swap_rule == 1 ? 1 : 0;
     s->mala = std::make_unique<MALA>(&g);
+    s->mala->factor_refresh = tamcmc_hip_factor_refresh(ctx);  // read here, by both engines; an existing sampler keeps its value
     s->moves.assign((size_t)c->Nchains, 0);
     s->ctx = ctx;
     s->cur = std::make_unique<Model_def>(&g, s->mala->Tcoefs, false, ctx);
@@ -137,6 +140,7 @@ int tamcmc_sampler_create(tamcmc_sampler **out, tamcmc_hip_ctx *ctx, const tamcm
         di.seed = c->seed; di.dN_mixing = (long)c->dN_mixing; di.chain_groups = c->chain_groups;
         di.swap_rule = g.MALA.swap_rule;
         di.use_drift = c->use_drift ? 1 : 0; di.delta = c->delta; di.fd_step_rel = g.MALA.fd_step_rel;
+        di.factor_refresh = s->mala->factor_refresh;
         di.c0 = c->c0; di.epsilon1 = c->epsilon1; di.epsi2 = c->epsilon2; di.A1 = c->A1; di.target_acceptance = c->target_acceptance;
         int rc = s->dev->init(ctx, di);
         if (rc) return rc;
@@ -173,8 +177,11 @@ int tamcmc_sampler_get_info(const tamcmc_sampler *s, int64_t *info, int32_t n) {
     v[TAMCMC_INFO_NCHAINS] = s->cfg.MALA.Nchains;
     v[TAMCMC_INFO_ADAPT_IN_LDS] = -1;
     if (s->dev) {
-        long d[14];
+        long d[18];
         s->dev->info(d);
+        v[TAMCMC_INFO_FACTOR_UPDATES] = d[14];
+        v[TAMCMC_INFO_FACTOR_REFRESHES] = d[15];
+        v[TAMCMC_INFO_FACTOR_FORCED] = d[16];
         v[TAMCMC_INFO_QUICK_MISMATCH] = d[13];
         v[TAMCMC_INFO_ADAPT_IN_LDS] = d[2];
         v[TAMCMC_INFO_FUSED_AVAILABLE] = d[3];
@@ -187,6 +194,12 @@ int tamcmc_sampler_get_info(const tamcmc_sampler *s, int64_t *info, int32_t n) {
         v[TAMCMC_INFO_ITER_JOINT] = d[11];
         v[TAMCMC_INFO_ITER_WINDOW] = d[12];
     }
+    if (!s->dev)
+        for (long m = 0; m < s->cfg.MALA.Nchains; m++) {
+            v[TAMCMC_INFO_FACTOR_UPDATES] += s->mala->n_factor_updates[(size_t)m];
+            v[TAMCMC_INFO_FACTOR_REFRESHES] += s->mala->n_factor_scheduled[(size_t)m];
+            v[TAMCMC_INFO_FACTOR_FORCED] += s->mala->n_factor_forced[(size_t)m];
+        }
     for (int32_t i = 0; i < n && i < TAMCMC_SAMPLER_INFO_N; i++) info[i] = v[i];
     return TAMCMC_OK;
 }
@@ -360,6 +373,29 @@ int tamcmc_sampler_get_proposal(const tamcmc_sampler *s, int32_t m, double *mu, 
     return TAMCMC_OK;
 }
 
+int tamcmc_sampler_get_factor(const tamcmc_sampler *s, int32_t m, double *L) {
+    if (!s || !L || m < 0 || m >= s->cfg.MALA.Nchains) return TAMCMC_ERR_BAD_ARG;
+    if (s->dev) return s->dev->download_factor((int)m, L);  // (the factor exists on the device only; the host mirror's is its own)
+    const Matrix &F = s->mala->factor((int)m);
+    std::memcpy(L, F.a.data(), F.a.size() * sizeof(double));
+    return TAMCMC_OK;
+}
+
+int tamcmc_factor_rank_one_update(int32_t Nvars, double *L, const double *w, double beta2) {
+    if (Nvars < 1 || !L || !w || !std::isfinite(beta2) || !(beta2 > 0.0)) return TAMCMC_ERR_BAD_ARG;
+    const size_t n = (size_t)Nvars;
+    for (size_t i = 0; i < n; i++) {
+        if (!std::isfinite(w[i]) || !(L[i * n + i] > 0.0)) return TAMCMC_ERR_BAD_ARG;
+        for (size_t k = 0; k <= i; k++)
+            if (!std::isfinite(L[i * n + k])) return TAMCMC_ERR_BAD_ARG;
+    }
+    std::vector<double> work(3 * n);
+    if (!factor_rank_one_serial((long)n, L, (long)n, w, beta2, work.data())) return TAMCMC_ERR_BAD_ARG;
+    for (size_t i = 0; i < n; i++)
+        for (size_t k = i + 1; k < n; k++) L[i * n + k] = 0.0;
+    return TAMCMC_OK;
+}
+
 int tamcmc_sampler_set_proposal(tamcmc_sampler *s, int32_t m, const double *mu, const double *covarmat, double sigma) {
     if (!s || m < 0 || m >= s->cfg.MALA.Nchains) return TAMCMC_ERR_BAD_ARG;
     if (int rc = s->refresh()) return rc;
@@ -449,7 +485,7 @@ int tamcmc_sampler_set_state(tamcmc_sampler *s, const double *vars, int64_t iter
     for (long m = 0; m < Nc; m++) {
         std::memcpy(s->cur->vars.row(m), vars + (size_t)m * Nv, (size_t)Nv * sizeof(double));
         s->cur->update_params_with_vars(m);
-        s->mala->invalidate((int)m);  // cached gradient of the old position
+        s->mala->invalidate_gradient((int)m);  // cached gradient of the old position (the law and its factor stay)
     }
     int rc = s->cur->generate_models_batch(&s->cfg.data.data, s->mala->Tcoefs);
     if (rc) return rc;

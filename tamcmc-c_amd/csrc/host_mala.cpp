@@ -11,6 +11,7 @@
 #include <cstring>
 #include <limits>
 
+#include "factor_update.h"
 #include "host_sampler.h"
 #include "rng.h"
 #include "step_schedule.h"
@@ -70,6 +71,11 @@ MALA::MALA(Config *cfg) {
     init_proposal(vars, vars_names, cfg->MALA.var_names_errors, cfg->MALA.fraction_errors, cfg->MALA.offset_errors);
     Lchol.assign((size_t)Nchains, Matrix());
     Lchol_valid.assign((size_t)Nchains, 0);
+    Lchol_ok.assign((size_t)Nchains, 0);
+    Lchol_adapted.assign((size_t)Nchains, 0);
+    n_factor_updates.assign((size_t)Nchains, 0);
+    n_factor_scheduled.assign((size_t)Nchains, 0);
+    n_factor_forced.assign((size_t)Nchains, 0);
     grad_cur = Matrix(Nchains, Nvars);
     grad_prop = Matrix(Nchains, Nvars);
     gradP_cur = Matrix(Nchains, Nvars);
@@ -103,11 +109,12 @@ long double MALA::p1_fct(long double x) {  // MALA.cpp:135-151
     if (x > A1) return A1;
     return x;
 }
-void MALA::p2_fct(Matrix &x) {  // MALA.cpp:153-164 (Frobenius norm)
+bool MALA::p2_fct(Matrix &x) {  // MALA.cpp:153-164 (Frobenius norm); true: the matrix was rescaled
     long double n2 = 0;
     for (double v : x.a) n2 += (long double)v * v;
     const double nrm = (double)std::sqrt(n2);
     if (!(nrm <= A1)) for (double &v : x.a) v = (double)(v * A1 / nrm);
+    return !(nrm <= A1);
 }
 void MALA::p3_fct(std::vector<double> &x) {  // MALA.cpp:166-176
     long double n2 = 0;
@@ -131,10 +138,25 @@ void MALA::update_proposal(const double *vars, long double acceptance, int m) {
         const double di = d[(size_t)i];
         for (long j = 0; j < Nvars; j++) ci[j] = ci[j] + g * (di * d[(size_t)j] - ci[j]);
     }
-    p2_fct(C);
+    const bool rescaled = p2_fct(C);
+    const double sigma_old = sigma[(size_t)m];
     const long double v1 = sigma[(size_t)m] + gamma * (acceptance - target_acceptance);
     sigma[(size_t)m] = (double)p1_fct(v1);
+    // the factor (factor_update.h): a rank-one step of the factor in force, or today's full factorisation (deferred to factor())
+    const int mode = factor_step_mode(factor_refresh, n_adapt);
+    if (factor_takes_rank_one(mode, g, rescaled, Lchol_valid[(size_t)m] && Lchol_ok[(size_t)m])) {
+        Matrix &L = Lchol[(size_t)m];
+        std::vector<double> w((size_t)Nvars), work(3 * (size_t)Nvars);
+        const double ws = factor_w_scale(g, sigma[(size_t)m]);
+        for (long k = 0; k < Nvars; k++) w[(size_t)k] = ws * d[(size_t)k];
+        // refused (a pivot not finite and positive): the old factor stays in force, the next adapting iteration is full
+        if (factor_rank_one_serial(Nvars, L.a.data(), Nvars, w.data(), factor_beta2(g, sigma_old, sigma[(size_t)m]), work.data())) n_factor_updates[(size_t)m]++;
+        else Lchol_ok[(size_t)m] = 0;
+        return;
+    }
+    (mode == 2 ? n_factor_forced : n_factor_scheduled)[(size_t)m]++;
     Lchol_valid[(size_t)m] = 0;
+    Lchol_adapted[(size_t)m] = 1;
 }
 
 // cached Cholesky factor of (covarmat[m] + epsilon2) * sigma[m]  (MALA.cpp:348-350 recomputes it every call)
@@ -145,7 +167,9 @@ const Matrix &MALA::factor(int m) {
         for (double &v : T.a) v *= sigma[(size_t)m];
         // not positive definite (only while gamma = c0/(1+i) > 1): the previous factor stays -- same rule as the device engine
         // (dev_iterate_impl.h::adapt_chain); the reference hands Eigen's partially computed factor on (MALA.cpp:348-350)
-        if (cholesky_lower(T) || Lchol[(size_t)m].a.empty()) Lchol[(size_t)m] = T;
+        const bool pd = cholesky_lower(T);
+        if (pd || Lchol[(size_t)m].a.empty()) Lchol[(size_t)m] = T;
+        Lchol_ok[(size_t)m] = (pd && Lchol_adapted[(size_t)m]) ? 1 : 0;  // (a law from outside defers its factorisation to here: no mark)
         Lchol_valid[(size_t)m] = 1;
     }
     return Lchol[(size_t)m];
@@ -402,6 +426,7 @@ int MALA::step(Model_def *cur, Model_def *prop, Data *data, Config *) {
         if (learn_at(i))
             update_proposal(cur->vars.row(m), cur->Pmove[(size_t)m], (int)m);  // position unchanged: gradient stays valid
     }
+    if (learn_at(i)) n_adapt++;  // (the count the factor's schedule reads: step_schedule.h::factor_step_mode)
     // [3] parallel tempering (MALA.cpp:688-703)
     if (is_swap_iteration((int)Nchains, dN_mixing, i)) parallel_tempering(cur);
     else { cur->swaped = false; cur->Pswap = 0; }

@@ -149,6 +149,9 @@ class MALA {  // MALA.h:26-69
     int swap_rule = 0;
     std::vector<Matrix> Lchol;          // cached factor of (covarmat+epsilon2)*sigma per chain
     std::vector<char> Lchol_valid;
+    std::vector<char> Lchol_ok;         // the factor in force is "marked valid" (factor_update.h's condition of a rank-one step): made by an adapting
+                                        // iteration of a positive definite matrix, or by a rank-one step; cleared wherever the law changes from outside
+    std::vector<char> Lchol_adapted;    // the deferred factorisation (Lchol_valid = 0) is an adapting iteration's full step: only that one sets the mark
     // Langevin state (use_drift): gradient of the tempered log-posterior at the current / proposed position
     Matrix grad_cur, grad_prop;
     Matrix gradP_cur, gradP_prop;       // the prior's share of those gradients (not tempered)
@@ -161,6 +164,11 @@ class MALA {  // MALA.h:26-69
     std::vector<Matrix> covarmat;
     long iteration = 0;                 // the reference's loop counter i (MALA.cpp:623)
     long Nswap_attempts = 0, Nswap_accepted = 0;
+    // TAMCMC_OPT_FACTOR_REFRESH (read at creation): R, the adapting iterations done so far, and per chain the rank-one steps taken, the
+    // full factorisations that were scheduled and those that a refused condition forced
+    int factor_refresh = 0;
+    long n_adapt = 0;
+    std::vector<long> n_factor_updates, n_factor_scheduled, n_factor_forced;
 
     explicit MALA(Config *cfg);
     void init_proposal(const std::vector<double> &vars, const std::vector<std::string> &var_names,
@@ -172,7 +180,7 @@ class MALA {  // MALA.h:26-69
     std::vector<double> new_prop_values(const double *vars, int m, const double *drift);   // MALA.cpp:339
     int parallel_tempering(Model_def *model);                                        // MALA.cpp:397
     long double p1_fct(long double x);
-    void p2_fct(Matrix &x);
+    bool p2_fct(Matrix &x);
     void p3_fct(std::vector<double> &x);
     // one iteration of the loop body MALA.cpp:645-703 for ALL chains (propose all -> batched evaluate -> accept all)
     int step(Model_def *model_current, Model_def *model_propose, Data *data_struc, Config *cfg);
@@ -181,7 +189,8 @@ class MALA {  // MALA.h:26-69
     const Matrix &factor(int m);
     bool learn_at(long i) const;  // MALA.cpp:656-667: is the proposal law updated after iteration i?
     uint64_t get_seed() const { return seed; }
-    void invalidate(int m) { Lchol_valid[(size_t)m] = 0; grad_valid[(size_t)m] = 0; }
+    void invalidate(int m) { Lchol_valid[(size_t)m] = 0; Lchol_ok[(size_t)m] = 0; Lchol_adapted[(size_t)m] = 0; grad_valid[(size_t)m] = 0; }  // a law from outside: the factor is deferred, the next adapting iteration is full
+    void invalidate_gradient(int m) { grad_valid[(size_t)m] = 0; }  // a position from outside: the law and its factor stay
     // the gradient held for chain m's position (tamcmc_sampler_get_gradient): rows of grad_cur / gradP_cur, and whether it is current
     const double *held_gradient(int m) const { return grad_cur.a.data() + (size_t)m * (size_t)Nvars; }
     const double *held_gradient_prior(int m) const { return gradP_cur.a.data() + (size_t)m * (size_t)Nvars; }

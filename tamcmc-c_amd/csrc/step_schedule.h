@@ -31,6 +31,13 @@ TAMCMC_HD_FLAT int swap_pair(uint64_t seed, int C, long dN_mixing, long it, doub
     return is_swap_iteration(C, dN_mixing, it) ? swap_draw(seed, C, it, u_out) : -1;
 }
 
+// ---- the proposal factor in an adapting iteration (TAMCMC_OPT_FACTOR_REFRESH = R; factor_update.h has the rule's other conditions) ----
+
+// What the k-th adapting iteration of a sampler (k counted from 0 since its creation, on the host) does with the factor: 1 = a full
+// factorisation, scheduled (always with R < 2: today's sampler; every R-th adapting iteration otherwise), 2 = a rank-one step where the
+// chain's state allows it.  (0 is "no adaptation" in the kernels' learn arguments.)
+TAMCMC_HD int factor_step_mode(int R, long k) { return (R >= 2 && k % R != 0) ? 2 : 1; }
+
 // ---- chain groups ----
 
 // Group of `chain` among the G contiguous groups [goff[g], goff[g+1]).

@@ -38,6 +38,8 @@ EXTRA_ABI += [
     ("tamcmc_sampler_get_state", C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _i64p]),
     ("tamcmc_sampler_get_proposal", C.c_int, [_vp, C.c_int32, _dp, _dp]),
     ("tamcmc_sampler_set_proposal", C.c_int, [_vp, C.c_int32, _dp, _dp, C.c_double]),
+    ("tamcmc_sampler_get_factor", C.c_int, [_vp, C.c_int32, _dp]),
+    ("tamcmc_factor_rank_one_update", C.c_int, [C.c_int32, _dp, _dp, C.c_double]),
     ("tamcmc_sampler_seed_proposal_fisher", C.c_int, [_vp, C.c_double, _dp]),
     ("tamcmc_fisher_seed_covariance", C.c_int, [C.c_int32, _dp, _dp, _dp]),
     ("tamcmc_sampler_set_state", C.c_int, [_vp, _dp, C.c_int64]),
@@ -154,12 +156,13 @@ class Sampler:
 
     def info(self):
         """tamcmc_sampler_get_info as a dict (engine, sizes, which side of the size limits, iterations per scheme)."""
-        v = np.zeros(15, dtype=np.int64)
-        rc = self._L.tamcmc_sampler_get_info(self._h, _p(v, _i64p), 15)
+        v = np.zeros(18, dtype=np.int64)
+        rc = self._L.tamcmc_sampler_get_info(self._h, _p(v, _i64p), 18)
         if rc != OK:
             raise TamcmcError(rc, "tamcmc_sampler_get_info")
         keys = ("engine", "nvars", "nparams", "nchains", "adapt_in_lds", "fused_available", "chain_groups", "iter_fused", "iter_lockstep",
-                "fused_stretches", "quick_fallbacks", "quick_sure", "iter_joint", "iter_window", "quick_mismatch")
+                "fused_stretches", "quick_fallbacks", "quick_sure", "iter_joint", "iter_window", "quick_mismatch", "factor_updates", "factor_refreshes",
+                "factor_refreshes_forced")
         return dict(zip(keys, (int(x) for x in v)))
 
     def gradient(self):
@@ -270,6 +273,14 @@ class Sampler:
         cov = _f64(cov) if cov is not None else None
         self._L.tamcmc_sampler_set_proposal(self._h, int(m), _p(mu), _p(cov), float(sigma))
 
+    def factor(self, m):
+        """The factor in force for chain m (tamcmc_sampler_get_factor): [Nvars x Nvars], lower triangular."""
+        L = np.zeros((self.nvars, self.nvars))
+        rc = self._L.tamcmc_sampler_get_factor(self._h, int(m), _p(L))
+        if rc != OK:
+            raise TamcmcError(rc, "tamcmc_sampler_get_factor")
+        return L
+
     def seed_proposal_fisher(self, hstep_rel=0.0):
         """Seeds every chain's proposal covariance with E (I + E F E)^-1 E, F the Fisher information at the chain's position and temperature
         (tamcmc_sampler_seed_proposal_fisher; hstep_rel = 0: 1e-6).  Returns F [Nchains x Nvars x Nvars]."""
@@ -290,6 +301,18 @@ def fisher_seed_covariance(F, errors):
     if rc != OK:
         raise TamcmcError(rc, "tamcmc_fisher_seed_covariance")
     return cov
+
+
+def factor_rank_one_update(L, w, beta2):
+    """The Cholesky factor of beta2 L L^T + w w^T from the lower-triangular L, on the host (tamcmc_factor_rank_one_update): the rank-one step
+    of OPT_FACTOR_REFRESH for one chain.  Returns a new array."""
+    lib_ = _rebind()
+    out, w = np.array(L, dtype=np.float64, order="C", copy=True), _f64(w)
+    assert out.ndim == 2 and out.shape == (w.size, w.size)
+    rc = lib_.tamcmc_factor_rank_one_update(w.size, _p(out), _p(w), float(beta2))
+    if rc != OK:
+        raise TamcmcError(rc, "tamcmc_factor_rank_one_update")
+    return out
 
 
 def default_errors(star):
