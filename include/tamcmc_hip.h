@@ -155,6 +155,13 @@ extern "C" {
                                         factorisation every R-th adapting iteration (both engines, both samplers, every model; the law and
                                         the rule: tamcmc_sampler.h).  Read when the sampler is created: changing it afterwards does not
                                         affect an existing sampler.  Any other value: TAMCMC_ERR_BAD_ARG */
+#define TAMCMC_OPT_ENVELOPE_GRADIENT 15 /* value: 0/1 (default 0) -- 1: for the Gaussian-envelope models, ids 0 and 1, tamcmc_hip_fd_gradient and
+                                        tamcmc_hip_fd_gradient_posterior (and with them the host engine's Langevin step) take the
+                                        likelihood's share from the analytic gradient, one pass over the bins per chain instead of
+                                        Nvars + 1 (see tamcmc_hip_envelope_gradient_sums).  Read at every call.  hstep is still required: it
+                                        sets the prior's forward and backward points and is not read by the likelihood's share.
+                                        TAMCMC_GRADIENT_ADJOINT keeps refusing these ids, and the device-resident engine keeps refusing
+                                        use_drift = 1 for them.  Any other value: TAMCMC_ERR_BAD_ARG */
 #define TAMCMC_FISHER_SLAB 2048     /* bins per workgroup (and per partial matrix) of the Gram kernel of tamcmc_hip_fisher / _weighted_gram */
 
 /* One (n,l) multiplet: <=7 Lorentzian m-components on its truncation window.
@@ -351,6 +358,46 @@ int tamcmc_hip_fd_gradient_posterior(tamcmc_hip_ctx *ctx, int model_id, int prio
  * beyond a table's own rows. */
 int tamcmc_hip_adjoint_table(tamcmc_hip_ctx *ctx, int model_id, int C, const double *params, int64_t Nparams, const int32_t *plength,
                              const double *Tcoefs, double p, double *G, double *Gn, int *nrows);
+
+/* Analytic gradient of the Gaussian-envelope fits (ids 0, 1; TAMCMC_OPT_ENVELOPE_GRADIENT = 1).  Both models are closed forms in which
+ * every parameter moves every bin, so with r_i = 1/M_i - y_i/M_i^2
+ *   dS/dtheta_j = sum_i r_i dM_i/dtheta_j,   S = sum_i (y_i/M_i + ln M_i),   logL = -(long)p S / T.
+ * The device sums r against the derivatives of M with respect to the ROW QUANTITIES (the scalars formed once per vector) in the pass that
+ * forms M -- 1024-bin tiles, one partial per (vector, tile), folded in a fixed order, no atomics -- and the host applies the chain rule
+ * from row quantities to parameters in long double.  With L = 1/(1 + e^u), D = L (1 - L), g = exp(-d^2/(2 sigma^2)), d = x - nu:
+ *   id 1  M = A g + sum_q H_q L_q + N0, u_q = pw_q (lna_q + ln x):   dM/dA = g, dM/dnu = A g d/sigma^2, dM/dsigma^2 = A g d^2/(2 sigma^4),
+ *         dM/dN0 = 1, dM/dH_q = L_q, dM/dlna_q = -H_q D_q pw_q, dM/dpw_q = -H_q D_q (lna_q + ln x); a term with tc = 0 is switched off and
+ *         has 0 in its three places.  A = |p7|, nu = p8, sigma^2 = |p9|^2, N0 = |p6|, H = |p[3q]|, lna = ln(1e-3 |p[3q+1]|), pw = |p[3q+2]|.
+ *   id 0  M = A eta^2 g + N0 + sum_k C_k L_k, u_k = c_k (ln x - ln b_k), C_k = a_k^2/(h I_k), I_k = sum_i w_i L_k(x_i) (the trapezoid sum
+ *         of the normalisation, h = x(1) - x(0)):   g's derivatives as above times eta^2, dM/da_k^2 = L_k/(h I_k),
+ *         dM/dln b_k = C_k (c_k D_k - L_k I_k^b/I_k), I_k^b = sum_i w_i c_k D_k,
+ *         dM/dc_k = C_k (-D_k (ln x - ln b_k) - L_k I_k^c/I_k), I_k^c = -sum_i w_i D_k (ln x - ln b_k):
+ *         the normalisation integral moves with b_k and c_k.  (c_k D_k - L_k I_k^b/I_k = c_k L_k (Lbar_k - L_k), Lbar_k = sum w L_k^2 / I_k:
+ *         the sums are formed for both forms and the one whose terms are the smaller is used, so a spectrum whose bins all lie on one
+ *         side of b_k keeps its digits.)  a_0^2 = (p0 nu^p1)^2, a_1 = p5, a_2 = p6,
+ *         ln b_k = ln|p_i| + p_j ln|nu + mu| for (i, j) = (2, 3), (7, 8), (10, 11), c = |p4|, |p9|, |p12|, N0 = |p13|, A = |p14|,
+ *         nu = |p15|, sigma = |p16|, mu = p17.  p18 does not reach the model: its likelihood share is exactly 0.
+ * Conventions.  d|p|/dp = copysign(1, p).  A bin adds exactly 0 to the lna / pw / ln b / c sums when D = 0 (a saturated term, which
+ * includes a first bin at x = 0) or when its ln x term is not finite.  With pw = 0 (or c = 0) the power law is 1 and L = 1/2, as the
+ * evaluation has it.  A degenerate vector (b_k = 0, tc = 0: d lna/dtc = 1/tc) gives non-finite components; they are returned as they come
+ * (both samplers map a non-finite component to 0).
+ * logL0 is tamcmc_hip_loglike_params_batch's bit for bit (the two sums of S and I_k are formed by the evaluation's statements in its
+ * orders); the prior's share and logPr0 are the default route's bits (same forward / backward points, same kernel).  A vector's sums do
+ * not depend on the batch it sits in; two calls give the same bits.
+ * Tolerance: M is stated to 1e-12 per bin, so component j lies within
+ *   B_j = 1e-12 sum_i |dM_i/dtheta_j| (1/M_i + 2 y_i/M_i^2)   (summed over the chain-rule branches of theta_j)
+ * of a 50-digit derivative of S itself (tests/test_gpu_envelope_gradient.py; measured ratios in DESIGN section 9).
+ *
+ * The audit entry: the row-space sums before the chain rule, whatever the option says.  S[C] (un-tempered); sums[C x TAMCMC_ENVELOPE_GRAD_N]
+ * = dS/d(row quantity) in the order
+ *   id 1  [A, nu, sigma^2, N0, H_0, H_1, lna_0, lna_1, pw_0, pw_1, 0, 0, 0]
+ *   id 0  [A, nu (through the Gaussian only), sigma^2, N0, a_0^2, a_1^2, a_2^2, ln b_0, ln b_1, ln b_2, c_0, c_1, c_2];
+ * ksi[C x TAMCMC_ENVELOPE_KSI_N] (id 0; may be NULL, not written for id 1) = [I_0, I_1, I_2, I_0^b, I_1^b, I_2^b, I_0^c, I_1^c, I_2^c].
+ * Other model ids: TAMCMC_ERR_BAD_MODEL; no spectrum: TAMCMC_ERR_NO_SPECTRUM. */
+#define TAMCMC_ENVELOPE_GRAD_N 13
+#define TAMCMC_ENVELOPE_KSI_N 9
+int tamcmc_hip_envelope_gradient_sums(tamcmc_hip_ctx *ctx, int model_id, int C, const double *params, int64_t Nparams, double *S, double *sums,
+                                      double *ksi);
 
 /* Audit entry of the red-giant gradient batches (ids 25, 27; others: TAMCMC_ERR_BAD_MODEL): the tables of the B = C x (Nvars + 1) vectors
  * of a batch -- slot c (Nvars + 1) is chain c's vector, slot c (Nvars + 1) + 1 + k the same with hstep[k] added to index_to_relax[k] --

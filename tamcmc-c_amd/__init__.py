@@ -31,6 +31,8 @@ OPT_GRADIENT, GRADIENT_FD, GRADIENT_ADJOINT = 9, 0, 1  # gradient batches: finit
 OPT_RGB_DEVICE_LANGEVIN = 11  # 1: Sampler(use_drift=1, engine="device") is built for the red-giant ids 25 / 27 (default 0: ERR_BAD_MODEL); read at creation
 OPT_ENVELOPE_DEVICE_ENGINE = 13  # 1: Sampler(engine="device", use_drift=0) is built for the Gaussian-envelope ids 0 / 1 (default 0: ERR_BAD_MODEL); read at creation
 OPT_FACTOR_REFRESH = 14  # R: 0 / 1 a full factorisation in every adapting iteration (default); 2 ... 65536 rank-one steps of the proposal factor, a full one every R-th; read at creation
+OPT_ENVELOPE_GRADIENT = 15  # 1: fd_gradient / fd_gradient_posterior (and the host engine's Langevin step) take the analytic likelihood share for ids 0 / 1 (default 0: brute force); read at every call
+ENVELOPE_GRAD_N, ENVELOPE_KSI_N = 13, 9  # row quantities / xi sums per vector of HipContext.envelope_gradient_sums
 OPT_RGB_ADJOINT = 12  # 1: under GRADIENT_ADJOINT the red-giant ids 25 / 27 take the hybrid adjoint batch (default 0: ERR_BAD_MODEL); read at every call
 OPT_FISHER_WORKSPACE_MB = 10  # MiB of model rows HipContext.fisher keeps on the device per pass (default 2048)
 FISHER_SLAB = 2048  # bins per workgroup of the Gram kernel (TAMCMC_FISHER_SLAB)
@@ -70,6 +72,7 @@ ABI = [
     ("tamcmc_hip_fd_gradient_posterior", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, C.c_int64, _ip, _ip, C.c_int, _dp, _dp, C.c_double,
                                                   _dp, _ip, _dp, _dp, _dp, _dp, _dp]),
     ("tamcmc_hip_adjoint_table", C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int64, _ip, _dp, C.c_double, _dp, _dp, C.POINTER(C.c_int)]),
+    ("tamcmc_hip_envelope_gradient_sums", C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int64, _dp, _dp, _dp]),
     ("tamcmc_hip_fisher", C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int64, _ip, _ip, C.c_int, _dp, _dp, C.c_double, _dp]),
     ("tamcmc_hip_weighted_gram", C.c_int, [_vp, C.c_int, C.c_int64, _dp, _dp, _dp]),
     ("tamcmc_hip_get_fisher_times", C.c_int, [_vp, _dp, _dp, _dp]),
@@ -280,6 +283,17 @@ class HipContext:
         self._chk(self._L.tamcmc_hip_adjoint_table(self._h, int(model_id), Cn, _p(params), Np, _p(plength, _ip), _p(T), float(p), _p(G), _p(Gn),
                                                    C.byref(n)))
         return G, Gn
+
+    def envelope_gradient_sums(self, model_id, params):
+        """Row-space sums of the envelope fits' analytic gradient, before the chain rule (tamcmc_hip_envelope_gradient_sums; ids 0 / 1):
+        (S [C], sums [C x 13] = dS/d(row quantity), ksi [C x 9] -- the xi sums I_k, I_k^b, I_k^c of id 0, zeros for id 1)."""
+        params = _f64(params)
+        if params.ndim == 1:
+            params = params[None, :]
+        Cn, Np = params.shape
+        S, sums, ksi = np.zeros(Cn), np.zeros((Cn, ENVELOPE_GRAD_N)), np.zeros((Cn, ENVELOPE_KSI_N))
+        self._chk(self._L.tamcmc_hip_envelope_gradient_sums(self._h, int(model_id), Cn, _p(params), Np, _p(S), _p(sums), _p(ksi)))
+        return S, sums, ksi
 
     def rgb_batch_tables(self, model_id, params, plength, index_to_relax, hstep):
         """The tables of a red-giant gradient batch as its own builder leaves them (tamcmc_hip_rgb_batch_tables), in batch order: slot

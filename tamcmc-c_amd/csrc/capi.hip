@@ -70,7 +70,7 @@ void tamcmc_hip_destroy(tamcmc_hip_ctx *c) {
     c->h_stage.release(); c->d_stage.release();
     c->d_part.release(); c->d_S.release(); c->d_model.release(); c->h_S.release();
     c->d_fd.release(); c->d_poly.release(); c->h_fd.release();
-    c->d_rgb.release(); c->h_rgb.release(); c->d_bg.release(); c->d_env.release(); c->d_fisher.release();
+    c->d_rgb.release(); c->h_rgb.release(); c->d_bg.release(); c->d_env.release(); c->d_envg.release(); c->d_fisher.release();
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->ev_split)
@@ -125,6 +125,10 @@ int tamcmc_hip_set_option(tamcmc_hip_ctx *c, int option, int64_t value) {
     case TAMCMC_OPT_FACTOR_REFRESH:
         if (value < 0 || value > 65536) return TAMCMC_ERR_BAD_ARG;
         c->factor_refresh = (int)value;
+        return TAMCMC_OK;
+    case TAMCMC_OPT_ENVELOPE_GRADIENT:
+        if (value < 0 || value > 1) return TAMCMC_ERR_BAD_ARG;
+        c->envelope_gradient = (int)value;
         return TAMCMC_OK;
     case TAMCMC_OPT_RGB_ADJOINT:
         if (value < 0 || value > 1) return TAMCMC_ERR_BAD_ARG;

@@ -84,6 +84,7 @@ struct tamcmc_hip_ctx {
     int rgb_adjoint = 0;  // 1: under TAMCMC_GRADIENT_ADJOINT the red-giant ids take the hybrid batch (fd_batch.hip; read at every call)
     int envelope_device_engine = 0;  // 1: the device-resident engine is built for the Gaussian-envelope ids 0 / 1 (read at sampler creation)
     int factor_refresh = 0;  // R of TAMCMC_OPT_FACTOR_REFRESH: < 2 a full factorisation per adapting iteration, else rank-one steps (read at sampler creation)
+    int envelope_gradient = 0;  // 1: the gradient batches of ids 0 / 1 take the analytic likelihood share (envelope.hip; read at every call)
     // resident spectrum
     int64_t Nx = 0;
     std::vector<double> hx;  // host copy of x (table builders need x[0], x[Nx-1], step)
@@ -97,6 +98,7 @@ struct tamcmc_hip_ctx {
     tamcmc::DevBuf<unsigned char> d_rgb;  // red-giant pre-step workspace (rgb_prestep.hip)
     tamcmc::PinBuf<unsigned char> h_rgb;  // its pinned host image: [Prep B | RowIn B] going up, [int status B] coming back
     tamcmc::DevBuf<double> d_env;  // Gaussian-envelope fits: per (vector, chunk) trapezoid sums of the Kallinger normalisations
+    tamcmc::DevBuf<double> d_envg;  // their analytic gradient: folded sums per vector, tile and chunk partials (envelope_grad_enqueue)
     tamcmc::DevBuf<double> d_bg;  // FAST far field: background series per (evaluation, tile) (bg_series.h)
     // finite-difference batches built on the device (fd_batch.hip)
     tamcmc::DevBuf<unsigned char> d_fd, d_poly;

@@ -37,4 +37,14 @@ int envelope_fd_run(tamcmc_hip_ctx *c, int model_id, bool with_prior, int prior_
                     const int32_t *index_to_relax, int Nvars, const double *hstep, const double *Tcoefs, double p, const double *priors,
                     const int32_t *priors_switch, double *logL0, double *logPr0, double *grad, double *grad_prior);
 
+// The same two entries with TAMCMC_OPT_ENVELOPE_GRADIENT = 1: the likelihood's share from the analytic gradient, one pass over the bins
+// per chain (k_env_ksi_grad, k_env_grad, k_env_grad_fold; the chain rule from row quantities to parameters on the host in long double,
+// env_row_jacobian); the prior's share and logPr0 from the same forward / backward points as envelope_fd_run, through the same kernel
+int envelope_grad_run(tamcmc_hip_ctx *c, int model_id, bool with_prior, int prior_class, int C, const double *params, int64_t Nparams,
+                      const int32_t *index_to_relax, int Nvars, const double *hstep, const double *Tcoefs, double p, const double *priors,
+                      const int32_t *priors_switch, double *logL0, double *logPr0, double *grad, double *grad_prior);
+
+// tamcmc_hip_envelope_gradient_sums: S [C], dS / d(row quantity) [C x TAMCMC_ENVELOPE_GRAD_N], the xi sums [C x 9] (id 0; ksi may be nullptr)
+int envelope_gradient_sums(tamcmc_hip_ctx *c, int model_id, int C, const double *params, int64_t Nparams, double *S, double *sums, double *ksi);
+
 }  // namespace tamcmc

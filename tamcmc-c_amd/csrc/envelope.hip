@@ -23,6 +23,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <vector>
 
 #include "../../include/tamcmc_hip.h"
@@ -66,6 +67,86 @@ __global__ void __launch_bounds__(EWG) k_env_eval(const double *x, const double 
         p[0] = out[0];
         p[1] = out[1];
     }
+}
+
+// ---- analytic gradient (TAMCMC_OPT_ENVELOPE_GRADIENT = 1): the same geometry, one pass over the bins per vector ----
+//   k_env_ksi_grad (id 0)  grid (chunks, C): k_env_ksi's three sums (same bits, same place: d_env) and the nine that carry the
+//                          normalisation integrals' dependence on b_k and c_k;
+//   k_env_grad             grid (tiles, C): env_ksi_coef as k_env_eval has it, then the tile's two sums of S (the layout k_finalize reads)
+//                          and its 10 / 16 gradient sums, one partial per (vector, tile);
+//   k_env_grad_fold        one workgroup per vector: the tile partials (and id 0's chunk partials) in a fixed order, no atomics; S[b] by
+//                          k_finalize's statements (same strides, same tree), so the bits of the evaluation route.
+__global__ void __launch_bounds__(EWG) k_env_ksi_grad(const double *logx, int Nx, int nchunk, const EnvRow *rows, double *part, double *gpart) {
+    __shared__ double s_red[ENV_GRAD_NKRAW * (EWG / 64)];
+    const int chunk = blockIdx.x, b = blockIdx.y;
+    double out[ENV_GRAD_NKRAW];
+    env_ksi_grad_chunk(logx, Nx, chunk, rows[b], s_red, out);
+    if (threadIdx.x == 0) {
+        double *p = part + ((size_t)b * nchunk + chunk) * 3, *g = gpart + ((size_t)b * nchunk + chunk) * (ENV_GRAD_NKRAW - 3);
+        for (int k = 0; k < 3; k++) p[k] = out[k];
+        for (int k = 0; k < ENV_GRAD_NKRAW - 3; k++) g[k] = out[3 + k];
+    }
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(EWG) k_env_grad(const double *x, const double *y, const double *logx, int Nx, int ntiles, int nchunk, double h,
+                                                  double xmax, const EnvRow *rows, const double *ksi_part, double *part, double *gpart) {
+    constexpr int NG = KIND == 0 ? ENV_GRAD_NRAW0 : ENV_GRAD_NRAW1;
+    __shared__ double s_red[(2 + NG) * (EWG / 64)];
+    __shared__ double s_coef[3];
+    const int tile = blockIdx.x, b = blockIdx.y;
+    const EnvRow &R = rows[b];
+    if (KIND == 0) env_ksi_coef(ksi_part + (size_t)b * nchunk * 3, nchunk, h, R, s_red, s_coef);
+    double out[2 + NG];
+    env_grad_tile<KIND>(x, y, logx, Nx, tile, xmax, R, s_coef, s_red, out);
+    if (threadIdx.x == 0) {
+        double *p = part + ((size_t)b * ntiles + tile) * 2, *g = gpart + ((size_t)b * ntiles + tile) * NG;
+        p[0] = out[0];
+        p[1] = out[1];
+#pragma unroll
+        for (int j = 0; j < NG; j++) g[j] = out[2 + j];
+    }
+}
+
+// per vector: the NG tile sums -> gsum[b * ENV_GRAD_NRAWMAX ...]; id 0: the chunk sums -> ksum[b * ENV_GRAD_NKRAW ...], the first three summed as
+// env_ksi_coef sums them (the I_k every tile used); S[b] from the tiles' two sums as k_finalize (kernels.hip) forms it
+template <int NG>
+__global__ void __launch_bounds__(EWG) k_env_grad_fold(const double *part, const double *gpart, int ntiles, const double *ksi_part,
+                                                       const double *ksi_gpart, int nchunk, double *S, double *gsum, double *ksum) {
+    __shared__ double s_red[(2 + NG) * (EWG / 64)];
+    const int b = blockIdx.x;
+    double s[2 + NG], out[2 + NG];
+#pragma unroll
+    for (int j = 0; j < 2 + NG; j++) s[j] = 0.0;
+    for (int t = threadIdx.x; t < ntiles; t += EWG) {
+        const double *q = part + ((size_t)b * ntiles + t) * 2, *p = gpart + ((size_t)b * ntiles + t) * NG;
+        s[0] = s[0] + q[0];
+        s[1] = s[1] + q[1];
+#pragma unroll
+        for (int j = 0; j < NG; j++) s[2 + j] = s[2 + j] + p[j];
+    }
+    env_block_reduce<2 + NG>(s, s_red, out);
+    if (threadIdx.x == 0) {
+        S[b] = out[0] + out[1];
+        for (int j = 0; j < NG; j++) gsum[(size_t)b * ENV_GRAD_NRAWMAX + j] = out[2 + j];
+        for (int j = NG; j < ENV_GRAD_NRAWMAX; j++) gsum[(size_t)b * ENV_GRAD_NRAWMAX + j] = 0.0;
+    }
+    if (NG != ENV_GRAD_NRAW0) return;
+    __syncthreads();
+    constexpr int NK = ENV_GRAD_NKRAW;
+    double k9[NK], o9[NK];
+#pragma unroll
+    for (int j = 0; j < NK; j++) k9[j] = 0.0;
+    for (int ch = threadIdx.x; ch < nchunk; ch += EWG) {
+        const double *p = ksi_part + ((size_t)b * nchunk + ch) * 3, *g = ksi_gpart + ((size_t)b * nchunk + ch) * (NK - 3);
+#pragma unroll
+        for (int j = 0; j < 3; j++) k9[j] = k9[j] + p[j];
+#pragma unroll
+        for (int j = 0; j < NK - 3; j++) k9[3 + j] = k9[3 + j] + g[j];
+    }
+    env_block_reduce<NK>(k9, s_red, o9);
+    if (threadIdx.x == 0)
+        for (int j = 0; j < NK; j++) ksum[(size_t)b * NK + j] = o9[j];
 }
 
 // log-priors of n parameter vectors (rows of Np doubles): one thread each, the serial evaluation of priors_impl.h in double
@@ -173,6 +254,56 @@ int envelope_loglike_params_batch(tamcmc_hip_ctx *c, int model_id, int B, const 
     return TAMCMC_OK;
 }
 
+// The points of a gradient batch, C x (Nvars + 1) rows per block: forward points theta + h e_k (the same double addition the
+// gradient's divisor uses), then (backward) a second block with the backward points theta - h e_k
+static std::vector<double> env_fd_points(int C, const double *params, int64_t Nparams, const int32_t *index_to_relax, int Nvars,
+                                         const double *hstep, bool backward) {
+    const int E = Nvars + 1;
+    const size_t B = (size_t)C * E, Np = (size_t)Nparams;
+    std::vector<double> P((backward ? 2 : 1) * B * Np);
+    for (int ch = 0; ch < C; ch++)
+        for (int e = 0; e < E; e++) {
+            double *f = P.data() + ((size_t)ch * E + e) * Np;
+            std::memcpy(f, params + (size_t)ch * Np, Np * 8);
+            if (e > 0) f[index_to_relax[e - 1]] = params[(size_t)ch * Np + index_to_relax[e - 1]] + hstep[e - 1];
+            if (backward) {
+                double *g = P.data() + (B + (size_t)ch * E + e) * Np;
+                std::memcpy(g, params + (size_t)ch * Np, Np * 8);
+                if (e > 0) g[index_to_relax[e - 1]] = params[(size_t)ch * Np + index_to_relax[e - 1]] - hstep[e - 1];
+            }
+        }
+    return P;
+}
+
+// Log-priors of the 2B points of env_fd_points on the device (k_env_prior), behind whatever the stream holds; synchronises.  lp: 2B
+// values; *first_err: the first status that is not TAMCMC_OK
+static int env_prior_points(tamcmc_hip_ctx *c, int prior_class, size_t B, const double *P, int64_t Nparams, const double *priors,
+                            const int32_t *priors_switch, std::vector<double> &lp, int *first_err) {
+    hipStream_t st = c->stream;
+    const size_t Np = (size_t)Nparams;
+    // one block: [vectors 2B x Np | priors 4 x Np | switch Np (int) ] in, [lp 2B | status 2B (int)] out
+    const size_t nP = 2 * B * Np, o_pp = nP * 8, o_sw = o_pp + 4 * Np * 8, o_lp = (o_sw + Np * 4 + 15) & ~(size_t)15,
+                 o_st = o_lp + 2 * B * 8, bytes = o_st + 2 * B * 4;
+    HIPCHK(c, c->h_fd.reserve(bytes));
+    HIPCHK(c, c->d_fd.reserve(bytes));
+    unsigned char *hb = c->h_fd.p, *db = c->d_fd.p;
+    std::memcpy(hb, P, nP * 8);
+    std::memcpy(hb + o_pp, priors, 4 * Np * 8);
+    std::memcpy(hb + o_sw, priors_switch, Np * 4);
+    HIPCHK(c, hipMemcpyAsync(db, hb, o_lp, hipMemcpyHostToDevice, st));
+    const int n = (int)(2 * B);
+    hipLaunchKernelGGL(k_env_prior, dim3((n + 63) / 64), dim3(64), 0, st, prior_class, n, (const double *)db, (long)Np,
+                       (const double *)(db + o_pp), (const int *)(db + o_sw), (double *)(db + o_lp), (int *)(db + o_st));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(hb + o_lp, db + o_lp, bytes - o_lp, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    lp.assign((const double *)(hb + o_lp), (const double *)(hb + o_lp) + 2 * B);
+    const int *lst = (const int *)(hb + o_st);
+    for (size_t s = 0; s < 2 * B; s++)
+        if (lst[s] != TAMCMC_OK && *first_err == TAMCMC_OK) *first_err = lst[s];
+    return TAMCMC_OK;
+}
+
 int envelope_fd_run(tamcmc_hip_ctx *c, int model_id, bool with_prior, int prior_class, int C, const double *params, int64_t Nparams,
                     const int32_t *index_to_relax, int Nvars, const double *hstep, const double *Tcoefs, double p, const double *priors,
                     const int32_t *priors_switch, double *logL0, double *logPr0, double *grad, double *grad_prior) {
@@ -180,58 +311,156 @@ int envelope_fd_run(tamcmc_hip_ctx *c, int model_id, bool with_prior, int prior_
     if (rc) return rc;
     if (with_prior && prior_class != model_id) return TAMCMC_ERR_BAD_MODEL;  // priors_ctrl.list pairs class 0 with id 0, class 1 with id 1
     const int E = Nvars + 1;
-    const size_t B = (size_t)C * E, Np = (size_t)Nparams;
+    const size_t B = (size_t)C * E;
     if (B > 65535) return TAMCMC_ERR_BAD_ARG;  // grid.y
-    // forward points theta + h e_k (the same double addition the gradient's divisor uses), then the backward points theta - h e_k
-    std::vector<double> P((with_prior ? 2 : 1) * B * Np);
-    for (int ch = 0; ch < C; ch++)
-        for (int e = 0; e < E; e++) {
-            double *f = P.data() + ((size_t)ch * E + e) * Np;
-            std::memcpy(f, params + (size_t)ch * Np, Np * 8);
-            if (e > 0) f[index_to_relax[e - 1]] = params[(size_t)ch * Np + index_to_relax[e - 1]] + hstep[e - 1];
-            if (with_prior) {
-                double *g = P.data() + (B + (size_t)ch * E + e) * Np;
-                std::memcpy(g, params + (size_t)ch * Np, Np * 8);
-                if (e > 0) g[index_to_relax[e - 1]] = params[(size_t)ch * Np + index_to_relax[e - 1]] - hstep[e - 1];
-            }
-        }
+    const std::vector<double> P = env_fd_points(C, params, Nparams, index_to_relax, Nvars, hstep, with_prior);
     rc = envelope_enqueue(c, model_id, (int)B, P.data(), Nparams, nullptr);
     if (rc) return rc;
     hipStream_t st = c->stream;
     HIPCHK(c, c->h_S.reserve(B));
     HIPCHK(c, hipMemcpyAsync(c->h_S.p, c->d_S.p, B * sizeof(double), hipMemcpyDeviceToHost, st));
     std::vector<double> lp;
-    std::vector<int> lst;
+    int first_err = TAMCMC_OK;
     if (with_prior) {
-        // one block: [vectors 2B x Np | priors 4 x Np | switch Np (int) ] in, [lp 2B | status 2B (int)] out
-        const size_t nP = 2 * B * Np, o_pp = nP * 8, o_sw = o_pp + 4 * Np * 8, o_lp = (o_sw + Np * 4 + 15) & ~(size_t)15,
-                     o_st = o_lp + 2 * B * 8, bytes = o_st + 2 * B * 4;
-        HIPCHK(c, c->h_fd.reserve(bytes));
-        HIPCHK(c, c->d_fd.reserve(bytes));
-        unsigned char *hb = c->h_fd.p, *db = c->d_fd.p;
-        std::memcpy(hb, P.data(), nP * 8);
-        std::memcpy(hb + o_pp, priors, 4 * Np * 8);
-        std::memcpy(hb + o_sw, priors_switch, Np * 4);
-        HIPCHK(c, hipMemcpyAsync(db, hb, o_lp, hipMemcpyHostToDevice, st));
-        const int n = (int)(2 * B);
-        hipLaunchKernelGGL(k_env_prior, dim3((n + 63) / 64), dim3(64), 0, st, prior_class, n, (const double *)db, (long)Np,
-                           (const double *)(db + o_pp), (const int *)(db + o_sw), (double *)(db + o_lp), (int *)(db + o_st));
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(hb + o_lp, db + o_lp, bytes - o_lp, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        lp.assign((const double *)(hb + o_lp), (const double *)(hb + o_lp) + 2 * B);
-        lst.assign((const int *)(hb + o_st), (const int *)(hb + o_st) + 2 * B);
+        if ((rc = env_prior_points(c, prior_class, B, P.data(), Nparams, priors, priors_switch, lp, &first_err))) return rc;
     } else {
         HIPCHK(c, hipStreamSynchronize(st));
     }
     rc = env_account(c, (int)B);
     if (rc) return rc;
-    int first_err = TAMCMC_OK;
-    for (size_t s = 0; s < lst.size(); s++)
-        if (lst[s] != TAMCMC_OK && first_err == TAMCMC_OK) first_err = lst[s];
     // same combination as the Lorentzian batches (no status per evaluation: these models have no table that can fail)
     assemble_gradient(C, Nvars, params, Nparams, index_to_relax, hstep, Tcoefs, p, c->h_S.p, false, with_prior ? lp.data() : nullptr,
                       lp.data() + B, nullptr, logL0, logPr0, grad, grad_prior);
+    return first_err;
+}
+
+// The analytic route's kernels for C vectors: S (C), the folded tile sums (C x 16) and xi sums (C x 12) in one block of d_envg
+static int envelope_grad_enqueue(tamcmc_hip_ctx *c, int model_id, int C, const double *params, int64_t Nparams, const EnvRow **host_rows,
+                                 const double **folded_dev) {
+    const int Nx = (int)c->Nx;
+    const int ntiles = (Nx + ETILE - 1) / ETILE, nchunk = (Nx + ECHUNK - 1) / ECHUNK;
+    const bool kal = model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN;
+    const int NG = env_grad_nraw(model_id);
+    const size_t row_bytes = (size_t)C * sizeof(EnvRow);
+    // d_envg: [S C | folded C x (16 + 12) | tile partials C x ntiles x NG | chunk partials C x nchunk x 9]; S sits in front of the
+    // folded sums so that one copy brings both back
+    const size_t o_tile = (size_t)C * (1 + ENV_GRAD_NRAWMAX + ENV_GRAD_NKRAW), o_chunk = o_tile + (size_t)C * ntiles * NG,
+                 total = o_chunk + (kal ? (size_t)C * nchunk * (ENV_GRAD_NKRAW - 3) : 0);
+    HIPCHK(c, c->h_stage.reserve(row_bytes));
+    HIPCHK(c, c->d_stage.reserve(row_bytes));
+    HIPCHK(c, c->d_part.reserve((size_t)C * ntiles * 2));
+    HIPCHK(c, c->d_envg.reserve(total));
+    EnvRow *hr = (EnvRow *)c->h_stage.p;
+    for (int b = 0; b < C; b++) env_row(model_id, params + (size_t)b * Nparams, hr[b]);
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(c->d_stage.p, c->h_stage.p, row_bytes, hipMemcpyHostToDevice, st));
+    const EnvRow *rows = (const EnvRow *)c->d_stage.p;
+    const double h = c->hx[1] - c->hx[0];
+    double *Sdev = c->d_envg.p, *gsum = Sdev + C, *ksum = gsum + (size_t)C * ENV_GRAD_NRAWMAX, *gtile = c->d_envg.p + o_tile, *gchunk = c->d_envg.p + o_chunk;
+    if (c->timing) HIPCHK(c, hipEventRecord(c->ev0, st));
+    const dim3 grid(ntiles, C);
+    if (kal) {
+        HIPCHK(c, c->d_env.reserve((size_t)C * nchunk * 3));
+        hipLaunchKernelGGL(k_env_ksi_grad, dim3(nchunk, C), dim3(EWG), 0, st, c->dlogx.p, Nx, nchunk, rows, c->d_env.p, gchunk);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL((k_env_grad<0>), grid, dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, Nx, ntiles, nchunk, h, c->xmax, rows, c->d_env.p, c->d_part.p, gtile);
+    } else {
+        hipLaunchKernelGGL((k_env_grad<1>), grid, dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, Nx, ntiles, nchunk, h, c->xmax, rows, nullptr, c->d_part.p, gtile);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (kal) hipLaunchKernelGGL((k_env_grad_fold<ENV_GRAD_NRAW0>), dim3(C), dim3(EWG), 0, st, c->d_part.p, gtile, ntiles, c->d_env.p, gchunk, nchunk, Sdev, gsum, ksum);
+    else hipLaunchKernelGGL((k_env_grad_fold<ENV_GRAD_NRAW1>), dim3(C), dim3(EWG), 0, st, c->d_part.p, gtile, ntiles, nullptr, nullptr, 0, Sdev, gsum, ksum);
+    HIPCHK(c, hipGetLastError());
+    if (c->timing) HIPCHK(c, hipEventRecord(c->ev1, st));
+    *host_rows = hr;
+    *folded_dev = Sdev;
+    return TAMCMC_OK;
+}
+
+// S and dS / d(row quantity) of C vectors, brought back: the long doubles every caller goes on from (dS: C x ENV_GRAD_N, ksi: C x 9).
+// Leaves the stream synchronised unless `more` (the caller has enqueued behind it and synchronises itself).
+static int envelope_grad_sums(tamcmc_hip_ctx *c, int model_id, int C, const double *params, int64_t Nparams, std::vector<double> &S,
+                              std::vector<long double> &dS, std::vector<long double> &ksi, const std::function<int()> &more) {
+    const EnvRow *hr = nullptr;
+    const double *folded = nullptr;
+    int rc = envelope_grad_enqueue(c, model_id, C, params, Nparams, &hr, &folded);
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    const size_t nf = (size_t)C * (ENV_GRAD_NRAWMAX + ENV_GRAD_NKRAW);
+    HIPCHK(c, c->h_S.reserve((size_t)C + nf));
+    HIPCHK(c, hipMemcpyAsync(c->h_S.p, folded, ((size_t)C + nf) * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (more) {
+        if ((rc = more())) return rc;
+    } else {
+        HIPCHK(c, hipStreamSynchronize(st));
+    }
+    if ((rc = env_account(c, C))) return rc;
+    const double h = c->hx[1] - c->hx[0];
+    const double *raw = c->h_S.p + C, *kraw = raw + (size_t)C * ENV_GRAD_NRAWMAX;
+    S.assign(c->h_S.p, c->h_S.p + C);
+    dS.assign((size_t)C * ENV_GRAD_N, 0.0L);
+    ksi.assign((size_t)C * ENV_GRAD_NKSI, 0.0L);
+    for (int b = 0; b < C; b++)
+        env_grad_rows(model_id, hr[b], h, raw + (size_t)b * ENV_GRAD_NRAWMAX, kraw + (size_t)b * ENV_GRAD_NKRAW, dS.data() + (size_t)b * ENV_GRAD_N,
+                      ksi.data() + (size_t)b * ENV_GRAD_NKSI);
+    return TAMCMC_OK;
+}
+
+int envelope_gradient_sums(tamcmc_hip_ctx *c, int model_id, int C, const double *params, int64_t Nparams, double *S, double *sums, double *ksi) {
+    int rc = env_check(c, model_id, Nparams);
+    if (rc) return rc;
+    if (C > 65535) return TAMCMC_ERR_BAD_ARG;  // grid.y
+    std::vector<double> Sv;
+    std::vector<long double> dS, ks;
+    if ((rc = envelope_grad_sums(c, model_id, C, params, Nparams, Sv, dS, ks, nullptr))) return rc;
+    for (int b = 0; b < C; b++) S[b] = Sv[(size_t)b];
+    for (size_t i = 0; i < dS.size(); i++) sums[i] = (double)dS[i];
+    if (ksi && model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN)
+        for (size_t i = 0; i < ks.size(); i++) ksi[i] = (double)ks[i];
+    return TAMCMC_OK;
+}
+
+int envelope_grad_run(tamcmc_hip_ctx *c, int model_id, bool with_prior, int prior_class, int C, const double *params, int64_t Nparams,
+                      const int32_t *index_to_relax, int Nvars, const double *hstep, const double *Tcoefs, double p, const double *priors,
+                      const int32_t *priors_switch, double *logL0, double *logPr0, double *grad, double *grad_prior) {
+    int rc = env_check(c, model_id, Nparams);
+    if (rc) return rc;
+    if (with_prior && prior_class != model_id) return TAMCMC_ERR_BAD_MODEL;
+    const int E = Nvars + 1;
+    const size_t B = (size_t)C * E, Np = (size_t)Nparams, Nv = (size_t)Nvars;
+    if (B > 65535) return TAMCMC_ERR_BAD_ARG;  // (the limit of the default route, whose points the prior keeps)
+    std::vector<double> S, lp;
+    std::vector<long double> dS, ks;
+    int first_err = TAMCMC_OK;
+    // the prior's share: today's forward / backward points through k_env_prior, behind the likelihood's kernels on the same stream
+    std::function<int()> prior;
+    std::vector<double> P;
+    if (with_prior) {
+        P = env_fd_points(C, params, Nparams, index_to_relax, Nvars, hstep, true);
+        prior = [&]() { return env_prior_points(c, prior_class, B, P.data(), Nparams, priors, priors_switch, lp, &first_err); };
+    }
+    if ((rc = envelope_grad_sums(c, model_id, C, params, Nparams, S, dS, ks, prior))) return rc;
+    // chain rule: dS/dtheta_j = sum_q dS/drow_q J[q][j]; logL = -(long)p S / T
+    const int NpJ = (int)envelope_nparams(model_id);
+    std::vector<long double> J((size_t)ENV_GRAD_N * NpJ);
+    std::vector<double> gL(Nv);
+    const long pl = (long)p;
+    for (int ch = 0; ch < C; ch++) {
+        env_row_jacobian(model_id, params + (size_t)ch * Np, J.data());
+        const double T = Tcoefs ? Tcoefs[ch] : 1.0;
+        for (int k = 0; k < Nvars; k++) {
+            const int j = index_to_relax[k];
+            long double s = 0.0L;
+            if (j < NpJ)
+                for (int q = 0; q < ENV_GRAD_N; q++) {
+                    const long double Jq = J[(size_t)q * NpJ + j];
+                    if (Jq != 0.0L) s += dS[(size_t)ch * ENV_GRAD_N + q] * Jq;  // (a parameter the model does not read: exactly 0)
+                }
+            gL[(size_t)k] = s == 0.0L ? 0.0 : (double)((-pl * s) / T);
+        }
+        assemble_gradient_analytic(ch, Nvars, params, Nparams, index_to_relax, hstep, Tcoefs, p, S[(size_t)ch], gL.data(),
+                                   with_prior ? lp.data() : nullptr, lp.data() + B, logL0, logPr0, grad, grad_prior);
+    }
     return first_err;
 }
 

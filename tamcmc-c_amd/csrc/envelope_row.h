@@ -89,6 +89,99 @@ TAMCMC_ENV_HD void env_row(int model_id, const double *p, EnvRow &R) {
     }
 }
 
+// ---- analytic gradient of S = sum_i (y_i/M_i + ln M_i) (TAMCMC_OPT_ENVELOPE_GRADIENT; conventions in include/tamcmc_hip.h) ----
+// The kernels sum r_i = 1/M_i - y_i/M_i^2 against what M's derivatives are made of, with L = 1/(1 + e^u), D = L (1 - L):
+//   tile pass   [sum r G, sum r G d, sum r G d^2, sum r, sum r L_q (NQ), sum r D_q (NQ), sum r D_q u_q (NQ); id 0: sum r L_k^2 (3)]
+//               G = g (id 1) / eta^2 g (id 0), d = x - numax; NQ = 2, u_q = lna_q + ln x (id 1); NQ = 3, u_q = ln x - ln b_q (id 0)
+//   xi pass     (id 0) [sum w L_k, sum w D_k, sum w D_k u_k, sum w L_k^2] (3 each)
+// A bin adds exactly 0 to the D and D u sums when D = 0 (a saturated term; a first bin at x = 0 is one) or when u is not finite.
+// The sums of L^2 serve dS/dln b_k alone.  dM/dln b_k = C_k c_k L (Lbar - L), Lbar = sum w L^2 / sum w L: written with D it is
+// c D - L I^b/I = c L ((1 - L) - (1 - Lbar)), which loses every digit where all of a spectrum's bins lie far above b_k (L << 1, a
+// two-bin spectrum does it); written with L^2 it loses them where all lie far below (L close to 1).  The host takes the form whose
+// terms are the smaller: L^2 where Lbar <= 1/2, D otherwise (env_grad_rows).
+constexpr int ENV_GRAD_NRAW0 = 16, ENV_GRAD_NRAW1 = 10;  // tile sums of id 0 / id 1 (after S's own two)
+constexpr int ENV_GRAD_NRAWMAX = 16;                     // stride of a vector's folded tile sums
+constexpr int ENV_GRAD_NKRAW = 12;                       // xi sums of id 0 as the device leaves them
+constexpr int ENV_GRAD_N = 13;                           // row quantities per vector: TAMCMC_ENVELOPE_GRAD_N
+constexpr int ENV_GRAD_NKSI = 9;                         // xi sums per vector: TAMCMC_ENVELOPE_KSI_N
+TAMCMC_ENV_HD int env_grad_nraw(int model_id) { return model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN ? ENV_GRAD_NRAW0 : ENV_GRAD_NRAW1; }
+
+// Folded sums of one vector -> dS / d(row quantity), in the order of tamcmc_hip_envelope_gradient_sums:
+//   id 1  [A, nu, sigma^2, N0, H_0, H_1, lna_0, lna_1, pw_0, pw_1, 0, 0, 0]
+//   id 0  [A, nu (the Gaussian's), sigma^2, N0, a_k^2 (3), ln b_k (3), c_k (3)]
+// and (id 0) the xi sums [I_k, I_k^b = c_k sum w D_k, I_k^c = -sum w D_k u_k] into ksi[9].  h: the trapezoid step x(1) - x(0).
+inline void env_grad_rows(int model_id, const EnvRow &R, double h, const double *raw, const double *kraw, long double *out, long double *ksi) {
+    for (int q = 0; q < ENV_GRAD_N; q++) out[q] = 0.0L;
+    const long double A = R.amp, s2 = R.sig2;
+    out[0] = raw[0];
+    out[1] = A * (long double)raw[1] / s2;
+    out[2] = A * (long double)raw[2] / (2.0L * s2 * s2);
+    out[3] = raw[3];
+    if (model_id == TAMCMC_MODEL_HARVEY_GAUSSIAN) {
+        for (int q = 0; q < 2; q++) {
+            if (!R.hon[q]) continue;  // a switched-off term: 0 in its three places
+            out[4 + q] = raw[4 + q];
+            out[6 + q] = -(long double)R.H[q] * (long double)R.pw[q] * (long double)raw[6 + q];
+            out[8 + q] = -(long double)R.H[q] * (long double)raw[8 + q];
+        }
+        return;
+    }
+    for (int k = 0; k < 3; k++) {
+        const long double I = kraw[k], Ib = (long double)R.c[k] * (long double)kraw[3 + k], Ic = -(long double)kraw[6 + k];
+        const long double hI = (long double)h * I, Ck = (long double)R.a2[k] / hI;
+        const long double rL = raw[4 + k], rD = raw[7 + k], rDu = raw[10 + k], rL2 = raw[13 + k];
+        const long double Kbar = (long double)kraw[3 + k] / I, Lbar = (long double)kraw[9 + k] / I;  // (Kbar + Lbar = 1)
+        out[4 + k] = rL / hI;
+        // the normalisation integral moves with b_k: c D - L I^b / I in whichever of its two forms keeps its digits ...
+        out[7 + k] = Ck * (long double)R.c[k] * (Lbar <= 0.5L ? rL * Lbar - rL2 : rD - rL * Kbar);
+        out[10 + k] = Ck * (-rDu - rL * Ic / I);                      // ... and with c_k
+        if (ksi) { ksi[k] = I; ksi[3 + k] = Ib; ksi[6 + k] = Ic; }
+    }
+}
+
+// d(row quantity) / d(parameter): J[q * Np + j], q in the order of env_grad_rows, j < Np = 10 (id 1) or 19 (id 0).  d|p|/dp =
+// copysign(1, p); d ln(1e-3 |tc|)/dtc = 1/tc (not finite at tc = 0, where the model is not continuous).  Long double.
+inline void env_row_jacobian(int model_id, const double *p, long double *J) {
+    const int Np = model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN ? 19 : 10;
+    for (int i = 0; i < ENV_GRAD_N * Np; i++) J[i] = 0.0L;
+    auto sgn = [](double v) { return (long double)std::copysign(1.0, v); };
+    auto at = [&](int q, int j) -> long double & { return J[q * Np + j]; };
+    if (model_id == TAMCMC_MODEL_HARVEY_GAUSSIAN) {
+        at(0, 7) = sgn(p[7]);
+        at(1, 8) = 1.0L;
+        at(2, 9) = 2.0L * (long double)p[9];
+        at(3, 6) = sgn(p[6]);
+        for (int q = 0; q < 2; q++) {
+            at(4 + q, 3 * q) = sgn(p[3 * q]);
+            at(6 + q, 3 * q + 1) = 1.0L / (long double)p[3 * q + 1];
+            at(8 + q, 3 * q + 2) = sgn(p[3 * q + 2]);
+        }
+        return;
+    }
+    const long double s15 = sgn(p[15]), nu = std::fabs((long double)p[15]), mu = p[17], nm = nu + mu, lnm = std::log(std::fabs(nm));
+    at(0, 14) = sgn(p[14]);
+    at(1, 15) = s15;
+    at(2, 16) = 2.0L * (long double)p[16];
+    at(3, 13) = sgn(p[13]);
+    // a_0^2 = (p0 nu^p1)^2
+    const long double p0 = p[0], p1 = p[1], nup = std::pow(nu, 2.0L * p1), a02 = p0 * p0 * nup;
+    at(4, 0) = 2.0L * p0 * nup;
+    at(4, 1) = a02 * 2.0L * std::log(nu);
+    at(4, 15) = a02 * 2.0L * p1 / nu * s15;
+    at(5, 5) = 2.0L * (long double)p[5];
+    at(6, 6) = 2.0L * (long double)p[6];
+    // ln b_k = ln|p_i| + p_j ln|nu + mu|
+    static const int bi[3] = {2, 7, 10}, bj[3] = {3, 8, 11}, ci[3] = {4, 9, 12};
+    for (int k = 0; k < 3; k++) {
+        const long double pj = p[bj[k]];
+        at(7 + k, bi[k]) = 1.0L / (long double)p[bi[k]];
+        at(7 + k, bj[k]) = lnm;
+        at(7 + k, 15) = pj / nm * s15;
+        at(7 + k, 17) = pj / nm;
+        at(10 + k, ci[k]) = sgn(p[ci[k]]);
+    }
+}
+
 #if defined(__HIPCC__)
 
 // t^p as the reference's pow(t, p) for t >= 0, from ln t: pow(t, 0) = 1 also at t = 0 (exp(0 * -inf) would be NaN)
@@ -203,6 +296,115 @@ __device__ __forceinline__ void env_tile(const double *x, const double *y, const
         }
     }
     env_block_reduce<2>(acc, s_red, out);
+}
+
+// D = L (1 - L) with L = 1 / (1 + e): below e = 1 as L (e L), which has no cancellation where L is close to 1
+__device__ __forceinline__ double env_logistic_slope(double L, double e) { return e < 1.0 ? L * (e * L) : L * (1.0 - L); }
+
+// One chunk of the xi pass with the sums the gradient needs (id 0): per k the trapezoid sums of L_k (the statements of env_ksi_chunk,
+// so the same bits), of D_k, of D_k (ln x - ln b_k) and of L_k^2; thread 0 gets them in out[]: [L (3), D (3), D u (3), L^2 (3)]
+__device__ __forceinline__ void env_ksi_grad_chunk(const double *logx, int Nx, int chunk, const EnvRow &R, double *s_red, double (&out)[12]) {
+    const double lnb[3] = {R.lnb[0], R.lnb[1], R.lnb[2]}, c[3] = {R.c[0], R.c[1], R.c[2]};
+    double s[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const int base = chunk * ECHUNK + threadIdx.x;
+#pragma unroll 2
+    for (int k = 0; k < EK1; k++) {
+        const int i = base + k * EWG;
+        if (i < Nx) {
+            const double lx = logx[i];
+            const double w = (i == 0 || i == Nx - 1) ? 0.5 : 1.0;
+#pragma unroll
+            for (int q = 0; q < 3; q++) {
+                const double u = lx - lnb[q];
+                const double e = pow_from_log(c[q], u);
+                const double L = 1.0 / (1.0 + e);
+                s[q] = s[q] + w * L;
+                s[9 + q] = s[9 + q] + w * (L * L);
+                const double D = env_logistic_slope(L, e);
+                if (D != 0.0 && isfinite(u)) {
+                    s[3 + q] = s[3 + q] + w * D;
+                    s[6 + q] = s[6 + q] + w * (D * u);
+                }
+            }
+        }
+    }
+    env_block_reduce<12>(s, s_red, out);
+}
+
+// env_tile with the gradient's sums: M by env_tile's statements (the two sums of S come out with the same bits), then r = (1 - y/M) / M
+// against the pieces of dM; thread 0 gets [sum y/M, sum ln M, the tile sums listed above] in out[]
+template <int KIND>
+__device__ __forceinline__ void env_grad_tile(const double *x, const double *y, const double *logx, int Nx, int tile, double xmax, const EnvRow &R,
+                                              const double *s_coef, double *s_red, double (&out)[2 + (KIND == 0 ? ENV_GRAD_NRAW0 : ENV_GRAD_NRAW1)]) {
+    constexpr int NQ = KIND == 0 ? 3 : 2, NA = 2 + (KIND == 0 ? ENV_GRAD_NRAW0 : ENV_GRAD_NRAW1);
+    const double amp = R.amp, numax = R.numax, sig2 = R.sig2, N0 = R.N0;
+    double acc[NA];
+#pragma unroll
+    for (int j = 0; j < NA; j++) acc[j] = 0.0;
+    const int base = tile * ETILE + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < EK; k++) {
+        const int i = base + k * EWG;
+        if (i < Nx) {
+            const double xi = x[i], yi = y[i], lx = logx[i];
+            const double d = xi - numax;
+            const double g = exp((-0.5 * (d * d)) / sig2);
+            double M, G = g, L[NQ], D[NQ], u[NQ];
+            if (KIND == 0) {
+                double eta2 = 1.0;
+                if (!(i == 0 && xi == 0.0)) {
+                    const double a = 0.5 * M_PI * xi / xmax;
+                    const double sn = sin(a) / a;
+                    eta2 = sn * sn;
+                }
+                G = eta2 * g;
+                M = (amp * eta2) * g;
+                M = M + N0;
+#pragma unroll
+                for (int q = 0; q < 3; q++) {
+                    u[q] = lx - R.lnb[q];
+                    const double e = pow_from_log(R.c[q], u[q]);
+                    L[q] = 1.0 / (e + 1.0);
+                    D[q] = env_logistic_slope(L[q], e);
+                    M = M + s_coef[q] * L[q];
+                }
+            } else {
+                M = amp * g;
+#pragma unroll
+                for (int q = 0; q < 2; q++) {
+                    L[q] = 0.0; D[q] = 0.0; u[q] = 0.0;
+                    if (R.hon[q]) {
+                        u[q] = R.lna[q] + lx;
+                        const double e = pow_from_log(R.pw[q], u[q]);
+                        L[q] = 1.0 / (e + 1.0);
+                        D[q] = env_logistic_slope(L[q], e);
+                        M = M + R.H[q] * L[q];
+                    }
+                }
+                M = M + N0;
+            }
+            const double t = yi / M;
+            acc[0] = acc[0] + t;
+            acc[1] = acc[1] + log(M);
+            const double r = (1.0 - t) * (1.0 / M);
+            const double rG = r * G;
+            acc[2] = acc[2] + rG;
+            acc[3] = acc[3] + rG * d;
+            acc[4] = acc[4] + rG * (d * d);
+            acc[5] = acc[5] + r;
+#pragma unroll
+            for (int q = 0; q < NQ; q++) {
+                acc[6 + q] = acc[6 + q] + r * L[q];
+                if (KIND == 0) acc[6 + 3 * NQ + q] = acc[6 + 3 * NQ + q] + r * (L[q] * L[q]);
+                if (D[q] != 0.0 && isfinite(u[q])) {
+                    const double rD = r * D[q];
+                    acc[6 + NQ + q] = acc[6 + NQ + q] + rD;
+                    acc[6 + 2 * NQ + q] = acc[6 + 2 * NQ + q] + rD * u[q];
+                }
+            }
+        }
+    }
+    env_block_reduce<NA>(acc, s_red, out);
 }
 
 #endif  // __HIPCC__

@@ -95,4 +95,11 @@ int assemble_gradient(int C, int Nvars, const double *params, int64_t Nparams, c
                       const double *Tcoefs, double p, const double *S, bool deltas, const double *lpp, const double *lpm, const int *status,
                       double *logL0, double *logPr0, double *grad, double *grad_prior);
 
+// Its sibling for a likelihood share that is a derivative, not a difference (the envelope fits' analytic route, envelope.hip), one chain
+// at a time: S the chain's sum, gL[k] = dlogL/dtheta_k already tempered; logL0 and the prior's share (lpp / lpm by slot of the
+// C x (Nvars + 1) layout, nullptr: no prior) exactly as assemble_gradient forms them.
+void assemble_gradient_analytic(int ch, int Nvars, const double *params, int64_t Nparams, const int32_t *index_to_relax, const double *hstep,
+                                const double *Tcoefs, double p, double S, const double *gL, const double *lpp, const double *lpm, double *logL0,
+                                double *logPr0, double *grad, double *grad_prior);
+
 }  // namespace tamcmc

@@ -715,6 +715,36 @@ int assemble_gradient(int C, int Nvars, const double *params, int64_t Nparams, c
     return first_err;
 }
 
+void assemble_gradient_analytic(int ch, int Nvars, const double *params, int64_t Nparams, const int32_t *index_to_relax, const double *hstep,
+                                const double *Tcoefs, double p, double S, const double *gL, const double *lpp, const double *lpm, double *logL0,
+                                double *logPr0, double *grad, double *grad_prior) {
+    const int E = Nvars + 1;
+    const size_t Np = (size_t)Nparams, Nv = (size_t)Nvars;
+    const long pl = (long)p;
+    const double T = Tcoefs ? Tcoefs[ch] : 1.0;
+    long double f = S;  // call_likelihood, as assemble_gradient scales a sum
+    f = -pl * f;
+    logL0[ch] = (double)(f / T);
+    const double pr0 = lpp ? lpp[(size_t)ch * E] : 0.0;
+    if (logPr0) logPr0[ch] = pr0;
+    for (int k = 0; k < Nvars; k++) {
+        double g = gL[k];
+        if (lpp) {  // the prior's share: assemble_gradient's statements on the same points
+            const double x0 = params[(size_t)ch * Np + index_to_relax[k]];
+            volatile double xp = x0 + hstep[k];
+            const double happ = xp - x0;
+            if (!std::isfinite(g)) g = 0.0;
+            const double prp = lpp[(size_t)ch * E + k + 1], prm = lpm[(size_t)ch * E + k + 1];
+            double gp;
+            if (std::isfinite(prp)) gp = (prp - pr0) / happ;
+            else gp = std::isfinite(prm) ? (pr0 - prm) / happ : 0.0;
+            g += gp;
+            if (grad_prior) grad_prior[(size_t)ch * Nv + k] = gp;
+        }
+        grad[(size_t)ch * Nv + k] = g;
+    }
+}
+
 }  // namespace tamcmc
 
 // STRICT keeps the reference's arithmetic for a red giant's scalar unpack too: long double on the host, exactly what
@@ -852,7 +882,8 @@ int tamcmc_hip_fd_gradient(tamcmc_hip_ctx *c, int model_id, int C, const double 
         const int rc = check_gradient_args(c, C, params, Nparams, nullptr, index_to_relax, Nvars, hstep, logL0 && grad, GA_VARS);
         if (rc || C == 0) return rc;
         HIPCHK(c, hipSetDevice(c->device));
-        return tamcmc::envelope_fd_run(c, model_id, false, 0, C, params, Nparams, index_to_relax, Nvars, hstep, Tcoefs, p, nullptr, nullptr,
+        const auto run = c->envelope_gradient ? tamcmc::envelope_grad_run : tamcmc::envelope_fd_run;  // (TAMCMC_OPT_ENVELOPE_GRADIENT)
+        return run(c, model_id, false, 0, C, params, Nparams, index_to_relax, Nvars, hstep, Tcoefs, p, nullptr, nullptr,
                                        logL0, nullptr, grad, nullptr);
     }
     return fd_run(c, model_id, 0, C, params, Nparams, plength, index_to_relax, Nvars, hstep, Tcoefs, p, nullptr, nullptr, nullptr,
@@ -873,12 +904,25 @@ int tamcmc_hip_fd_gradient_posterior(tamcmc_hip_ctx *c, int model_id, int prior_
         if (prior_class != 0 && prior_class != 1) return TAMCMC_ERR_BAD_MODEL;
         if (C == 0) return TAMCMC_OK;
         HIPCHK(c, hipSetDevice(c->device));
-        return tamcmc::envelope_fd_run(c, model_id, true, prior_class, C, params, Nparams, index_to_relax, Nvars, hstep, Tcoefs, p, priors,
+        const auto run = c->envelope_gradient ? tamcmc::envelope_grad_run : tamcmc::envelope_fd_run;
+        return run(c, model_id, true, prior_class, C, params, Nparams, index_to_relax, Nvars, hstep, Tcoefs, p, priors,
                                        priors_switch, logL0, logPr0, grad, grad_prior);
     }
     if (is_rgb_model(model_id) ? prior_class != 4 : (prior_class != 2 && prior_class != 3)) return TAMCMC_ERR_BAD_MODEL;  // io_asymptotic is the red giants' prior, and theirs only
     return fd_run(c, model_id, prior_class, C, params, Nparams, plength, index_to_relax, Nvars, hstep, Tcoefs, p, priors,
                   priors_switch, extra_priors, logL0, logPr0, grad, grad_prior);
+}
+
+// Audit entry of the envelope fits' analytic gradient (TAMCMC_OPT_ENVELOPE_GRADIENT): the row-space sums before the chain rule
+int tamcmc_hip_envelope_gradient_sums(tamcmc_hip_ctx *c, int model_id, int C, const double *params, int64_t Nparams, double *S, double *sums,
+                                      double *ksi) {
+    if (!c) return TAMCMC_ERR_BAD_ARG;
+    if (!tamcmc::is_envelope_model(model_id)) return TAMCMC_ERR_BAD_MODEL;
+    if (c->Nx <= 0) return TAMCMC_ERR_NO_SPECTRUM;
+    if (C < 0 || !params || !S || !sums) return TAMCMC_ERR_BAD_ARG;
+    if (C == 0) return TAMCMC_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return tamcmc::envelope_gradient_sums(c, model_id, C, params, Nparams, S, sums, ksi);
 }
 
 // Audit entry of the adjoint route: the batch with no perturbed vector (Nvars = 0) on Route::Adjoint, whatever the context's
