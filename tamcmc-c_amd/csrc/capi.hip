@@ -15,6 +15,7 @@
 #include "rgb_prestep.h"
 #include "mode_tables.h"
 #include "envelope.h"
+#include "grad_assemble.h"
 
 #include "ctx.h"
 
@@ -244,20 +245,8 @@ static int run_staged(tamcmc_hip_ctx *c, int B, const StageLayout &L, int noise_
                 (h[2] - h[0]) * 0.01, (h[3] - h[0]) * 0.01, (h[4] - h[0]) * 0.01, (h[5] - h[0]) * 0.01, (h[6] - h[0]) * 0.01);
     }
 #endif
-    if (c->timing) {
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        c->kernel_ms += ms;
-        c->launches += 1;
-        c->evals += B;
-    }
-    // call_likelihood (model_def.cpp:399-401): f = -p*(sum1+sum2) in long double, then / Tcoefs[m]
-    const long pl = (long)p;
-    for (int b = 0; b < B; b++) {
-        long double f = c->h_S.p[b];
-        f = -pl * f;
-        logL[b] = (double)(f / (Tcoefs ? Tcoefs[b] : 1.0));
-    }
+    if (int rc = account_kernel_time(c, B)) return rc;
+    for (int b = 0; b < B; b++) logL[b] = tamcmc::tempered_loglike(c->h_S.p[b], p, tamcmc::temperature_of(Tcoefs, b));
     return TAMCMC_OK;
 }
 

@@ -142,3 +142,15 @@ struct StageLayout {
             return TAMCMC_ERR_HIP;                                                            \
         }                                                                                     \
     } while (0)
+
+// Timing on: the likelihood launches a host entry bracketed with ev0 / ev1, into the totals of tamcmc_hip_get_kernel_stats -- their
+// device time, one launch, `evals` evaluations.  Call after the stream is synchronised.
+inline int account_kernel_time(tamcmc_hip_ctx *c, int64_t evals) {
+    if (!c->timing) return TAMCMC_OK;
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->kernel_ms += ms;
+    c->launches += 1;
+    c->evals += evals;
+    return TAMCMC_OK;
+}

@@ -3,7 +3,8 @@
 //                                         eta_squared_Kallinger2014 in noise_models.cpp:70-153
 //   model_Harvey_Gaussian (id 1)          tamcmc/sources/models.cpp (before model_Kallinger2014_Gaussian), harvey_like noise_models.cpp:15-39
 // Every bin of the fitted range depends on every parameter: no mode table, no window.  The host forms a few scalars per vector
-// (EnvRow); the device walks the bins.
+// (EnvRow); the device walks the bins.  These are envelope.hip's doors: two for evaluations (a batch of vectors; the sampler's rows
+// already on the device), one per C entry behind them.  What they share underneath is stated once in envelope.hip and envelope_row.h.
 #pragma once
 #include <stdint.h>
 
@@ -31,16 +32,13 @@ int envelope_stage_enqueue(tamcmc_hip_ctx *c, int model_id, int cnt, const void 
 int envelope_loglike_params_batch(tamcmc_hip_ctx *c, int model_id, int B, const double *params, int64_t Nparams, const double *Tcoefs,
                                   double p, double *logL, double *model, int32_t *status);
 
-// tamcmc_hip_fd_gradient(_posterior) for ids 0 and 1: brute force, C x (Nvars + 1) full evaluations in one batch; with_prior: the
-// log-priors of the forward and backward points (prior class 0 / 1, priors_impl.h) on the device, one thread per point
-int envelope_fd_run(tamcmc_hip_ctx *c, int model_id, bool with_prior, int prior_class, int C, const double *params, int64_t Nparams,
-                    const int32_t *index_to_relax, int Nvars, const double *hstep, const double *Tcoefs, double p, const double *priors,
-                    const int32_t *priors_switch, double *logL0, double *logPr0, double *grad, double *grad_prior);
-
-// The same two entries with TAMCMC_OPT_ENVELOPE_GRADIENT = 1: the likelihood's share from the analytic gradient, one pass over the bins
-// per chain (k_env_ksi_grad, k_env_grad, k_env_grad_fold; the chain rule from row quantities to parameters on the host in long double,
-// env_row_jacobian); the prior's share and logPr0 from the same forward / backward points as envelope_fd_run, through the same kernel
-int envelope_grad_run(tamcmc_hip_ctx *c, int model_id, bool with_prior, int prior_class, int C, const double *params, int64_t Nparams,
+// tamcmc_hip_fd_gradient (with_prior false) and tamcmc_hip_fd_gradient_posterior (true) for ids 0 and 1, from the entry's first line
+// on: the argument rules, the refusal under TAMCMC_GRADIENT_ADJOINT, the prior-class rule (class 0 with id 0, class 1 with id 1), and
+// the route -- TAMCMC_OPT_ENVELOPE_GRADIENT is read here and nowhere else.  The likelihood's share: C x (Nvars + 1) full evaluations in
+// one batch (option 0), or the analytic gradient, one pass over the bins per chain (k_env_ksi_grad, k_env_grad, k_env_grad_fold; the
+// chain rule from row quantities to parameters on the host in long double, env_row_jacobian).  The prior's share and logPr0 on either
+// route: the log-priors of the forward and backward points on the device, one thread per point (priors_impl.h)
+int envelope_gradient(tamcmc_hip_ctx *c, int model_id, bool with_prior, int prior_class, int C, const double *params, int64_t Nparams,
                       const int32_t *index_to_relax, int Nvars, const double *hstep, const double *Tcoefs, double p, const double *priors,
                       const int32_t *priors_switch, double *logL0, double *logPr0, double *grad, double *grad_prior);
 

@@ -14,8 +14,12 @@
 // The chunk and tile sizes depend on Nx only, never on B, and every sum runs in a fixed order: a vector's logL is bit-identical whatever
 // batch it sits in and whatever its position there.
 //
-// The bodies of the two passes and the row builder are in envelope_row.h: the device-resident sampler's one-launch step (k_env_step,
-// dev_env_step_impl.h) evaluates its tiles through the same statements.
+// Who owns what.  envelope_row.h: the row builder, the xi term, the bodies of the two passes (the model of a bin, twice); the
+// device-resident sampler's one-launch step (k_env_step, dev_env_step_impl.h) evaluates its tiles through the same bodies.  This file:
+// the kernels around those bodies, and on the host ONE staging of rows (env_stage_rows), ONE statement of the evaluation's launches
+// (env_launch_eval: the batch and the sampler's lockstep route both call it), ONE gradient run for the brute-force and the analytic
+// likelihood share (envelope_gradient_run) behind ONE front door for the two gradient entries (envelope_gradient).  The tempered
+// log-likelihood and the gradient's assembly are grad_assemble.h's, the timing totals ctx.h's (account_kernel_time).
 //
 // One arithmetic mode (TAMCMC_OPT_PRECISION does not apply): double, the reference's order of operations per bin except for the power laws
 // taken through exp/log and the trapezoid sums taken as a tree instead of a left-to-right loop.
@@ -23,7 +27,6 @@
 
 #include <cmath>
 #include <cstring>
-#include <functional>
 #include <vector>
 
 #include "../../include/tamcmc_hip.h"
@@ -31,6 +34,7 @@
 #include "envelope.h"
 #include "envelope_row.h"
 #include "fd_batch.h"
+#include "grad_assemble.h"
 #include "kernels.h"
 #include "priors_impl.h"
 
@@ -159,73 +163,79 @@ __global__ void __launch_bounds__(64) k_env_prior(int prior_class, int n, const 
     status[v] = st;
 }
 
+// Tiles and chunks of the resident spectrum (they depend on Nx only) and get_ksinorm's step
+struct EnvGeom {
+    int Nx, ntiles, nchunk;
+    double h;  // x(1) - x(0), whatever the rest of the grid does
+    explicit EnvGeom(const tamcmc_hip_ctx *c)
+        : Nx((int)c->Nx), ntiles((Nx + ETILE - 1) / ETILE), nchunk((Nx + ECHUNK - 1) / ECHUNK), h(c->hx[1] - c->hx[0]) {}
+};
+
+// THE staging of rows: n vectors -> EnvRow each (host: h_stage, which keeps them until the next staging) and their upload to d_stage
+// on the context stream.  Between the staging buffers' reservation and the upload it reserves what the kernels behind it write, the
+// tile partials (d_part, n x ntiles x 2) and the caller's `sums`: the order in which the entries have always reserved them.
+int env_stage_rows(tamcmc_hip_ctx *c, int model_id, int n, int ntiles, const double *params, int64_t Nparams, DevBuf<double> &sums,
+                   size_t nsums) {
+    const size_t row_bytes = (size_t)n * sizeof(EnvRow);
+    HIPCHK(c, c->h_stage.reserve(row_bytes));
+    HIPCHK(c, c->d_stage.reserve(row_bytes));
+    HIPCHK(c, c->d_part.reserve((size_t)n * ntiles * 2));
+    HIPCHK(c, sums.reserve(nsums));
+    EnvRow *hr = (EnvRow *)c->h_stage.p;
+    for (int b = 0; b < n; b++) env_row(model_id, params + (size_t)b * Nparams, hr[b]);
+    HIPCHK(c, hipMemcpyAsync(c->d_stage.p, c->h_stage.p, row_bytes, hipMemcpyHostToDevice, c->stream));
+    return TAMCMC_OK;
+}
+const EnvRow *staged_rows_host(const tamcmc_hip_ctx *c) { return (const EnvRow *)c->h_stage.p; }
+const EnvRow *staged_rows_dev(const tamcmc_hip_ctx *c) { return (const EnvRow *)c->d_stage.p; }
+
+// THE launches of the evaluation: k_env_ksi (id 0) into ksi_part, then k_env_eval for `cnt` rows into `partials` (and model_dev, if
+// any).  check_each: the launch error is read after k_env_ksi too (the batch); otherwise once, after both (the sampler's lockstep route)
+int env_launch_eval(tamcmc_hip_ctx *c, int model_id, int cnt, const EnvRow *rows, double *ksi_part, double *model_dev, double *partials,
+                    hipStream_t st, bool check_each) {
+    const EnvGeom g(c);
+    const bool kal = model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN;
+    if (kal) {
+        hipLaunchKernelGGL(k_env_ksi, dim3(g.nchunk, cnt), dim3(EWG), 0, st, c->dlogx.p, g.Nx, g.nchunk, rows, ksi_part);
+        if (check_each) HIPCHK(c, hipGetLastError());
+    }
+    const auto eval = kal ? (model_dev ? k_env_eval<0, true> : k_env_eval<0, false>) : (model_dev ? k_env_eval<1, true> : k_env_eval<1, false>);
+    hipLaunchKernelGGL(eval, dim3(g.ntiles, cnt), dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, g.Nx, g.ntiles, g.nchunk, g.h, c->xmax, rows,
+                       kal ? ksi_part : nullptr, model_dev, partials);
+    HIPCHK(c, hipGetLastError());
+    return TAMCMC_OK;
+}
+
+// the copy of n sums (d_S) behind the kernels
+int env_fetch_sums(tamcmc_hip_ctx *c, const double *dev, size_t n) {
+    HIPCHK(c, c->h_S.reserve(n));
+    HIPCHK(c, hipMemcpyAsync(c->h_S.p, dev, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return TAMCMC_OK;
+}
+
+int env_check(tamcmc_hip_ctx *c, int model_id, int64_t Nparams) {
+    if (Nparams < envelope_nparams(model_id)) return TAMCMC_ERR_BAD_ARG;
+    if (c->Nx > 0x7fffffff / 2) return TAMCMC_ERR_BAD_ARG;
+    return TAMCMC_OK;
+}
+
 }  // namespace
 
 int envelope_enqueue(tamcmc_hip_ctx *c, int model_id, int B, const double *params, int64_t Nparams, double *model_dev) {
-    const int Nx = (int)c->Nx;
-    const int ntiles = (Nx + ETILE - 1) / ETILE, nchunk = (Nx + ECHUNK - 1) / ECHUNK;
-    const size_t row_bytes = (size_t)B * sizeof(EnvRow);
-    HIPCHK(c, c->h_stage.reserve(row_bytes));
-    HIPCHK(c, c->d_stage.reserve(row_bytes));
-    HIPCHK(c, c->d_part.reserve((size_t)B * ntiles * 2));
-    HIPCHK(c, c->d_S.reserve((size_t)B));
-    EnvRow *hr = (EnvRow *)c->h_stage.p;
-    for (int b = 0; b < B; b++) env_row(model_id, params + (size_t)b * Nparams, hr[b]);
+    const EnvGeom g(c);
+    if (int rc = env_stage_rows(c, model_id, B, g.ntiles, params, Nparams, c->d_S, (size_t)B)) return rc;
     hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(c->d_stage.p, c->h_stage.p, row_bytes, hipMemcpyHostToDevice, st));
-    const EnvRow *rows = (const EnvRow *)c->d_stage.p;
-    const double h = c->hx[1] - c->hx[0];  // get_ksinorm's step: x(1) - x(0), whatever the rest of the grid does
     if (c->timing) HIPCHK(c, hipEventRecord(c->ev0, st));
-    if (model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN) {
-        HIPCHK(c, c->d_env.reserve((size_t)B * nchunk * 3));
-        hipLaunchKernelGGL(k_env_ksi, dim3(nchunk, B), dim3(EWG), 0, st, c->dlogx.p, Nx, nchunk, rows, c->d_env.p);
-        HIPCHK(c, hipGetLastError());
-    }
-    const dim3 grid(ntiles, B);
-    if (model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN) {
-        if (model_dev) hipLaunchKernelGGL((k_env_eval<0, true>), grid, dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, Nx, ntiles, nchunk, h, c->xmax, rows, c->d_env.p, model_dev, c->d_part.p);
-        else hipLaunchKernelGGL((k_env_eval<0, false>), grid, dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, Nx, ntiles, nchunk, h, c->xmax, rows, c->d_env.p, model_dev, c->d_part.p);
-    } else {
-        if (model_dev) hipLaunchKernelGGL((k_env_eval<1, true>), grid, dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, Nx, ntiles, nchunk, h, c->xmax, rows, nullptr, model_dev, c->d_part.p);
-        else hipLaunchKernelGGL((k_env_eval<1, false>), grid, dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, Nx, ntiles, nchunk, h, c->xmax, rows, nullptr, model_dev, c->d_part.p);
-    }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, launch_finalize(c->d_part.p, B, ntiles, c->d_S.p, st));
+    if (model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN) HIPCHK(c, c->d_env.reserve((size_t)B * g.nchunk * 3));
+    if (int rc = env_launch_eval(c, model_id, B, staged_rows_dev(c), c->d_env.p, model_dev, c->d_part.p, st, true)) return rc;
+    HIPCHK(c, launch_finalize(c->d_part.p, B, g.ntiles, c->d_S.p, st));
     if (c->timing) HIPCHK(c, hipEventRecord(c->ev1, st));
     return TAMCMC_OK;
 }
 
 // The sampler's lockstep route: the rows are on the device already (written by k_iterate), one per chain
 int envelope_stage_enqueue(tamcmc_hip_ctx *c, int model_id, int cnt, const void *rows_dev, double *ksi_part, double *partials, hipStream_t st) {
-    const int Nx = (int)c->Nx;
-    const int ntiles = (Nx + ETILE - 1) / ETILE, nchunk = (Nx + ECHUNK - 1) / ECHUNK;
-    const EnvRow *rows = (const EnvRow *)rows_dev;
-    const double h = c->hx[1] - c->hx[0];
-    const dim3 grid(ntiles, cnt);
-    if (model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN) {
-        hipLaunchKernelGGL(k_env_ksi, dim3(nchunk, cnt), dim3(EWG), 0, st, c->dlogx.p, Nx, nchunk, rows, ksi_part);
-        hipLaunchKernelGGL((k_env_eval<0, false>), grid, dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, Nx, ntiles, nchunk, h, c->xmax, rows, ksi_part, nullptr, partials);
-    } else {
-        hipLaunchKernelGGL((k_env_eval<1, false>), grid, dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, Nx, ntiles, nchunk, h, c->xmax, rows, nullptr, nullptr, partials);
-    }
-    HIPCHK(c, hipGetLastError());
-    return TAMCMC_OK;
-}
-
-static int env_check(tamcmc_hip_ctx *c, int model_id, int64_t Nparams) {
-    if (Nparams < envelope_nparams(model_id)) return TAMCMC_ERR_BAD_ARG;
-    if (c->Nx > 0x7fffffff / 2) return TAMCMC_ERR_BAD_ARG;
-    return TAMCMC_OK;
-}
-
-static int env_account(tamcmc_hip_ctx *c, int B) {
-    if (!c->timing) return TAMCMC_OK;
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    c->kernel_ms += ms;
-    c->launches += 1;
-    c->evals += B;
-    return TAMCMC_OK;
+    return env_launch_eval(c, model_id, cnt, (const EnvRow *)rows_dev, ksi_part, nullptr, partials, st, false);
 }
 
 int envelope_loglike_params_batch(tamcmc_hip_ctx *c, int model_id, int B, const double *params, int64_t Nparams, const double *Tcoefs,
@@ -237,18 +247,12 @@ int envelope_loglike_params_batch(tamcmc_hip_ctx *c, int model_id, int B, const 
     rc = envelope_enqueue(c, model_id, B, params, Nparams, model ? c->d_model.p : nullptr);
     if (rc) return rc;
     hipStream_t st = c->stream;
-    HIPCHK(c, c->h_S.reserve((size_t)B));
-    HIPCHK(c, hipMemcpyAsync(c->h_S.p, c->d_S.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+    if ((rc = env_fetch_sums(c, c->d_S.p, (size_t)B))) return rc;
     if (model) HIPCHK(c, hipMemcpyAsync(model, c->d_model.p, (size_t)B * Nx * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    rc = env_account(c, B);
-    if (rc) return rc;
-    // call_likelihood (model_def.cpp:399-401): f = -p*(sum1+sum2) in long double, then / Tcoefs[m]
-    const long pl = (long)p;
+    if ((rc = account_kernel_time(c, B))) return rc;
     for (int b = 0; b < B; b++) {
-        long double f = c->h_S.p[b];
-        f = -pl * f;
-        logL[b] = (double)(f / (Tcoefs ? Tcoefs[b] : 1.0));
+        logL[b] = tempered_loglike(c->h_S.p[b], p, temperature_of(Tcoefs, b));
         if (status) status[b] = TAMCMC_OK;  // these models have no table that can fail: a non-finite vector gives a non-finite logL
     }
     return TAMCMC_OK;
@@ -304,164 +308,142 @@ static int env_prior_points(tamcmc_hip_ctx *c, int prior_class, size_t B, const 
     return TAMCMC_OK;
 }
 
-int envelope_fd_run(tamcmc_hip_ctx *c, int model_id, bool with_prior, int prior_class, int C, const double *params, int64_t Nparams,
-                    const int32_t *index_to_relax, int Nvars, const double *hstep, const double *Tcoefs, double p, const double *priors,
-                    const int32_t *priors_switch, double *logL0, double *logPr0, double *grad, double *grad_prior) {
-    int rc = env_check(c, model_id, Nparams);
-    if (rc) return rc;
-    if (with_prior && prior_class != model_id) return TAMCMC_ERR_BAD_MODEL;  // priors_ctrl.list pairs class 0 with id 0, class 1 with id 1
-    const int E = Nvars + 1;
-    const size_t B = (size_t)C * E;
-    if (B > 65535) return TAMCMC_ERR_BAD_ARG;  // grid.y
-    const std::vector<double> P = env_fd_points(C, params, Nparams, index_to_relax, Nvars, hstep, with_prior);
-    rc = envelope_enqueue(c, model_id, (int)B, P.data(), Nparams, nullptr);
-    if (rc) return rc;
-    hipStream_t st = c->stream;
-    HIPCHK(c, c->h_S.reserve(B));
-    HIPCHK(c, hipMemcpyAsync(c->h_S.p, c->d_S.p, B * sizeof(double), hipMemcpyDeviceToHost, st));
-    std::vector<double> lp;
-    int first_err = TAMCMC_OK;
-    if (with_prior) {
-        if ((rc = env_prior_points(c, prior_class, B, P.data(), Nparams, priors, priors_switch, lp, &first_err))) return rc;
-    } else {
-        HIPCHK(c, hipStreamSynchronize(st));
-    }
-    rc = env_account(c, (int)B);
-    if (rc) return rc;
-    // same combination as the Lorentzian batches (no status per evaluation: these models have no table that can fail)
-    assemble_gradient(C, Nvars, params, Nparams, index_to_relax, hstep, Tcoefs, p, c->h_S.p, false, with_prior ? lp.data() : nullptr,
-                      lp.data() + B, nullptr, logL0, logPr0, grad, grad_prior);
-    return first_err;
-}
-
-// The analytic route's kernels for C vectors: S (C), the folded tile sums (C x 16) and xi sums (C x 12) in one block of d_envg
-static int envelope_grad_enqueue(tamcmc_hip_ctx *c, int model_id, int C, const double *params, int64_t Nparams, const EnvRow **host_rows,
-                                 const double **folded_dev) {
-    const int Nx = (int)c->Nx;
-    const int ntiles = (Nx + ETILE - 1) / ETILE, nchunk = (Nx + ECHUNK - 1) / ECHUNK;
+// The analytic route's kernels for C vectors and the copy of what they fold: S (C), the tile sums (C x 16) and the xi sums (C x 12),
+// one block of d_envg and then of h_S
+static int envelope_grad_enqueue(tamcmc_hip_ctx *c, int model_id, int C, const double *params, int64_t Nparams) {
+    const EnvGeom g(c);
     const bool kal = model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN;
     const int NG = env_grad_nraw(model_id);
-    const size_t row_bytes = (size_t)C * sizeof(EnvRow);
     // d_envg: [S C | folded C x (16 + 12) | tile partials C x ntiles x NG | chunk partials C x nchunk x 9]; S sits in front of the
     // folded sums so that one copy brings both back
-    const size_t o_tile = (size_t)C * (1 + ENV_GRAD_NRAWMAX + ENV_GRAD_NKRAW), o_chunk = o_tile + (size_t)C * ntiles * NG,
-                 total = o_chunk + (kal ? (size_t)C * nchunk * (ENV_GRAD_NKRAW - 3) : 0);
-    HIPCHK(c, c->h_stage.reserve(row_bytes));
-    HIPCHK(c, c->d_stage.reserve(row_bytes));
-    HIPCHK(c, c->d_part.reserve((size_t)C * ntiles * 2));
-    HIPCHK(c, c->d_envg.reserve(total));
-    EnvRow *hr = (EnvRow *)c->h_stage.p;
-    for (int b = 0; b < C; b++) env_row(model_id, params + (size_t)b * Nparams, hr[b]);
+    const size_t o_tile = (size_t)C * (1 + ENV_GRAD_NRAWMAX + ENV_GRAD_NKRAW), o_chunk = o_tile + (size_t)C * g.ntiles * NG,
+                 total = o_chunk + (kal ? (size_t)C * g.nchunk * (ENV_GRAD_NKRAW - 3) : 0);
+    if (int rc = env_stage_rows(c, model_id, C, g.ntiles, params, Nparams, c->d_envg, total)) return rc;
     hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(c->d_stage.p, c->h_stage.p, row_bytes, hipMemcpyHostToDevice, st));
-    const EnvRow *rows = (const EnvRow *)c->d_stage.p;
-    const double h = c->hx[1] - c->hx[0];
+    const EnvRow *rows = staged_rows_dev(c);
     double *Sdev = c->d_envg.p, *gsum = Sdev + C, *ksum = gsum + (size_t)C * ENV_GRAD_NRAWMAX, *gtile = c->d_envg.p + o_tile, *gchunk = c->d_envg.p + o_chunk;
     if (c->timing) HIPCHK(c, hipEventRecord(c->ev0, st));
-    const dim3 grid(ntiles, C);
+    const dim3 grid(g.ntiles, C);
     if (kal) {
-        HIPCHK(c, c->d_env.reserve((size_t)C * nchunk * 3));
-        hipLaunchKernelGGL(k_env_ksi_grad, dim3(nchunk, C), dim3(EWG), 0, st, c->dlogx.p, Nx, nchunk, rows, c->d_env.p, gchunk);
+        HIPCHK(c, c->d_env.reserve((size_t)C * g.nchunk * 3));
+        hipLaunchKernelGGL(k_env_ksi_grad, dim3(g.nchunk, C), dim3(EWG), 0, st, c->dlogx.p, g.Nx, g.nchunk, rows, c->d_env.p, gchunk);
         HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL((k_env_grad<0>), grid, dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, Nx, ntiles, nchunk, h, c->xmax, rows, c->d_env.p, c->d_part.p, gtile);
+        hipLaunchKernelGGL((k_env_grad<0>), grid, dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, g.Nx, g.ntiles, g.nchunk, g.h, c->xmax, rows, c->d_env.p, c->d_part.p, gtile);
     } else {
-        hipLaunchKernelGGL((k_env_grad<1>), grid, dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, Nx, ntiles, nchunk, h, c->xmax, rows, nullptr, c->d_part.p, gtile);
+        hipLaunchKernelGGL((k_env_grad<1>), grid, dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, g.Nx, g.ntiles, g.nchunk, g.h, c->xmax, rows, nullptr, c->d_part.p, gtile);
     }
     HIPCHK(c, hipGetLastError());
-    if (kal) hipLaunchKernelGGL((k_env_grad_fold<ENV_GRAD_NRAW0>), dim3(C), dim3(EWG), 0, st, c->d_part.p, gtile, ntiles, c->d_env.p, gchunk, nchunk, Sdev, gsum, ksum);
-    else hipLaunchKernelGGL((k_env_grad_fold<ENV_GRAD_NRAW1>), dim3(C), dim3(EWG), 0, st, c->d_part.p, gtile, ntiles, nullptr, nullptr, 0, Sdev, gsum, ksum);
+    if (kal) hipLaunchKernelGGL((k_env_grad_fold<ENV_GRAD_NRAW0>), dim3(C), dim3(EWG), 0, st, c->d_part.p, gtile, g.ntiles, c->d_env.p, gchunk, g.nchunk, Sdev, gsum, ksum);
+    else hipLaunchKernelGGL((k_env_grad_fold<ENV_GRAD_NRAW1>), dim3(C), dim3(EWG), 0, st, c->d_part.p, gtile, g.ntiles, nullptr, nullptr, 0, Sdev, gsum, ksum);
     HIPCHK(c, hipGetLastError());
     if (c->timing) HIPCHK(c, hipEventRecord(c->ev1, st));
-    *host_rows = hr;
-    *folded_dev = Sdev;
-    return TAMCMC_OK;
+    return env_fetch_sums(c, Sdev, (size_t)C * (1 + ENV_GRAD_NRAWMAX + ENV_GRAD_NKRAW));
 }
 
-// S and dS / d(row quantity) of C vectors, brought back: the long doubles every caller goes on from (dS: C x ENV_GRAD_N, ksi: C x 9).
-// Leaves the stream synchronised unless `more` (the caller has enqueued behind it and synchronises itself).
-static int envelope_grad_sums(tamcmc_hip_ctx *c, int model_id, int C, const double *params, int64_t Nparams, std::vector<double> &S,
-                              std::vector<long double> &dS, std::vector<long double> &ksi, const std::function<int()> &more) {
-    const EnvRow *hr = nullptr;
-    const double *folded = nullptr;
-    int rc = envelope_grad_enqueue(c, model_id, C, params, Nparams, &hr, &folded);
-    if (rc) return rc;
-    hipStream_t st = c->stream;
-    const size_t nf = (size_t)C * (ENV_GRAD_NRAWMAX + ENV_GRAD_NKRAW);
-    HIPCHK(c, c->h_S.reserve((size_t)C + nf));
-    HIPCHK(c, hipMemcpyAsync(c->h_S.p, folded, ((size_t)C + nf) * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (more) {
-        if ((rc = more())) return rc;
-    } else {
-        HIPCHK(c, hipStreamSynchronize(st));
-    }
-    if ((rc = env_account(c, C))) return rc;
-    const double h = c->hx[1] - c->hx[0];
+// What envelope_grad_enqueue brought back, once the stream is idle: S is h_S's first C values; dS / d(row quantity) (C x ENV_GRAD_N) and
+// the xi sums (C x 9) in long double, which every caller goes on from
+static void envelope_grad_unfold(const tamcmc_hip_ctx *c, int model_id, int C, std::vector<long double> &dS, std::vector<long double> &ksi) {
+    const double h = EnvGeom(c).h;
+    const EnvRow *hr = staged_rows_host(c);
     const double *raw = c->h_S.p + C, *kraw = raw + (size_t)C * ENV_GRAD_NRAWMAX;
-    S.assign(c->h_S.p, c->h_S.p + C);
     dS.assign((size_t)C * ENV_GRAD_N, 0.0L);
     ksi.assign((size_t)C * ENV_GRAD_NKSI, 0.0L);
     for (int b = 0; b < C; b++)
         env_grad_rows(model_id, hr[b], h, raw + (size_t)b * ENV_GRAD_NRAWMAX, kraw + (size_t)b * ENV_GRAD_NKRAW, dS.data() + (size_t)b * ENV_GRAD_N,
                       ksi.data() + (size_t)b * ENV_GRAD_NKSI);
-    return TAMCMC_OK;
 }
 
 int envelope_gradient_sums(tamcmc_hip_ctx *c, int model_id, int C, const double *params, int64_t Nparams, double *S, double *sums, double *ksi) {
     int rc = env_check(c, model_id, Nparams);
     if (rc) return rc;
     if (C > 65535) return TAMCMC_ERR_BAD_ARG;  // grid.y
-    std::vector<double> Sv;
+    if ((rc = envelope_grad_enqueue(c, model_id, C, params, Nparams))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((rc = account_kernel_time(c, C))) return rc;
     std::vector<long double> dS, ks;
-    if ((rc = envelope_grad_sums(c, model_id, C, params, Nparams, Sv, dS, ks, nullptr))) return rc;
-    for (int b = 0; b < C; b++) S[b] = Sv[(size_t)b];
+    envelope_grad_unfold(c, model_id, C, dS, ks);
+    for (int b = 0; b < C; b++) S[b] = c->h_S.p[b];
     for (size_t i = 0; i < dS.size(); i++) sums[i] = (double)dS[i];
     if (ksi && model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN)
         for (size_t i = 0; i < ks.size(); i++) ksi[i] = (double)ks[i];
     return TAMCMC_OK;
 }
 
-int envelope_grad_run(tamcmc_hip_ctx *c, int model_id, bool with_prior, int prior_class, int C, const double *params, int64_t Nparams,
-                      const int32_t *index_to_relax, int Nvars, const double *hstep, const double *Tcoefs, double p, const double *priors,
-                      const int32_t *priors_switch, double *logL0, double *logPr0, double *grad, double *grad_prior) {
-    int rc = env_check(c, model_id, Nparams);
-    if (rc) return rc;
-    if (with_prior && prior_class != model_id) return TAMCMC_ERR_BAD_MODEL;
-    const int E = Nvars + 1;
-    const size_t B = (size_t)C * E, Np = (size_t)Nparams, Nv = (size_t)Nvars;
-    if (B > 65535) return TAMCMC_ERR_BAD_ARG;  // (the limit of the default route, whose points the prior keeps)
-    std::vector<double> S, lp;
-    std::vector<long double> dS, ks;
-    int first_err = TAMCMC_OK;
-    // the prior's share: today's forward / backward points through k_env_prior, behind the likelihood's kernels on the same stream
-    std::function<int()> prior;
-    std::vector<double> P;
-    if (with_prior) {
-        P = env_fd_points(C, params, Nparams, index_to_relax, Nvars, hstep, true);
-        prior = [&]() { return env_prior_points(c, prior_class, B, P.data(), Nparams, priors, priors_switch, lp, &first_err); };
-    }
-    if ((rc = envelope_grad_sums(c, model_id, C, params, Nparams, S, dS, ks, prior))) return rc;
-    // chain rule: dS/dtheta_j = sum_q dS/drow_q J[q][j]; logL = -(long)p S / T
+// Chain rule of the analytic route: dS / d(row quantity) of C vectors -> dlogL / dtheta_k (C x Nvars), tempered, in long double
+static std::vector<double> envelope_chain_rule(int model_id, int C, const double *params, int64_t Nparams, const int32_t *index_to_relax, int Nvars,
+                                               const double *Tcoefs, double p, const std::vector<long double> &dS) {
     const int NpJ = (int)envelope_nparams(model_id);
     std::vector<long double> J((size_t)ENV_GRAD_N * NpJ);
-    std::vector<double> gL(Nv);
-    const long pl = (long)p;
+    std::vector<double> gL((size_t)C * Nvars);
     for (int ch = 0; ch < C; ch++) {
-        env_row_jacobian(model_id, params + (size_t)ch * Np, J.data());
-        const double T = Tcoefs ? Tcoefs[ch] : 1.0;
+        env_row_jacobian(model_id, params + (size_t)ch * Nparams, J.data());
         for (int k = 0; k < Nvars; k++) {
             const int j = index_to_relax[k];
-            long double s = 0.0L;
+            long double s = 0.0L;  // dS/dtheta_j = sum_q dS/drow_q J[q][j]
             if (j < NpJ)
                 for (int q = 0; q < ENV_GRAD_N; q++) {
                     const long double Jq = J[(size_t)q * NpJ + j];
                     if (Jq != 0.0L) s += dS[(size_t)ch * ENV_GRAD_N + q] * Jq;  // (a parameter the model does not read: exactly 0)
                 }
-            gL[(size_t)k] = s == 0.0L ? 0.0 : (double)((-pl * s) / T);
+            gL[(size_t)ch * Nvars + k] = s == 0.0L ? 0.0 : tempered_loglike(s, p, temperature_of(Tcoefs, ch));  // (+0, not -p * 0)
         }
-        assemble_gradient_analytic(ch, Nvars, params, Nparams, index_to_relax, hstep, Tcoefs, p, S[(size_t)ch], gL.data(),
-                                   with_prior ? lp.data() : nullptr, lp.data() + B, logL0, logPr0, grad, grad_prior);
     }
+    return gL;
+}
+
+// THE gradient run of ids 0 and 1.  Shared: the checks, the forward (and, with a prior, backward) points, the prior's share -- the
+// log-priors of those points on the device (k_env_prior, prior class 0 / 1 of priors_impl.h), one thread per point -- and the assembly.
+// The likelihood's share: brute force, the C x (Nvars + 1) forward points evaluated in one batch; or (analytic,
+// TAMCMC_OPT_ENVELOPE_GRADIENT = 1) one pass over the bins per chain and the chain rule on the host.  Stream order on either route:
+// the likelihood's kernels, the copy of their sums, the prior's upload / kernel / download, one synchronise.
+static int envelope_gradient_run(tamcmc_hip_ctx *c, int model_id, bool analytic, bool with_prior, int prior_class, int C, const double *params,
+                                 int64_t Nparams, const int32_t *index_to_relax, int Nvars, const double *hstep, const double *Tcoefs, double p,
+                                 const double *priors, const int32_t *priors_switch, double *logL0, double *logPr0, double *grad,
+                                 double *grad_prior) {
+    int rc = env_check(c, model_id, Nparams);
+    if (rc) return rc;
+    if (with_prior && prior_class != model_id) return TAMCMC_ERR_BAD_MODEL;  // priors_ctrl.list pairs class 0 with id 0, class 1 with id 1
+    const size_t B = (size_t)C * (Nvars + 1);
+    if (B > 65535) return TAMCMC_ERR_BAD_ARG;  // grid.y of the brute-force batch (the analytic route keeps the limit: the prior keeps the points)
+    std::vector<double> P;
+    if (!analytic || with_prior) P = env_fd_points(C, params, Nparams, index_to_relax, Nvars, hstep, with_prior);
+    if (analytic) rc = envelope_grad_enqueue(c, model_id, C, params, Nparams);
+    else if (!(rc = envelope_enqueue(c, model_id, (int)B, P.data(), Nparams, nullptr))) rc = env_fetch_sums(c, c->d_S.p, B);
+    if (rc) return rc;
+    std::vector<double> lp;
+    int first_err = TAMCMC_OK;
+    if (with_prior) {
+        if ((rc = env_prior_points(c, prior_class, B, P.data(), Nparams, priors, priors_switch, lp, &first_err))) return rc;
+    } else {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    if ((rc = account_kernel_time(c, analytic ? C : (int64_t)B))) return rc;
+    std::vector<double> gL;
+    if (analytic) {
+        std::vector<long double> dS, ks;
+        envelope_grad_unfold(c, model_id, C, dS, ks);
+        gL = envelope_chain_rule(model_id, C, params, Nparams, index_to_relax, Nvars, Tcoefs, p, dS);
+    }
+    // (no status per evaluation: these models have no table that can fail)
+    assemble_gradient(C, Nvars, params, Nparams, index_to_relax, hstep, Tcoefs, p, analytic ? LikelihoodShare::Derivative : LikelihoodShare::FullSums,
+                      c->h_S.p, analytic ? gL.data() : nullptr, with_prior ? lp.data() : nullptr, with_prior ? lp.data() + B : nullptr, nullptr,
+                      logL0, logPr0, grad, grad_prior);
     return first_err;
+}
+
+int envelope_gradient(tamcmc_hip_ctx *c, int model_id, bool with_prior, int prior_class, int C, const double *params, int64_t Nparams,
+                      const int32_t *index_to_relax, int Nvars, const double *hstep, const double *Tcoefs, double p, const double *priors,
+                      const int32_t *priors_switch, double *logL0, double *logPr0, double *grad, double *grad_prior) {
+    if (!c) return TAMCMC_ERR_BAD_ARG;
+    if (c->gradient == TAMCMC_GRADIENT_ADJOINT) return TAMCMC_ERR_BAD_MODEL;  // (no mode table: no table-space adjoint)
+    const int rc = check_gradient_args(c, C, params, Nparams, nullptr, index_to_relax, Nvars, hstep,
+                                       logL0 && grad && (!with_prior || (priors && priors_switch)), GA_VARS);
+    if (rc) return rc;
+    if (with_prior && prior_class != 0 && prior_class != 1) return TAMCMC_ERR_BAD_MODEL;
+    if (C == 0) return TAMCMC_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return envelope_gradient_run(c, model_id, c->envelope_gradient != 0, with_prior, prior_class, C, params, Nparams, index_to_relax, Nvars, hstep,
+                                 Tcoefs, p, priors, priors_switch, logL0, logPr0, grad, grad_prior);
 }
 
 }  // namespace tamcmc

@@ -2,6 +2,11 @@
 // device-resident sampler (dev_sampler.hip): the scalars formed once per parameter vector (EnvRow, env_row: one function for host and
 // device), the tile geometry, and the device bodies of the two passes over the bins.  A kernel that evaluates a tile through these
 // bodies gets the bits of k_env_ksi / k_env_eval: same statements, same reduction orders.
+// Who owns what.  The xi pass's term and weight are env_ksi_term / env_ksi_weight, which env_ksi_chunk (k_env_ksi, k_env_step) and
+// env_ksi_grad_chunk (k_env_ksi_grad) both sum.  The model of a bin still stands twice, in env_tile (k_env_eval, k_env_step) and in
+// env_grad_tile (k_env_grad), each naming the other: a shared statement was measured and did not hold the parent's speed.  The tile
+// and chunk bodies own their loops, their accumulators and the reduction (env_block_reduce); the kernels around them own grids and
+// partial layouts.
 #pragma once
 #include <stdint.h>
 
@@ -212,8 +217,24 @@ __device__ __forceinline__ void env_block_reduce(double (&v)[NV], double *s_red,
     }
 }
 
-// One chunk of get_ksinorm's three trapezoid sums (id 0): sum_i w_i / (1 + (x_i/b_k)^c_k), w = 1/2 on the first and last bin of the
-// spectrum; thread 0 gets them in out[]
+// L = 1 / (1 + t^c) at u = ln t, the xi pass's power-law term (env_ksi_term); e = t^c goes to a caller that wants the slope D too
+__device__ __forceinline__ double env_logistic(double c, double u, double &e) {
+    e = pow_from_log(c, u);
+    return 1.0 / (e + 1.0);
+}
+
+// D = L (1 - L) with L = 1 / (1 + e): below e = 1 as L (e L), which has no cancellation where L is close to 1
+__device__ __forceinline__ double env_logistic_slope(double L, double e) { return e < 1.0 ? L * (e * L) : L * (1.0 - L); }
+
+// THE xi term of get_ksinorm's trapezoid sums (id 0) at bin i: L = 1 / (1 + (x_i/b)^c) with u = ln x_i - ln b, and its weight w = 1/2
+// on the first and last bin of the spectrum.  env_ksi_chunk and env_ksi_grad_chunk both sum w L from here: the same bits.
+__device__ __forceinline__ double env_ksi_weight(int i, int Nx) { return (i == 0 || i == Nx - 1) ? 0.5 : 1.0; }
+__device__ __forceinline__ double env_ksi_term(double c, double lx, double lnb, double &u, double &e) {
+    u = lx - lnb;
+    return env_logistic(c, u, e);
+}
+
+// One chunk of get_ksinorm's three trapezoid sums (id 0): sum_i w_i L_i; thread 0 gets them in out[]
 __device__ __forceinline__ void env_ksi_chunk(const double *logx, int Nx, int chunk, const EnvRow &R, double *s_red, double (&out)[3]) {
     const double lnb0 = R.lnb[0], lnb1 = R.lnb[1], lnb2 = R.lnb[2], c0 = R.c[0], c1 = R.c[1], c2 = R.c[2];
     double s[3] = {0.0, 0.0, 0.0};
@@ -222,11 +243,11 @@ __device__ __forceinline__ void env_ksi_chunk(const double *logx, int Nx, int ch
     for (int k = 0; k < EK1; k++) {
         const int i = base + k * EWG;
         if (i < Nx) {
-            const double lx = logx[i];
-            const double w = (i == 0 || i == Nx - 1) ? 0.5 : 1.0;
-            s[0] = s[0] + w * (1.0 / (1.0 + pow_from_log(c0, lx - lnb0)));
-            s[1] = s[1] + w * (1.0 / (1.0 + pow_from_log(c1, lx - lnb1)));
-            s[2] = s[2] + w * (1.0 / (1.0 + pow_from_log(c2, lx - lnb2)));
+            const double lx = logx[i], w = env_ksi_weight(i, Nx);
+            double u, e;
+            s[0] = s[0] + w * env_ksi_term(c0, lx, lnb0, u, e);
+            s[1] = s[1] + w * env_ksi_term(c1, lx, lnb1, u, e);
+            s[2] = s[2] + w * env_ksi_term(c2, lx, lnb2, u, e);
         }
     }
     env_block_reduce<3>(s, s_red, out);
@@ -255,6 +276,10 @@ __device__ __forceinline__ void env_ksi_coef(const double *ksi_part, int nchunk,
     __syncthreads();
 }
 
+// The model of a bin is written twice, here and in env_grad_tile below: the two copies must stay equal statement for statement, for
+// include/tamcmc_hip.h promises that the analytic route's logL0 is the evaluation's bit for bit.  One shared per-bin function was
+// tried and measured: same bits, fewer instructions, but k_env_grad<1> came out 1 % slower at 10^6 bins and two
+// more rows missed the parent's spread, so each body keeps its own statements.
 // The model on one 1024-bin tile and the tile's sums of y/M and ln M (thread 0 gets them in out[]).  KIND: model id (0 Kallinger, 1
 // Harvey); model_row (WRITE_MODEL): the vector's row of Nx model values
 template <int KIND, bool WRITE_MODEL>
@@ -298,11 +323,8 @@ __device__ __forceinline__ void env_tile(const double *x, const double *y, const
     env_block_reduce<2>(acc, s_red, out);
 }
 
-// D = L (1 - L) with L = 1 / (1 + e): below e = 1 as L (e L), which has no cancellation where L is close to 1
-__device__ __forceinline__ double env_logistic_slope(double L, double e) { return e < 1.0 ? L * (e * L) : L * (1.0 - L); }
-
-// One chunk of the xi pass with the sums the gradient needs (id 0): per k the trapezoid sums of L_k (the statements of env_ksi_chunk,
-// so the same bits), of D_k, of D_k (ln x - ln b_k) and of L_k^2; thread 0 gets them in out[]: [L (3), D (3), D u (3), L^2 (3)]
+// One chunk of the xi pass with the sums the gradient needs (id 0): per k the trapezoid sums of L_k (env_ksi_term, as env_ksi_chunk
+// sums it), of D_k, of D_k (ln x - ln b_k) and of L_k^2; thread 0 gets them in out[]: [L (3), D (3), D u (3), L^2 (3)]
 __device__ __forceinline__ void env_ksi_grad_chunk(const double *logx, int Nx, int chunk, const EnvRow &R, double *s_red, double (&out)[12]) {
     const double lnb[3] = {R.lnb[0], R.lnb[1], R.lnb[2]}, c[3] = {R.c[0], R.c[1], R.c[2]};
     double s[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -311,13 +333,11 @@ __device__ __forceinline__ void env_ksi_grad_chunk(const double *logx, int Nx, i
     for (int k = 0; k < EK1; k++) {
         const int i = base + k * EWG;
         if (i < Nx) {
-            const double lx = logx[i];
-            const double w = (i == 0 || i == Nx - 1) ? 0.5 : 1.0;
+            const double lx = logx[i], w = env_ksi_weight(i, Nx);
 #pragma unroll
             for (int q = 0; q < 3; q++) {
-                const double u = lx - lnb[q];
-                const double e = pow_from_log(c[q], u);
-                const double L = 1.0 / (1.0 + e);
+                double u, e;
+                const double L = env_ksi_term(c[q], lx, lnb[q], u, e);
                 s[q] = s[q] + w * L;
                 s[9 + q] = s[9 + q] + w * (L * L);
                 const double D = env_logistic_slope(L, e);
@@ -331,7 +351,8 @@ __device__ __forceinline__ void env_ksi_grad_chunk(const double *logx, int Nx, i
     env_block_reduce<12>(s, s_red, out);
 }
 
-// env_tile with the gradient's sums: M by env_tile's statements (the two sums of S come out with the same bits), then r = (1 - y/M) / M
+// env_tile with the gradient's sums: M by env_tile's statements, kept equal to them by hand (see the note at env_tile; the two sums of
+// S come out with the same bits), then r = (1 - y/M) / M
 // against the pieces of dM; thread 0 gets [sum y/M, sum ln M, the tile sums listed above] in out[]
 template <int KIND>
 __device__ __forceinline__ void env_grad_tile(const double *x, const double *y, const double *logx, int Nx, int tile, double xmax, const EnvRow &R,

@@ -3,7 +3,9 @@
 // (tamcmc_hip_fd_gradient*, tamcmc_hip_adjoint_table, tamcmc_hip_fisher) and by the device-resident Langevin step (dev_sampler.hip: run_mala).
 // Who owns what: the head of the block -- the arrays a caller fills and reads back -- is fd_block.h's (FdBlockHead: offsets, stage(),
 // results()); the host entries go through begin() / finish() and never see an offset.  Everything behind the head (tables, delta tables,
-// adjoint workspace) is layout()'s and is read by fd_batch.hip alone.
+// adjoint workspace) is layout()'s and is read by fd_batch.hip alone.  What a finished batch's sums become -- logL0, logPr0, grad,
+// grad_prior -- is grad_assemble.h's (host only: assemble_gradient, tempered_loglike), shared with the envelope fits (envelope.hip), whose
+// two gradient entries fd_batch.hip hands to envelope_gradient() unread.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -87,19 +89,5 @@ struct FdBatch {
 enum : unsigned { GA_PLENGTH = 1, GA_VARS = 2, GA_FISHER = 4, GA_EMPTY_FIRST = 8 };
 int check_gradient_args(const tamcmc_hip_ctx *c, int C, const double *params, int64_t Nparams, const int32_t *plength,
                         const int32_t *index_to_relax, int Nvars, const double *hstep, bool rest_ok, unsigned rules);
-
-// Sums and log-priors of a finished batch -> logL0, logPr0, grad, grad_prior (host; the device's counterpart is mala_gradient,
-// dev_mala_impl.h).  S: B full sums, or (deltas) C base sums then B differences; lpp / lpm: log-priors at the forward / backward points by
-// slot (nullptr: no prior, logPr0 = 0); status by slot (nullptr: no evaluation can fail).  Returns the first status that is not TAMCMC_OK.
-int assemble_gradient(int C, int Nvars, const double *params, int64_t Nparams, const int32_t *index_to_relax, const double *hstep,
-                      const double *Tcoefs, double p, const double *S, bool deltas, const double *lpp, const double *lpm, const int *status,
-                      double *logL0, double *logPr0, double *grad, double *grad_prior);
-
-// Its sibling for a likelihood share that is a derivative, not a difference (the envelope fits' analytic route, envelope.hip), one chain
-// at a time: S the chain's sum, gL[k] = dlogL/dtheta_k already tempered; logL0 and the prior's share (lpp / lpm by slot of the
-// C x (Nvars + 1) layout, nullptr: no prior) exactly as assemble_gradient forms them.
-void assemble_gradient_analytic(int ch, int Nvars, const double *params, int64_t Nparams, const int32_t *index_to_relax, const double *hstep,
-                                const double *Tcoefs, double p, double S, const double *gL, const double *lpp, const double *lpm, double *logL0,
-                                double *logPr0, double *grad, double *grad_prior);
 
 }  // namespace tamcmc

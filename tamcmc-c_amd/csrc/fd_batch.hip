@@ -44,6 +44,7 @@
 #include "dev_unpack.h"
 #include "kernels.h"
 #include "fd_batch.h"
+#include "grad_assemble.h"
 #include "rgb_prestep.h"
 #include "rgb_front.h"
 #include "adjoint.h"
@@ -665,86 +666,6 @@ int check_gradient_args(const tamcmc_hip_ctx *c, int C, const double *params, in
     return TAMCMC_OK;
 }
 
-int assemble_gradient(int C, int Nvars, const double *params, int64_t Nparams, const int32_t *index_to_relax, const double *hstep,
-                      const double *Tcoefs, double p, const double *S, bool deltas, const double *lpp, const double *lpm, const int *status,
-                      double *logL0, double *logPr0, double *grad, double *grad_prior) {
-    const int E = Nvars + 1;
-    const size_t Np = (size_t)Nparams, Nv = (size_t)Nvars;
-    const long pl = (long)p;
-    int first_err = TAMCMC_OK;
-    for (int ch = 0; ch < C; ch++) {
-        const double T = Tcoefs ? Tcoefs[ch] : 1.0;
-        // call_likelihood (model_def.cpp:399-401): f = -p*(sum1+sum2) in long double, then / Tcoefs[m]
-        auto scaled = [&](double s) {
-            long double f = s;
-            f = -pl * f;
-            return (double)(f / T);
-        };
-        auto failed = [&](int e) {
-            const int st = status ? status[(size_t)ch * E + e] : TAMCMC_OK;
-            if (first_err == TAMCMC_OK) first_err = st;
-            return st != TAMCMC_OK;
-        };
-        // S of evaluation e: full sums (B of them) or base sum + difference (deltas)
-        const double L0 = failed(0) ? (double)NAN : scaled(deltas ? S[ch] : S[(size_t)ch * E]);
-        auto dlogL_of = [&](int e) {  // logL(theta + h e_k) - logL(theta)
-            if (failed(e)) return (double)NAN;
-            if (deltas) return scaled(S[(size_t)C + (size_t)ch * E + e]);
-            return scaled(S[(size_t)ch * E + e]) - L0;
-        };
-        logL0[ch] = L0;
-        const double pr0 = lpp ? lpp[(size_t)ch * E] : 0.0;
-        if (logPr0) logPr0[ch] = pr0;
-        for (int k = 0; k < Nvars; k++) {
-            const double x0 = params[(size_t)ch * Np + index_to_relax[k]];
-            volatile double xp = x0 + hstep[k];
-            const double happ = xp - x0;  // the step actually applied (the device adds the same two doubles)
-            double g = dlogL_of(k + 1) / happ;
-            if (lpp) {
-                if (!std::isfinite(g)) g = 0.0;
-                const double prp = lpp[(size_t)ch * E + k + 1], prm = lpm[(size_t)ch * E + k + 1];
-                double gp;
-                if (std::isfinite(prp)) gp = (prp - pr0) / happ;
-                else gp = std::isfinite(prm) ? (pr0 - prm) / happ : 0.0;  // forward point outside the support: backward, else flat
-                g += gp;
-                if (grad_prior) grad_prior[(size_t)ch * Nv + k] = gp;
-            }
-            grad[(size_t)ch * Nv + k] = g;
-        }
-    }
-    return first_err;
-}
-
-void assemble_gradient_analytic(int ch, int Nvars, const double *params, int64_t Nparams, const int32_t *index_to_relax, const double *hstep,
-                                const double *Tcoefs, double p, double S, const double *gL, const double *lpp, const double *lpm, double *logL0,
-                                double *logPr0, double *grad, double *grad_prior) {
-    const int E = Nvars + 1;
-    const size_t Np = (size_t)Nparams, Nv = (size_t)Nvars;
-    const long pl = (long)p;
-    const double T = Tcoefs ? Tcoefs[ch] : 1.0;
-    long double f = S;  // call_likelihood, as assemble_gradient scales a sum
-    f = -pl * f;
-    logL0[ch] = (double)(f / T);
-    const double pr0 = lpp ? lpp[(size_t)ch * E] : 0.0;
-    if (logPr0) logPr0[ch] = pr0;
-    for (int k = 0; k < Nvars; k++) {
-        double g = gL[k];
-        if (lpp) {  // the prior's share: assemble_gradient's statements on the same points
-            const double x0 = params[(size_t)ch * Np + index_to_relax[k]];
-            volatile double xp = x0 + hstep[k];
-            const double happ = xp - x0;
-            if (!std::isfinite(g)) g = 0.0;
-            const double prp = lpp[(size_t)ch * E + k + 1], prm = lpm[(size_t)ch * E + k + 1];
-            double gp;
-            if (std::isfinite(prp)) gp = (prp - pr0) / happ;
-            else gp = std::isfinite(prm) ? (pr0 - prm) / happ : 0.0;
-            g += gp;
-            if (grad_prior) grad_prior[(size_t)ch * Nv + k] = gp;
-        }
-        grad[(size_t)ch * Nv + k] = g;
-    }
-}
-
 }  // namespace tamcmc
 
 // STRICT keeps the reference's arithmetic for a red giant's scalar unpack too: long double on the host, exactly what
@@ -842,12 +763,8 @@ static int fd_run(tamcmc_hip_ctx *c, int model_id, int prior_class, int C, const
     HIPCHK(c, hipMemcpyAsync(c->h_S.p, c->d_S.p, nS * 8, hipMemcpyDeviceToHost, st));
     FdResults res;
     if ((rc = fb.finish(c, &res))) return rc;
+    if ((rc = account_kernel_time(c, fb.B))) return rc;
     if (c->timing) {
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        c->kernel_ms += ms;
-        c->launches += 1;
-        c->evals += fb.B;
         if (fb.route == FdBatch::Route::Windowed) {  // what the delta launch really touched (roofline bookkeeping of bench.py)
             long bins = 0, full = 0;
             HIPCHK(c, fb.delta_stats(db, &bins, &full));
@@ -858,6 +775,7 @@ static int fd_run(tamcmc_hip_ctx *c, int model_id, int prior_class, int C, const
         if (split) {
             static const int from[6] = {0, 1, 3, 4, 2, 5};  // tables, base launch, row pass, noise pass + fold, fallback delta, contraction
             for (int i = 0; i < 6; i++) {
+                float ms = 0;
                 HIPCHK(c, hipEventElapsedTime(&ms, split[from[i]], split[from[i] + 1]));
                 c->rgb_adj_ms[i] = ms;
             }
@@ -867,7 +785,8 @@ static int fd_run(tamcmc_hip_ctx *c, int model_id, int prior_class, int C, const
             c->rgb_adj_fallback += fall;
         }
     }
-    return assemble_gradient(C, Nvars, params, Nparams, index_to_relax, hstep, Tcoefs, p, c->h_S.p, fb.deltas(),
+    return assemble_gradient(C, Nvars, params, Nparams, index_to_relax, hstep, Tcoefs, p,
+                             fb.deltas() ? LikelihoodShare::Differences : LikelihoodShare::FullSums, c->h_S.p, nullptr,
                              prior_class != 0 ? res.lpp : nullptr, res.lpm, res.status, logL0, logPr0, grad, grad_prior);
 }
 
@@ -876,16 +795,9 @@ extern "C" {
 int tamcmc_hip_fd_gradient(tamcmc_hip_ctx *c, int model_id, int C, const double *params, int64_t Nparams,
                            const int32_t *plength, const int32_t *index_to_relax, int Nvars, const double *hstep,
                            const double *Tcoefs, double p, double *logL0, double *grad) {
-    if (tamcmc::is_envelope_model(model_id)) {  // every parameter moves every bin: Nvars + 1 full evaluations per chain, one batch
-        if (!c) return TAMCMC_ERR_BAD_ARG;
-        if (c->gradient == TAMCMC_GRADIENT_ADJOINT) return TAMCMC_ERR_BAD_MODEL;  // (no mode table: no table-space adjoint)
-        const int rc = check_gradient_args(c, C, params, Nparams, nullptr, index_to_relax, Nvars, hstep, logL0 && grad, GA_VARS);
-        if (rc || C == 0) return rc;
-        HIPCHK(c, hipSetDevice(c->device));
-        const auto run = c->envelope_gradient ? tamcmc::envelope_grad_run : tamcmc::envelope_fd_run;  // (TAMCMC_OPT_ENVELOPE_GRADIENT)
-        return run(c, model_id, false, 0, C, params, Nparams, index_to_relax, Nvars, hstep, Tcoefs, p, nullptr, nullptr,
-                                       logL0, nullptr, grad, nullptr);
-    }
+    if (tamcmc::is_envelope_model(model_id))  // every parameter moves every bin: no table, no window (envelope.hip)
+        return tamcmc::envelope_gradient(c, model_id, false, 0, C, params, Nparams, index_to_relax, Nvars, hstep, Tcoefs, p, nullptr, nullptr,
+                                         logL0, nullptr, grad, nullptr);
     return fd_run(c, model_id, 0, C, params, Nparams, plength, index_to_relax, Nvars, hstep, Tcoefs, p, nullptr, nullptr, nullptr,
                   logL0, nullptr, grad, nullptr);
 }
@@ -895,19 +807,9 @@ int tamcmc_hip_fd_gradient_posterior(tamcmc_hip_ctx *c, int model_id, int prior_
                                      const double *hstep, const double *Tcoefs, double p, const double *priors,
                                      const int32_t *priors_switch, const double *extra_priors, double *logL0, double *logPr0,
                                      double *grad, double *grad_prior) {
-    if (tamcmc::is_envelope_model(model_id)) {  // brute force, priors of classes 0 / 1 on the device (envelope.hip)
-        if (!c) return TAMCMC_ERR_BAD_ARG;
-        if (c->gradient == TAMCMC_GRADIENT_ADJOINT) return TAMCMC_ERR_BAD_MODEL;
-        const int rc = check_gradient_args(c, C, params, Nparams, nullptr, index_to_relax, Nvars, hstep, logL0 && grad && priors && priors_switch,
-                                           GA_VARS);
-        if (rc) return rc;
-        if (prior_class != 0 && prior_class != 1) return TAMCMC_ERR_BAD_MODEL;
-        if (C == 0) return TAMCMC_OK;
-        HIPCHK(c, hipSetDevice(c->device));
-        const auto run = c->envelope_gradient ? tamcmc::envelope_grad_run : tamcmc::envelope_fd_run;
-        return run(c, model_id, true, prior_class, C, params, Nparams, index_to_relax, Nvars, hstep, Tcoefs, p, priors,
-                                       priors_switch, logL0, logPr0, grad, grad_prior);
-    }
+    if (tamcmc::is_envelope_model(model_id))  // priors of classes 0 / 1 on the device (envelope.hip)
+        return tamcmc::envelope_gradient(c, model_id, true, prior_class, C, params, Nparams, index_to_relax, Nvars, hstep, Tcoefs, p, priors,
+                                         priors_switch, logL0, logPr0, grad, grad_prior);
     if (is_rgb_model(model_id) ? prior_class != 4 : (prior_class != 2 && prior_class != 3)) return TAMCMC_ERR_BAD_MODEL;  // io_asymptotic is the red giants' prior, and theirs only
     return fd_run(c, model_id, prior_class, C, params, Nparams, plength, index_to_relax, Nvars, hstep, Tcoefs, p, priors,
                   priors_switch, extra_priors, logL0, logPr0, grad, grad_prior);
