@@ -4,7 +4,8 @@
 //   fit_star <local|global|asymptotic|simple> <star.model> <star.data> <sampler.cfg> <errors.cfg> <output root> [slice index] [--seed-fisher]
 //
 //   --seed-fisher: before the learning phase, seed every chain's proposal covariance from the Fisher information at the starting point
-//                  (tamcmc_sampler_seed_proposal_fisher; off by default; the table models only)
+//                  (tamcmc_sampler_seed_proposal_fisher; off by default; the table models only -- for the red giants, ids 25 and 27,
+//                  the switch sets TAMCMC_OPT_RGB_FISHER itself)
 //
 //   simple: the Gaussian-envelope fits (model ids 0, 1) -- their `.model` does not name its model, the .cfg's !Modeling model_fct_name does
 //
@@ -128,6 +129,7 @@ int main(int argc, char **argv) {
     CHECK(tamcmc_sampler_create(&s, g_ctx, &sc), "sampler_create");
     // ---- learning, then the recorded samples (buffers of Nbuffer iterations appended to the output files)
     const int64_t n_learn = sc.n_Nt_learn > 0 ? Nt_learn[sc.n_Nt_learn - 1] : 0;
+    if (seed_fisher && red_giant) CHECK(tamcmc_hip_set_option(g_ctx, TAMCMC_OPT_RGB_FISHER, 1), "set_option (red-giant Fisher information)");
     if (seed_fisher) CHECK(tamcmc_sampler_seed_proposal_fisher(s, 0.0, nullptr), "seed_proposal_fisher");
     CHECK(tamcmc_sampler_run(s, n_learn, nullptr, nullptr), "sampler_run (learning)");
     const int32_t C = sc.Nchains;

@@ -162,6 +162,10 @@ extern "C" {
                                         sets the prior's forward and backward points and is not read by the likelihood's share.
                                         TAMCMC_GRADIENT_ADJOINT keeps refusing these ids, and the device-resident engine keeps refusing
                                         use_drift = 1 for them.  Any other value: TAMCMC_ERR_BAD_ARG */
+#define TAMCMC_OPT_RGB_FISHER 16     /* value: 0/1 (default 0) -- 1: tamcmc_hip_fisher (and with it tamcmc_sampler_seed_proposal_fisher) accepts the
+                                        red-giant models, ids 25 and 27, on a FAST or FAST_DIRECT context; 0: it refuses them with
+                                        TAMCMC_ERR_BAD_MODEL, whatever TAMCMC_OPT_RGB_ADJOINT says.  Read at every call; nothing else
+                                        changes with it.  Any other value: TAMCMC_ERR_BAD_ARG */
 #define TAMCMC_FISHER_SLAB 2048     /* bins per workgroup (and per partial matrix) of the Gram kernel of tamcmc_hip_fisher / _weighted_gram */
 
 /* One (n,l) multiplet: <=7 Lorentzian m-components on its truncation window.
@@ -345,8 +349,8 @@ int tamcmc_hip_fd_gradient_posterior(tamcmc_hip_ctx *ctx, int model_id, int prio
  * bit for bit what the windowed route gives for that component; a slot with a failed table gives NaN and the status, as there.  The base
  * launch is the windowed route's: logL0 is its bits, and the prior's share is the finite-difference route's bits.  Same determinism as
  * above.  FAST or FAST_DIRECT with a workgroup geometry that has the windowed route (256 x 4, 64 x 8, 64 x 4: others return
- * TAMCMC_ERR_BAD_ARG); STRICT returns TAMCMC_ERR_BAD_ARG; tamcmc_hip_fisher keeps refusing the ids.  With the option at 0 the ids are
- * refused as before.
+ * TAMCMC_ERR_BAD_ARG); STRICT returns TAMCMC_ERR_BAD_ARG; tamcmc_hip_fisher does not read this option (its own is
+ * TAMCMC_OPT_RGB_FISHER).  With the option at 0 the ids are refused as before.
  * Tolerance of a linearisable component: G and Gn as above, within 1e-11 of their absolute sums A, An, carried through the contraction with
  * the batch's own tables (tamcmc_hip_rgb_batch_tables):
  *   |d grad_k| <= (p/T)/|h_applied| 1e-11 [sum_rows sum_f A[row][f] |dT[row].f| + sum_j An[j] |d noise_j|];
@@ -436,13 +440,33 @@ int tamcmc_hip_fd_batch_tables(tamcmc_hip_ctx *ctx, int model_id, int prior_clas
  * with the fp64 matrix instruction, the slabs are added in slab order.  One fixed order everywhere: two calls give the same bits, F is
  * symmetric bit for bit, and a chain's F does not depend on the number of chains, its place in the batch or the number of passes.
  * Out: F [C x Nvars x Nvars].  hstep[k] != 0.
- * Models: the fixed-length table models, ids 3, 11, 12, 13, 14, 23; ids 0, 1 (no table) and 25, 27 (tables of variable length) return
- * TAMCMC_ERR_BAD_MODEL.  Arithmetic: FAST or FAST_DIRECT; STRICT returns TAMCMC_ERR_BAD_ARG, as for the adjoint route.  A perturbed
+ * Models: the fixed-length table models, ids 3, 11, 12, 13, 14, 23, and with TAMCMC_OPT_RGB_FISHER = 1 the red giants, ids 25 and 27 (below);
+ * ids 0, 1 (no table) return TAMCMC_ERR_BAD_MODEL, and so do 25 and 27 with the option at 0.  Arithmetic: FAST or FAST_DIRECT; STRICT returns TAMCMC_ERR_BAD_ARG, as for the adjoint route.  A perturbed
  * vector whose table fails makes the call return that status; row and column k of that chain's F are then NaN (all of it when the base
  * table fails), the other chains are unaffected.
  * Tolerance: the FAST tolerance of a model row (|dM|/M <= 1e-12 per bin) carried through the difference and the product: against the same
  * quantity from long-double model rows, |dF_jk| <= 2 (p/T) (eps_k ||U_j||_1 + eps_j ||U_k||_1 + Nx eps_j eps_k), eps_k = 2e-12 / |h_applied,k|
- * (tests/test_gpu_fisher.py; the factor 2 covers the device table builder's last-ulp differences in the frequencies). */
+ * (tests/test_gpu_fisher.py; the factor 2 covers the device table builder's last-ulp differences in the frequencies).
+ *
+ * Red giants (ids 25, 27; TAMCMC_OPT_RGB_FISHER = 1).  A perturbation may change the SET of l=1 mixed modes; every later row then shifts and
+ * "the base row's window" means nothing.  For each chain and variable BOTH perturbed tables are classified on the device against the
+ * chain's base table with the rule of the hybrid adjoint (see tamcmc_hip_adjoint_table: LINEARISABLE / FALLBACK, csrc/adj_rgb_match.h),
+ * and the form follows from the two classes (csrc/fisher_rgb_rule.h):
+ *   both linearisable   the frozen central difference above;
+ *   one linearisable    the frozen ONE-SIDED difference on that side, U_k,i = (M+ - M0) / ((x+ - x0) M0) or (M0 - M-) / ((x0 - x-) M0): the
+ *                       other slot is overwritten with the base table, so that its model row is M0 bit for bit and it adds exactly zero;
+ *   both fallback       the central difference of the two rows on their OWN windows (unfrozen): F then carries the window-edge error
+ *                       quantified above, which is better than no information for a seed;
+ *   a failed table      as above: NaN in row and column k (the whole chain when the base vector fails), the status returned.
+ * The step is the difference of the doubles as stored for the form used.  tamcmc_hip_get_rgb_fisher_stats counts the three forms.
+ * The one-sided form's truncation error, measured on the small test star at a point where both forms exist for the same variable (the
+ * period spacing; numpy yardstick, tests/test_gpu_rgb_fisher.py): at most 4.0e-3 of sqrt(F_jj F_kk) (id 25;
+ * 2.5e-3 for id 27) over all elements when EVERY variable is taken one-sided at steps of 1e-6 |theta| -- the largest element is the one
+ * between the period spacing, in which the mixed-mode frequencies are curved, and a bias value of those frequencies -- against 4e-5 for the central form at h and h / 2.  Across the mode-count change
+ * of that test the unfrozen central difference would give F_kk = 5.8e7 where the one-sided form gives 3.2e4.
+ * The same tolerance, with h_applied the step of the form used; the same determinism: a chain's F does not depend on the number of chains,
+ * its place in the batch or the number of passes (the chains of a pass are the smaller of the row budget's and what the red-giant
+ * pre-step's workspace takes at 2 Nvars + 1 vectors a chain). */
 int tamcmc_hip_fisher(tamcmc_hip_ctx *ctx, int model_id, int C, const double *params, int64_t Nparams, const int32_t *plength,
                       const int32_t *index_to_relax, int Nvars, const double *hstep, const double *Tcoefs, double p,
                       double *F /* [C x Nvars x Nvars] */);
@@ -451,8 +475,13 @@ int tamcmc_hip_fisher(tamcmc_hip_ctx *ctx, int model_id, int C, const double *pa
 int tamcmc_hip_weighted_gram(tamcmc_hip_ctx *ctx, int N, int64_t K, const double *A /* [N x K] */, const double *w /* [K] or NULL */,
                              double *G /* [N x N] */);
 /* Split of the last tamcmc_hip_fisher call made with TAMCMC_OPT_TIMING on, from HIP events on the context's stream, summed over its
- * passes: table build, window freeze + row launches, Gram + fold (milliseconds; any pointer may be NULL). */
+ * passes: table build (red giants: with the mixed-mode pre-step), window freeze + row launches, Gram + fold (milliseconds; any pointer
+ * may be NULL). */
 int tamcmc_hip_get_fisher_times(tamcmc_hip_ctx *ctx, double *tables_ms, double *rows_ms, double *gram_ms);
+/* Red giants (TAMCMC_OPT_RGB_FISHER): the (chain, variable) pairs of the last tamcmc_hip_fisher call made with TAMCMC_OPT_TIMING on that
+ * took the central, the one-sided and the unfrozen form, summed over its passes; pairs with a failed table are in none (any pointer may
+ * be NULL). */
+int tamcmc_hip_get_rgb_fisher_stats(tamcmc_hip_ctx *ctx, int64_t *central, int64_t *one_sided, int64_t *unfrozen);
 
 /* Timing of the likelihood kernel measured with HIP events on the context's own stream
  * (enabled by TAMCMC_OPT_TIMING): totals since the last reset. */

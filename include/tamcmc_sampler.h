@@ -108,8 +108,9 @@ int64_t tamcmc_sampler_nvars(const tamcmc_sampler *s);
  *                                  logL is what tamcmc_hip_loglike_params_batch returns for the same EnvRow bits, i.e. within 1e-12 |logL|
  *                                  of the reference.  TAMCMC_OPT_WORKGROUP / _BINS_PER_THREAD / _PRECISION do not apply.  No tables:
  *                                  tamcmc_sampler_get_tables -> TAMCMC_ERR_BAD_MODEL; see tamcmc_sampler_get_envelope_rows
- *   tamcmc_sampler_seed_proposal   models 3, 11, 12, 13, 14, 23 on a FAST or FAST_DIRECT context (tamcmc_hip_fisher's refusals: ids 0, 1, 25,
- *     _fisher                      27 -> TAMCMC_ERR_BAD_MODEL, STRICT -> TAMCMC_ERR_BAD_ARG); Nvars <= 16384
+ *   tamcmc_sampler_seed_proposal   models 3, 11, 12, 13, 14, 23, and with TAMCMC_OPT_RGB_FISHER = 1 the red giants 25, 27, on a FAST or
+ *     _fisher                      FAST_DIRECT context, both engines (tamcmc_hip_fisher's refusals: ids 0, 1, and 25, 27 with the option
+ *                                  at 0 -> TAMCMC_ERR_BAD_MODEL, STRICT -> TAMCMC_ERR_BAD_ARG); Nvars <= 16384
  * The host-driven engine has no size-dependent branches (host memory, column Cholesky).
  * tamcmc_sampler_get_info reports which side of each limit a sampler is on and how many iterations each scheme has run. */
 #define TAMCMC_INFO_ENGINE 0          /* 0 host-driven, 1 device-resident */
@@ -248,7 +249,9 @@ int tamcmc_factor_rank_one_update(int32_t Nvars, double *L /* lower, row-major, 
  * The inverse is taken on the host from a Cholesky factor in long double; Sigma_m goes through tamcmc_sampler_set_proposal, so both
  * engines get it; mu and sigma are not touched.  F (may be NULL) receives the F_m, [Nchains x Nvars x Nvars].  Never called implicitly:
  * without it nothing changes.  Any failure (a refusal of tamcmc_hip_fisher, a table that fails at a perturbed point, a non-finite F)
- * returns the status and leaves every proposal law as it was. */
+ * returns the status and leaves every proposal law as it was.  Red giants (ids 25, 27): set TAMCMC_OPT_RGB_FISHER = 1 on the context
+ * first (read at every call; with it at 0 this returns TAMCMC_ERR_BAD_MODEL); a variable whose step reaches across a change of the set
+ * of mixed modes then takes the one-sided or the unfrozen form of the derivative (tamcmc_hip_fisher). */
 int tamcmc_sampler_seed_proposal_fisher(tamcmc_sampler *s, double hstep_rel, double *F /* may be NULL, [Nchains x Nv x Nv] */);
 /* The rule alone, on the host (no device): cov [Nvars x Nvars] = E (I + E F E)^-1 E for a symmetric F and E = diag(errors); symmetric bit
  * for bit.  TAMCMC_ERR_BAD_ARG for a non-finite entry or an F so far from positive semi-definite that I + E F E has no Cholesky factor. */

@@ -34,6 +34,7 @@ OPT_FACTOR_REFRESH = 14  # R: 0 / 1 a full factorisation in every adapting itera
 OPT_ENVELOPE_GRADIENT = 15  # 1: fd_gradient / fd_gradient_posterior (and the host engine's Langevin step) take the analytic likelihood share for ids 0 / 1 (default 0: brute force); read at every call
 ENVELOPE_GRAD_N, ENVELOPE_KSI_N = 13, 9  # row quantities / xi sums per vector of HipContext.envelope_gradient_sums
 OPT_RGB_ADJOINT = 12  # 1: under GRADIENT_ADJOINT the red-giant ids 25 / 27 take the hybrid adjoint batch (default 0: ERR_BAD_MODEL); read at every call
+OPT_RGB_FISHER = 16  # 1: HipContext.fisher (and Sampler.seed_proposal_fisher) accepts the red-giant ids 25 / 27 (default 0: ERR_BAD_MODEL); read at every call
 OPT_FISHER_WORKSPACE_MB = 10  # MiB of model rows HipContext.fisher keeps on the device per pass (default 2048)
 FISHER_SLAB = 2048  # bins per workgroup of the Gram kernel (TAMCMC_FISHER_SLAB)
 OPT_QUICK_DECIDE = 8  # test facility: 1 = the fused step's decision shortcut always falls back to the exact evaluation
@@ -76,6 +77,7 @@ ABI = [
     ("tamcmc_hip_fisher", C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int64, _ip, _ip, C.c_int, _dp, _dp, C.c_double, _dp]),
     ("tamcmc_hip_weighted_gram", C.c_int, [_vp, C.c_int, C.c_int64, _dp, _dp, _dp]),
     ("tamcmc_hip_get_fisher_times", C.c_int, [_vp, _dp, _dp, _dp]),
+    ("tamcmc_hip_get_rgb_fisher_stats", C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("tamcmc_hip_rgb_mixed_modes", C.c_int, [_vp, C.c_int, _dp, C.c_int64, _ip, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int)]),
     ("tamcmc_hip_get_kernel_stats", C.c_int, [_vp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("tamcmc_hip_reset_kernel_stats", C.c_int, [_vp]),
@@ -360,7 +362,8 @@ class HipContext:
 
     def fisher(self, model_id, params, plength, index_to_relax, hstep, Tcoefs=None, p=1.0):
         """Expected (Fisher) information F [C x Nvars x Nvars] of the likelihood at each row of params (tamcmc_hip_fisher): central
-        differences with frozen windows, F = (p / T) U U^T.  A table that fails at a perturbed point leaves NaN in that row and column;
+        differences with frozen windows, F = (p / T) U U^T (red giants, with OPT_RGB_FISHER: per variable the central, the one-sided or the
+        unfrozen form, include/tamcmc_hip.h).  A table that fails at a perturbed point leaves NaN in that row and column;
         the status of the call is left in self.last_fisher_status."""
         params = _f64(params)
         if params.ndim == 1:
@@ -380,6 +383,12 @@ class HipContext:
         a, b, g = C.c_double(0), C.c_double(0), C.c_double(0)
         self._chk(self._L.tamcmc_hip_get_fisher_times(self._h, C.byref(a), C.byref(b), C.byref(g)))
         return a.value, b.value, g.value
+
+    def rgb_fisher_stats(self):
+        """(central, one-sided, unfrozen) (chain, variable) pairs of the last fisher() call on a red giant (OPT_RGB_FISHER; timing on)."""
+        a, b, u = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self._L.tamcmc_hip_get_rgb_fisher_stats(self._h, C.byref(a), C.byref(b), C.byref(u)))
+        return a.value, b.value, u.value
 
     def weighted_gram(self, A, w=None):
         """G [N x N] = sum_k w_k A_jk A_lk through the Gram and fold kernels of fisher() (tamcmc_hip_weighted_gram; w None: ones)."""

@@ -135,6 +135,10 @@ int tamcmc_hip_set_option(tamcmc_hip_ctx *c, int option, int64_t value) {
         if (value < 0 || value > 1) return TAMCMC_ERR_BAD_ARG;
         c->rgb_adjoint = (int)value;
         return TAMCMC_OK;
+    case TAMCMC_OPT_RGB_FISHER:
+        if (value < 0 || value > 1) return TAMCMC_ERR_BAD_ARG;
+        c->rgb_fisher = (int)value;
+        return TAMCMC_OK;
     case TAMCMC_OPT_WORKGROUP:  // sets the workgroup size AND its default bins per thread
         if (value != 64 && value != 256) return TAMCMC_ERR_BAD_ARG;
         c->wgs = (int)value;

@@ -82,6 +82,7 @@ struct tamcmc_hip_ctx {
     int gradient = TAMCMC_GRADIENT_FD;  // gradient batches: finite differences, or the table-space adjoint with frozen windows (adjoint.h)
     int rgb_device_langevin = 0;  // 1: the device-resident engine builds its Langevin sampler for the red-giant ids (read at sampler creation)
     int rgb_adjoint = 0;  // 1: under TAMCMC_GRADIENT_ADJOINT the red-giant ids take the hybrid batch (fd_batch.hip; read at every call)
+    int rgb_fisher = 0;  // 1: tamcmc_hip_fisher accepts the red-giant ids (fisher.hip: k_fisher_freeze_rgb; read at every call)
     int envelope_device_engine = 0;  // 1: the device-resident engine is built for the Gaussian-envelope ids 0 / 1 (read at sampler creation)
     int factor_refresh = 0;  // R of TAMCMC_OPT_FACTOR_REFRESH: < 2 a full factorisation per adapting iteration, else rank-one steps (read at sampler creation)
     int envelope_gradient = 0;  // 1: the gradient batches of ids 0 / 1 take the analytic likelihood share (envelope.hip; read at every call)
@@ -106,6 +107,7 @@ struct tamcmc_hip_ctx {
     bool poly_ready = false;
     tamcmc::DevBuf<double> d_fisher;  // Fisher information (fisher.hip): 1/h_applied, weights, slab partials, F
     double fisher_ms[3] = {0, 0, 0};  // last tamcmc_hip_fisher call with timing on: table build, row launches, Gram + fold (HIP events, summed over passes)
+    int64_t rgb_fisher_forms[3] = {0, 0, 0};  // ... of a red giant: (chain, variable) pairs on the central, one-sided, unfrozen form (summed over passes)
     tamcmc::PinBuf<double> h_S;
     // samplers created on this context (they borrow its stream and buffers): tamcmc_hip_destroy with samplers still attached only
     // marks the context; the last tamcmc_sampler_destroy frees it -- any destruction order is safe

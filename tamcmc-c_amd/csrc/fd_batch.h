@@ -51,6 +51,11 @@ struct FdBatch {
     size_t o_tab = 0, o_dtab = 0, o_btab = 0, o_drange = 0, o_dflags = 0, o_drow = 0, o_dnold = 0, total_bytes = 0;
     size_t o_adjG = 0, o_adjGn = 0, o_adjpart = 0, o_adjGpart = 0;  // adjoint workspace inside the block: G [C x per x 17], Gn [C x stride], noise tile partials, row segment partials
     int adj_ntn = 0, adj_nseg = 0;
+    // Route::Rows of a red giant (TAMCMC_OPT_RGB_FISHER; N = Nvars / 2 variables): the three candidate step reciprocals [3 x C x N] the
+    // caller uploads, the ones k_fisher_freeze_rgb chose [C x N], and three integers -- the (chain, variable) pairs that took the central,
+    // the one-sided and the unfrozen form -- which the kernel adds to when count_forms is set (the caller zeroes and reads them)
+    size_t o_frh3 = 0, o_frh = 0, o_fcount = 0;
+    bool count_forms = false;
     size_t o_adjcount = 0;  // hybrid: two integers, the perturbed slots k_adj_contract contracted / took from the DELTA launch (count_slots)
     int layout(tamcmc_hip_ctx *c, Request request, int model_id, int prior_class, int C, int64_t Nparams, const int32_t *plength, int Nvars);
     // block: the batch's device block (total_bytes), constants in place; d_params: C x Np parameter vectors on the device (nullptr: the

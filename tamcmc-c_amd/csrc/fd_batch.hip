@@ -25,7 +25,9 @@
 //             (base), NaN (a failed table).  The moments are taken for every chain: which chains have a fallback slot is known on the
 //             device only.  The row pass keeps its (segment, row, chain) grid: see DESIGN section 9 for what a work list cost;
 //   Rows      (tamcmc_hip_fisher) k_fd_unpack -> k_fisher_freeze (every perturbed table gets its base table's windows) -> k_loglike on
-//             all B tables, model rows kept, no sums.
+//             all B tables, model rows kept, no sums.  Red giants (TAMCMC_OPT_RGB_FISHER = 1): k_fd_rgb_perturb -> rgb_device_stage ->
+//             k_fisher_freeze_rgb (per chain and variable, both sides classified as the hybrid batch classifies a slot: windows frozen,
+//             a side replaced by the base table, or both left alone -- fisher_rgb_rule.h) -> the same launch.
 // Red-giant models (ids 25 / 27): the table of a vector needs the mixed-mode solver, so k_fd_unpack's place is taken by
 //   k_fd_rgb_perturb (perturbed vector, class-4 log-prior, scalar unpack into the pre-step workspace) -> rgb_device_stage (solver, rows),
 // in chunks of vectors through ONE workspace slice; everything after the tables is the same.
@@ -365,7 +367,8 @@ int FdBatch::layout(tamcmc_hip_ctx *c, Request request, int model_id_, int prior
     model_id = model_id_; prior_class = prior_class_; C = C_; Np = Nparams; Nvars = Nvars_;
     rgb = is_rgb_model(model_id);
     E = Nvars + 1; B = C * E;
-    if (int rc = fd_route(request, c->gradient, c->fd_windowed, c->precision, delta_geometry(c->wgs, c->K), Nvars, rgb, &route, c->rgb_adjoint != 0))
+    if (int rc = fd_route(request, c->gradient, c->fd_windowed, c->precision, delta_geometry(c->wgs, c->K), Nvars, rgb, &route, c->rgb_adjoint != 0,
+                          c->rgb_fisher != 0))
         return rc;
     tables_only = request == Request::Tables;
     // (the hybrid batch's fallback slots go through the DELTA launch, which exists for the default geometries only: 256 x 4, 64 x 8, 64 x 4)
@@ -414,6 +417,13 @@ int FdBatch::layout(tamcmc_hip_ctx *c, Request request, int model_id_, int prior
         adj_nseg = (int)((c->Nx + ADJ_SEG - 1) / ADJ_SEG);
         o_adjGpart = o; o = al16(o + (size_t)C * per * adj_nseg * ADJ_F * 8);
         if (hybrid()) { o_adjcount = o; o = al16(o + 16); }
+    }
+    o_frh3 = o_frh = o_fcount = 0;
+    if (route == Route::Rows && rgb) {
+        const size_t n_rh = (size_t)C * (Nvars / 2);
+        o_frh3 = o; o = al16(o + 3 * n_rh * 8);
+        o_frh = o; o = al16(o + n_rh * 8);
+        o_fcount = o; o = al16(o + 24);
     }
     total_bytes = o;
     const int tbins = tile_bins(c->wgs, c->K);
@@ -583,7 +593,15 @@ int FdBatch::enqueue(tamcmc_hip_ctx *c, unsigned char *db, const double *d_param
         if (int rc = evaluate_tables(c, fa, fa.T, B, Keep::Nothing, true, w, a)) return rc;
         break;
     case Route::Rows:  // frozen windows, then the B model rows (no sums are read: the partials are the launch's scratch)
-        HIPCHK(c, launch_fisher_freeze(fa.T.mults, fa.T.pairs, fa.status, per, C, E, st));
+        if (rgb) {  // (per chain and variable, both sides seen together: fisher_rgb_rule.h)
+            FisherRgbArgs r;
+            r.mults = fa.T.mults; r.pairs = fa.T.pairs; r.nh = fa.T.nh; r.nn = fa.T.nn; r.noise = fa.T.noise; r.status = fa.status;
+            r.per = per; r.stride = stride; r.C = C; r.N = Nvars / 2;
+            r.rh3 = (const double *)(db + o_frh3); r.rh = (double *)(db + o_frh);
+            r.counts = count_forms ? (unsigned long long *)(db + o_fcount) : nullptr;
+            HIPCHK(c, launch_fisher_freeze_rgb(r, st));
+        } else
+            HIPCHK(c, launch_fisher_freeze(fa.T.mults, fa.T.pairs, fa.status, per, C, E, st));
         if (int rc = evaluate_tables(c, fa, fa.T, B, Keep::Rows, false, w, a)) return rc;
         break;
     case Route::Adjoint: {

@@ -14,6 +14,7 @@ namespace tamcmc {
 //             TAMCMC_OPT_RGB_ADJOINT): the hybrid batch -- the contraction for the slots whose rows correspond one to one with the base
 //             table's (adj_rgb_match.h), Windowed's DELTA launch for the others;
 //   Rows      every perturbed table given its base table's windows, then ONE launch that leaves the B model rows (fisher.h): no sums.
+//             Red giants (rgb, with TAMCMC_OPT_RGB_FISHER): the windows per (chain, variable) by the rule of fisher_rgb_rule.h.
 enum class FdRoute { Brute, Windowed, Adjoint, Rows };
 // Who asks: the gradient entries and the sampler follow the context's options, the audit entry (tamcmc_hip_adjoint_table) and the Fisher
 // information (tamcmc_hip_fisher) name their route whatever the options say; Tables (tamcmc_hip_rgb_batch_tables, tamcmc_hip_fd_batch_tables) asks for the batch's
@@ -23,15 +24,15 @@ enum class FdRequest { FromOptions, Adjoint, Rows, Tables };
 // gradient = TAMCMC_OPT_GRADIENT, fd_windowed = TAMCMC_OPT_FD_WINDOWED, precision = TAMCMC_OPT_PRECISION, delta_geometry: the DELTA variant
 // of the likelihood kernel exists for the context's workgroup geometry; rgb: a red-giant model (tables of variable length); rgb_adjoint =
 // TAMCMC_OPT_RGB_ADJOINT: the red-giant models may take the adjoint route, as the hybrid batch (FdBatch::layout then asks for a geometry
-// that has the DELTA variant).
+// that has the DELTA variant); rgb_fisher = TAMCMC_OPT_RGB_FISHER: the red-giant models may take the Rows route.
 // Returns TAMCMC_OK and the route, or the refusal.
 inline int fd_route(FdRequest request, int gradient, int fd_windowed, int precision, bool delta_geometry, int Nvars, bool rgb, FdRoute *route,
-                    bool rgb_adjoint = false) {
+                    bool rgb_adjoint = false, bool rgb_fisher = false) {
     const bool strict = precision == TAMCMC_PRECISION_STRICT;
     if (request == FdRequest::Tables) {
         *route = FdRoute::Brute;
     } else if (request == FdRequest::Rows) {
-        if (rgb || strict) return TAMCMC_ERR_BAD_ARG;  // (tamcmc_hip_fisher refuses both before it gets here)
+        if ((rgb && !rgb_fisher) || strict) return TAMCMC_ERR_BAD_ARG;  // (tamcmc_hip_fisher refuses both before it gets here)
         *route = FdRoute::Rows;
     } else if (request == FdRequest::Adjoint || gradient == TAMCMC_GRADIENT_ADJOINT) {
         if (rgb && !rgb_adjoint) return TAMCMC_ERR_BAD_MODEL;  // (no row-by-row contraction of tables that differ in length, unless opted in)

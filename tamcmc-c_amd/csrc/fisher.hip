@@ -1,5 +1,6 @@
-// fisher.hip -- expected (Fisher) information of the chi^2(2p) likelihood (fisher.h): k_fisher_freeze, k_fisher_gram, k_fisher_fold and the two
-// C entries tamcmc_hip_fisher / tamcmc_hip_weighted_gram.  No atomics: the bins of a slab are added in bin order (four per matrix
+// fisher.hip -- expected (Fisher) information of the chi^2(2p) likelihood (fisher.h): k_fisher_freeze, k_fisher_freeze_rgb, k_fisher_gram,
+// k_fisher_fold and the two C entries tamcmc_hip_fisher / tamcmc_hip_weighted_gram.  No atomics in anything that reaches F (the red giants'
+// form counters are integers beside it): the bins of a slab are added in bin order (four per matrix
 // instruction), the slabs in slab order, so two calls give the same bits and a chain's F does not depend on the chains around it, on its
 // place in the batch or on the number of passes.
 #include <hip/hip_runtime.h>
@@ -12,6 +13,7 @@
 #include "envelope.h"
 #include "fd_batch.h"
 #include "fisher.h"
+#include "fisher_rgb_rule.h"
 #include "kernels.h"
 
 namespace tamcmc {
@@ -36,6 +38,55 @@ __global__ void __launch_bounds__(128) k_fisher_freeze(tamcmc_multiplet *mults, 
     for (int j = threadIdx.x; j < n; j += 128) {
         t[j].i0 = b[j].i0;
         t[j].i1 = b[j].i1;
+    }
+}
+
+// Red giants: one workgroup per (chain c, variable k).  Lanes over the rows of the base table compare both perturbed tables with it
+// (adj_rgb_row_matches; an LDS flag per side, every writer stores the same value, as k_fd_compare under FdArgs::hybrid), the rule of
+// fisher_rgb_rule.h chooses the form, and the workgroup writes what the form asks for.  Only this workgroup writes the two perturbed
+// slots; the base slot is read by every workgroup of the chain and written by none.
+__global__ void __launch_bounds__(128) k_fisher_freeze_rgb(const FisherRgbArgs a) {
+    const int c = blockIdx.x / a.N, k = blockIdx.x - c * a.N, tid = threadIdx.x, E = 2 * a.N + 1;
+    const int sb = c * E, sp = sb + 1 + k, sm = sb + 1 + a.N + k;
+    __shared__ int s_moved[2];
+    const int n_b = a.pairs[2 * sb + 1] - a.pairs[2 * sb], n_p = a.pairs[2 * sp + 1] - a.pairs[2 * sp], n_m = a.pairs[2 * sm + 1] - a.pairs[2 * sm];
+    const tamcmc_multiplet *tb = a.mults + a.pairs[2 * sb];
+    tamcmc_multiplet *tp = a.mults + a.pairs[2 * sp], *tm = a.mults + a.pairs[2 * sm];
+    const bool ok_b = a.status[sb] == TAMCMC_OK, ok_p = ok_b && a.status[sp] == TAMCMC_OK, ok_m = ok_b && a.status[sm] == TAMCMC_OK;
+    const bool same_p = ok_p && n_p == n_b, same_m = ok_m && n_m == n_b;  // (uniform)
+    const int n = min(n_b, a.per);
+    if (tid < 2) s_moved[tid] = 0;
+    __syncthreads();
+    for (int j = tid; j < n; j += 128) {
+        if (same_p && !adj_rgb_row_matches(tb, tp, n_b, j)) s_moved[0] = 1;
+        if (same_m && !adj_rgb_row_matches(tb, tm, n_b, j)) s_moved[1] = 1;
+    }
+    __syncthreads();
+    const int cls_p = !ok_p ? ADJ_RGB_FAILED : (same_p && !s_moved[0] ? ADJ_RGB_LINEARISABLE : ADJ_RGB_FALLBACK);
+    const int cls_m = !ok_m ? ADJ_RGB_FAILED : (same_m && !s_moved[1] ? ADJ_RGB_LINEARISABLE : ADJ_RGB_FALLBACK);
+    const FisherRgbChoice ch = fisher_rgb_choose(cls_p, cls_m);
+    if (tid == 0) {
+        const size_t CN = (size_t)a.C * a.N, o = (size_t)c * a.N + k;
+        a.rh[o] = a.rh3[(size_t)ch.rh * CN + o];
+        if (a.counts && ch.form != FISHER_RGB_FAILED) atomicAdd(&a.counts[ch.form - 1], 1ULL);
+    }
+    for (int j = tid; j < n; j += 128) {
+        if (ch.freeze_plus) { tp[j].i0 = tb[j].i0; tp[j].i1 = tb[j].i1; }
+        if (ch.freeze_minus) { tm[j].i0 = tb[j].i0; tm[j].i1 = tb[j].i1; }
+    }
+    if (ch.substitute != FISHER_RGB_SIDE_NONE) {
+        // the side that does not correspond becomes the base table: rows as 8-byte words, then the noise row and the counts
+        const int ss = ch.substitute == FISHER_RGB_SIDE_PLUS ? sp : sm;
+        constexpr int NW = (int)(sizeof(tamcmc_multiplet) / 8);
+        const unsigned long long *src = (const unsigned long long *)tb;
+        unsigned long long *dst = (unsigned long long *)(ch.substitute == FISHER_RGB_SIDE_PLUS ? tp : tm);
+        for (int w = tid; w < n * NW; w += 128) dst[w] = src[w];
+        for (int i = tid; i < a.stride; i += 128) a.noise[(size_t)ss * a.stride + i] = a.noise[(size_t)sb * a.stride + i];
+        if (tid == 0) {
+            a.pairs[2 * ss + 1] = a.pairs[2 * ss] + n;
+            a.nh[ss] = a.nh[sb];
+            a.nn[ss] = a.nn[sb];
+        }
     }
 }
 
@@ -153,6 +204,14 @@ hipError_t launch_fisher_freeze(tamcmc_multiplet *mults, const int *pairs, const
     return hipGetLastError();
 }
 
+hipError_t launch_fisher_freeze_rgb(const FisherRgbArgs &a, hipStream_t st) {
+    if (a.C <= 0 || a.N <= 0 || (long)a.C * a.N > 0x7fffffffL || a.per <= 0 || a.stride <= 0 || !a.mults || !a.pairs || !a.nh || !a.nn || !a.noise ||
+        !a.status || !a.rh3 || !a.rh)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_fisher_freeze_rgb, dim3(a.C * a.N), dim3(128), 0, st, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_fisher_gram(const GramArgs &g, hipStream_t st) {
     const int nsb = (g.NP + FG_SB - 1) / FG_SB;
     const long pairs = (long)nsb * (nsb + 1) / 2, fold = ((long)g.N * g.N + 255) / 256;
@@ -173,7 +232,8 @@ extern "C" {
 int tamcmc_hip_fisher(tamcmc_hip_ctx *c, int model_id, int C, const double *params, int64_t Nparams, const int32_t *plength,
                       const int32_t *index_to_relax, int Nvars, const double *hstep, const double *Tcoefs, double p, double *F) {
     if (!c) return TAMCMC_ERR_BAD_ARG;
-    if (is_envelope_model(model_id) || is_rgb_model(model_id)) return TAMCMC_ERR_BAD_MODEL;  // (no table / tables of variable length)
+    const bool rgb = is_rgb_model(model_id);
+    if (is_envelope_model(model_id) || (rgb && !c->rgb_fisher)) return TAMCMC_ERR_BAD_MODEL;  // (no table / red giants: TAMCMC_OPT_RGB_FISHER)
     int rc = check_gradient_args(c, C, params, Nparams, plength, index_to_relax, Nvars, hstep, F != nullptr, GA_PLENGTH | GA_VARS | GA_FISHER);
     if (rc) return rc;
     if (c->precision == TAMCMC_PRECISION_STRICT) return TAMCMC_ERR_BAD_ARG;  // (as the adjoint route)
@@ -184,7 +244,9 @@ int tamcmc_hip_fisher(tamcmc_hip_ctx *c, int model_id, int C, const double *para
     if (rc) return rc;
     const size_t Np = (size_t)Nparams, N = (size_t)Nvars, Nx = (size_t)c->Nx;
     const int NP = fisher_padded(Nvars), nslab = fisher_slabs((long)c->Nx);
-    int chunk = fisher_chunk(C, Nvars, (long)c->Nx, (size_t)c->fisher_ws_mb);
+    // (red giants: the chains of a pass also have to go through the pre-step workspace slice, 2 Nvars + 1 vectors each)
+    int chunk = rgb ? fisher_rgb_chunk(C, Nvars, (long)c->Nx, (size_t)c->fisher_ws_mb, rgb_device_workspace_bytes(1), FD_RGB_WORKSPACE)
+                    : fisher_chunk(C, Nvars, (long)c->Nx, (size_t)c->fisher_ws_mb);
     {  // launch limits of a pass: chains on a grid axis of k_fisher_gram, (slots x tiles) workgroups of the row launch
         const long tiles = ((long)c->Nx + tile_bins(c->wgs, c->K) - 1) / tile_bins(c->wgs, c->K) + 8;
         const long cap = 0x7fffffffL / (tiles * (2 * Nvars + 1));
@@ -204,6 +266,7 @@ int tamcmc_hip_fisher(tamcmc_hip_ctx *c, int model_id, int C, const double *para
         HIPCHK(c, hipEventCreate(&ev[0]));
         HIPCHK(c, hipEventCreate(&ev[1]));
         c->fisher_ms[0] = c->fisher_ms[1] = c->fisher_ms[2] = 0.0;
+        c->rgb_fisher_forms[0] = c->rgb_fisher_forms[1] = c->rgb_fisher_forms[2] = 0;
     }
     int first_err = TAMCMC_OK;
     std::vector<double> h2(2 * N);  // [+h, -h]
@@ -222,18 +285,33 @@ int tamcmc_hip_fisher(tamcmc_hip_ctx *c, int model_id, int C, const double *para
         if ((r = fb.begin(c, in, &db))) return r;
         // 1 / h_applied (the difference of the two perturbed doubles as stored; the device adds the same doubles) and the temperatures
         const size_t n_rh = (size_t)cp * N, n_F = (size_t)cp * N * N, n_part = (size_t)cp * nslab * NP * NP;
-        HIPCHK(c, c->h_S.reserve(n_rh + cp));
+        // (red giants: the three candidates behind them, 1 / (x+ - x0) and 1 / (x0 - x-); k_fisher_freeze_rgb chooses on the device)
+        HIPCHK(c, c->h_S.reserve((rgb ? 3 : 1) * n_rh + cp));
         for (int ch = 0; ch < cp; ch++) {
             for (size_t k = 0; k < N; k++) {
                 const double x0 = params[(size_t)(c0 + ch) * Np + index_to_relax[k]];
                 volatile double xp = x0 + hstep[k], xm = x0 + (-hstep[k]);
                 c->h_S.p[(size_t)ch * N + k] = 1.0 / (xp - xm);
+                if (rgb) {
+                    c->h_S.p[n_rh + cp + (size_t)ch * N + k] = 1.0 / (xp - x0);
+                    c->h_S.p[2 * n_rh + cp + (size_t)ch * N + k] = 1.0 / (x0 - xm);
+                }
             }
             c->h_S.p[n_rh + ch] = Tcoefs ? Tcoefs[c0 + ch] : 1.0;
         }
         HIPCHK(c, c->d_fisher.reserve(n_rh + cp + n_F + n_part));
         double *d_rh = c->d_fisher.p, *d_T = d_rh + n_rh, *d_F = d_T + cp, *d_part = d_F + n_F;
-        HIPCHK(c, hipMemcpyAsync(d_rh, c->h_S.p, (n_rh + cp) * 8, hipMemcpyHostToDevice, st));
+        if (!rgb) HIPCHK(c, hipMemcpyAsync(d_rh, c->h_S.p, (n_rh + cp) * 8, hipMemcpyHostToDevice, st));
+        if (rgb) {  // the temperatures alone; candidates [central | plus | minus] into the block, the chosen reciprocals come back in its o_frh
+            HIPCHK(c, hipMemcpyAsync(d_T, c->h_S.p + n_rh, (size_t)cp * 8, hipMemcpyHostToDevice, st));
+            HIPCHK(c, hipMemcpyAsync(db + fb.o_frh3, c->h_S.p, n_rh * 8, hipMemcpyHostToDevice, st));
+            HIPCHK(c, hipMemcpyAsync(db + fb.o_frh3 + n_rh * 8, c->h_S.p + n_rh + cp, 2 * n_rh * 8, hipMemcpyHostToDevice, st));
+            d_rh = (double *)(db + fb.o_frh);
+            if (c->timing) {
+                fb.count_forms = true;
+                HIPCHK(c, hipMemsetAsync(db + fb.o_fcount, 0, 24, st));
+            }
+        }
         if (c->timing) HIPCHK(c, hipEventRecord(ev[0], st));
         r = fb.enqueue(c, db, c->timing ? c->ev0 : nullptr, c->timing ? c->ev1 : nullptr);
         if (r) return r;
@@ -245,6 +323,8 @@ int tamcmc_hip_fisher(tamcmc_hip_ctx *c, int model_id, int C, const double *para
         HIPCHK(c, launch_fisher_gram(g, st));
         if (c->timing) HIPCHK(c, hipEventRecord(ev[1], st));
         HIPCHK(c, hipMemcpyAsync(F + (size_t)c0 * N * N, d_F, n_F * 8, hipMemcpyDeviceToHost, st));
+        unsigned long long forms[3] = {0, 0, 0};
+        if (fb.count_forms) HIPCHK(c, hipMemcpyAsync(forms, db + fb.o_fcount, sizeof forms, hipMemcpyDeviceToHost, st));
         FdResults res;
         if ((r = fb.finish(c, &res))) return r;
         if (c->timing) {
@@ -253,6 +333,7 @@ int tamcmc_hip_fisher(tamcmc_hip_ctx *c, int model_id, int C, const double *para
             HIPCHK(c, hipEventElapsedTime(&ms[1], c->ev0, c->ev1));
             HIPCHK(c, hipEventElapsedTime(&ms[2], c->ev1, ev[1]));
             for (int i = 0; i < 3; i++) c->fisher_ms[i] += ms[i];
+            for (int i = 0; i < 3; i++) c->rgb_fisher_forms[i] += (int64_t)forms[i];
         }
         if (first_err == TAMCMC_OK) first_err = res.first_status();
         return TAMCMC_OK;
@@ -279,6 +360,14 @@ int tamcmc_hip_weighted_gram(tamcmc_hip_ctx *c, int N, int64_t K, const double *
     HIPCHK(c, launch_fisher_gram(g, st));
     HIPCHK(c, hipMemcpyAsync(G, d_G, n_G * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
+    return TAMCMC_OK;
+}
+
+int tamcmc_hip_get_rgb_fisher_stats(tamcmc_hip_ctx *c, int64_t *central, int64_t *one_sided, int64_t *unfrozen) {
+    if (!c) return TAMCMC_ERR_BAD_ARG;
+    if (central) *central = c->rgb_fisher_forms[0];
+    if (one_sided) *one_sided = c->rgb_fisher_forms[1];
+    if (unfrozen) *unfrozen = c->rgb_fisher_forms[2];
     return TAMCMC_OK;
 }
 
