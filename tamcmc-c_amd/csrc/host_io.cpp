@@ -1,7 +1,7 @@
 // host_io.cpp -- input front end (include/tamcmc_io.h): `.data` reader, `.model` reader and the parameter-vector /
 // prior-table builders of the local fit (model_MS_local_basic), of the global main-sequence fits
 // (model_MS_Global_aj_HarveyLike, model_MS_Global_a1etaa3_HarveyLike_Classic) and of the red-giant fits
-// (model_RGB_asympt_aj_AppWidth_HarveyLike_v4, ..._CteWidth_..., io_asymptotic.cpp).  Plain C++ (no device code).
+// (model_RGB_asympt_aj_AppWidth_HarveyLike_v4, ..._CteWidth_...).  Plain C++ (no device code).
 //
 // Restates, in its own structure (a table of parameter blocks instead of the reference's per-degree vectors):
 //   Config::read_data_ascii_Ncols  tamcmc/sources/config.cpp:907-1060     Config::setup range cut  config.cpp:312-347
@@ -9,12 +9,21 @@
 //   set_noise_params_local         io_local.cpp:1178-1238                  IO_models::fill_param*   io_models.cpp:40-120
 //   read_MCMC_file_MS_Global / build_init_MS_Global / set_noise_params / settings_aj_splittings
 //                                  tamcmc/sources/io_ms_global.cpp:27-360, :362-1445, :1447-1536, :1718-1850
+//   build_init_asymptotic / settings_aj_splittings_RGB    tamcmc/sources/io_asymptotic.cpp:32-838, :841-955
+//   set_width_App2016_params_v2    io_ms_global.cpp:1625-1720
 // The reference exits on malformed input; every such exit is a TAMCMC_IO_ERR_* code here.
+//
+// build_local, build_global and build_asymptotic each list, top to bottom, the keywords they accept and the order of their
+// blocks; what they have in common is stated once above them: read_switches, max_degree, read_eigen_table, heights_to_amplitudes,
+// the kw_* keyword rules (put_keyword for the plain ones), Block::put, assemble, finish, and load_model behind the three C entry
+// points.  A keyword a builder does not name stays unread there.
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <initializer_list>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -99,8 +108,25 @@ struct Block {
                    const std::vector<double> &vals, int pos, int i0_free) {
         for (size_t i = 0; i < v.size(); i++) fill(name, rel[i] ? prior : "Fix", v[i], vals, pos + (int)i, i0_free);
     }
+    // a slot fixed at a value; its prior values stay as an earlier line left them
+    void fix_at(int pos, const std::string &name, double value) {
+        names[(size_t)pos] = name;
+        prior_names[(size_t)pos] = "Fix";
+        relax[(size_t)pos] = 0;
+        inputs[(size_t)pos] = value;
+    }
     std::vector<double> prior_col(int i) {
         return {pr(0, i), pr(1, i), pr(2, i), pr(3, i)};
+    }
+    // IO_models::add_param, io_models.cpp:122-146: block b copied to positions pos ... pos + b.n - 1
+    void put(const Block &b, int pos) {
+        for (int i = 0; i < b.n; i++) {
+            names[(size_t)(pos + i)] = b.names[(size_t)i];
+            prior_names[(size_t)(pos + i)] = b.prior_names[(size_t)i];
+            inputs[(size_t)(pos + i)] = b.inputs[(size_t)i];
+            relax[(size_t)(pos + i)] = b.relax[(size_t)i];
+            for (int k = 0; k < 4; k++) pr(k, pos + i) = b.priors[(size_t)k * b.n + i];
+        }
     }
 };
 
@@ -288,15 +314,13 @@ int read_model_file(const char *path, int slice_ind /* < 0: global fit, one rang
     return TAMCMC_IO_OK;
 }
 
-int build_local(const ModelFile &mf, double resol, tamcmc_inputs &out) {
-    const long double pi = 3.141592653589793238L;
-    const double G = 6.667e-8, Dnu_sun = 135.1, R_sun = 6.96342e5, M_sun = 1.98855e30;
-    const double rho_sun = (double)(M_sun * 1e3 / (4 * pi * std::pow(R_sun * 1e5, 3) / 3));
-    const double rho = std::pow(mf.dnu / Dnu_sun, 2.) * rho_sun;
-    const double Hmin = 1, Hmax = 10000;
-    // ---- switches read before anything else (io_local.cpp:381-411)
-    std::string model;
-    int do_amp = 0;
+// ---------------------------------------------------------------- what the three builders share, each rule stated once
+const long double pi = 3.141592653589793238L;
+const double Hmin = 1, Hmax = 10000;  // the default Jeffreys prior of the heights
+
+// the two switches read before anything else (io_local.cpp:381-411)
+int read_switches(const ModelFile &mf, std::string &model, int &do_amp) {
+    do_amp = 0;
     for (const auto &c : mf.common) {
         if (c.name == "model_fullname") model = c.prior;
         if (c.name == "fit_squareAmplitude_instead_Height") {
@@ -305,109 +329,203 @@ int build_local(const ModelFile &mf, double resol, tamcmc_inputs &out) {
         }
     }
     if (model.empty()) return fail(TAMCMC_IO_ERR_SYNTAX, "the .model file has no model_fullname");
-    const bool hnlm = (model == "model_MS_local_Hnlm");  // one height per (n, l, m >= 0) instead of the inclination
-    if (model != "model_MS_local_basic" && !hnlm) return fail(TAMCMC_IO_ERR_UNSUPPORTED, "model not covered by this loader: " + model);
+    return 0;
+}
 
-    // ---- per degree: the eigen-table rows of that degree, each matched to ONE mode line within 1e-2 (:416-502), then only
-    //      the modes strictly inside the slice's range (:504-557)
-    std::vector<double> f, h, w, fmin, fmax;
-    std::vector<int> rf, rh, rw;
-    int Nf[4] = {0, 0, 0, 0};
-    int lmax = 0;
+int max_degree(const ModelFile &mf, int &lmax) {
+    lmax = 0;
     for (const auto &m : mf.modes) lmax = m.l > lmax ? m.l : lmax;
     if (lmax > 3) return fail(TAMCMC_IO_ERR_SYNTAX, "degrees above 3 are not supported");
+    return 0;
+}
+
+// the columns of the eigen table, degree after degree, with the flags of the mode line each row belongs to
+struct ModeColumns {
+    std::vector<double> f, fmin, fmax, h, w;
+    std::vector<int> rf, rh, rw;
+    int Nf[4] = {0, 0, 0, 0};
+};
+// Per degree: the eigen-table rows of that degree, each matched to ONE mode line within 1e-2 (io_local.cpp:416-502,
+// io_ms_global.cpp:530-580, io_asymptotic.cpp:146-197).  `slice` (the local fit): only the degrees the mode list names, and of their
+// rows -- once matched -- only those strictly inside the slice's range (io_local.cpp:504-557).  `hw_every_degree` (the local fit):
+// heights and widths of every row; otherwise those of l = 0 only.
+int read_eigen_table(const ModelFile &mf, int lmax, bool slice, bool hw_every_degree, ModeColumns &m) {
     for (int el = 0; el <= lmax; el++) {
-        bool listed = false;
-        for (const auto &m : mf.modes) listed = listed || m.l == el;
-        if (!listed) continue;
+        if (slice) {
+            bool listed = false;
+            for (const auto &ml : mf.modes) listed = listed || ml.l == el;
+            if (!listed) continue;
+        }
         for (const auto &e : mf.eigen) {
             if ((int)e[0] != el) continue;
             int match = -1, nmatch = 0;
             for (size_t k = 0; k < mf.modes.size(); k++)
                 if (mf.modes[k].l == el && mf.modes[k].f > e[1] - 1e-2 && mf.modes[k].f < e[1] + 1e-2) { match = (int)k; nmatch++; }
             if (nmatch != 1) return fail(TAMCMC_IO_ERR_SYNTAX, "eigen-table frequency without a unique entry in the mode list");
-            if (!(e[1] > mf.range[0] && e[1] < mf.range[1])) continue;
-            f.push_back(e[1]); fmin.push_back(e[2]); fmax.push_back(e[3]); w.push_back(e[4]); h.push_back(e[5]);
-            rf.push_back(mf.modes[(size_t)match].rf); rw.push_back(mf.modes[(size_t)match].rW); rh.push_back(mf.modes[(size_t)match].rH);
-            Nf[el]++;
+            if (slice && !(e[1] > mf.range[0] && e[1] < mf.range[1])) continue;
+            const ModeLine &ml = mf.modes[(size_t)match];
+            m.f.push_back(e[1]); m.fmin.push_back(e[2]); m.fmax.push_back(e[3]);
+            m.rf.push_back(ml.rf);
+            if (hw_every_degree || el == 0) {
+                m.w.push_back(e[4]); m.h.push_back(e[5]);
+                m.rw.push_back(ml.rW); m.rh.push_back(ml.rH);
+            }
+            m.Nf[el]++;
         }
     }
-    const int Ntot = (int)f.size();
+    return 0;
+}
+
+void heights_to_amplitudes(ModeColumns &m) {  // squared amplitudes pi*H*W (io_local.cpp:569-583)
+    for (size_t i = 0; i < m.h.size(); i++) m.h[i] = (double)(pi * m.w[i] * m.h[i]);
+}
+
+// ---- keywords of "# Controls and priors for common parameters"
+// a keyword as the files spell it: all lower case, or with a capital first letter
+bool named(const Common &c, const char *lower) {
+    return c.name == lower || (!c.name.empty() && c.name[0] == std::toupper(lower[0]) && c.name.compare(1, std::string::npos, lower + 1) == 0);
+}
+bool is_height(const Common &c) { return named(c, "height") || named(c, "amplitude"); }
+bool is_visibility(const Common &c) { return named(c, "visibility_l1") || named(c, "visibility_l2") || named(c, "visibility_l3"); }
+
+int no_auto(const Common &c) { return c.prior == "Fix_Auto" ? fail(TAMCMC_IO_ERR_SYNTAX, c.name + " cannot be Fix_Auto") : 0; }
+// the plain keyword: start value = its first number, prior values from the second
+int put_keyword(const Common &c, Block &b, const std::string &name, int slot) {
+    if (int rc = no_auto(c)) return rc;
+    b.fill(name, c.prior, c.v[0], c.v, slot, 1);
+    return 0;
+}
+int kw_asymmetry(const Common &c, Block &snlm, int slot) { return put_keyword(c, snlm, "Lorentzian_asymetry", slot); }
+int kw_inclination(const Common &c, Block &inc) {
+    if (int rc = no_auto(c)) return rc;
+    inc.fill("Inclination", c.prior, c.v[0] >= 90 ? 89.99999 : c.v[0], c.v, 0, 1);
+    return 0;
+}
+int kw_cos_sin(const Common &c, Block &snlm, bool &cosi, bool &sini) {  // slots 3 and 4 of the six-slot splitting block
+    const bool is_cos = (c.name == "sqrt(splitting_a1).cosi");
+    if (int rc = put_keyword(c, snlm, c.name, is_cos ? 3 : 4)) return rc;
+    (is_cos ? cosi : sini) = true;
+    return 0;
+}
+int kw_visibility(const Common &c, int lmax, Block &vis) {  // a degree the mode list does not reach has no slot
+    if (int rc = no_auto(c)) return rc;
+    const int k = c.name.back() - '0';
+    if (lmax >= k) vis.fill(std::string("Visibility_l") + c.name.back(), c.prior, c.v[0], c.v, k - 1, 1);
+    return 0;
+}
+int kw_freq_smoothness(const Common &c, double *extra) {
+    if (c.prior != "bool") return fail(TAMCMC_IO_ERR_SYNTAX, "freq_smoothness must be 'bool'");
+    extra[0] = c.v[0];
+    extra[1] = c.v[1];
+    return 0;
+}
+// the global and red-giant fits: one prior for the l = 0 heights, its values from the FIRST number (io_ms_global.cpp:880-886)
+int kw_height_l0(const Common &c, const ModeColumns &m, const std::string &hname, Block &height) {
+    if (int rc = no_auto(c)) return rc;
+    height.fill_vect(m.h, m.rh, hname, c.prior, c.v, 0, 0);
+    return 0;
+}
+
+// ---- assembly
+// out.plength is the caller's; the blocks follow each other in the order given, then come the two parameters every model has
+// after its blocks (non-positive trunc_c -> full Lorentzian, io_local.cpp:1108-1110).  Returns the index after these two.
+int assemble(tamcmc_inputs &out, std::initializer_list<const Block *> blocks, double trunc_c, int do_amp) {
+    int N = 0;
+    for (int k = 0; k < 11; k++) N += out.plength[k];
+    Block &A = out.all;
+    A.init(N);
+    int p0 = 0;
+    for (const Block *b : blocks) {
+        A.put(*b, p0);
+        p0 += b->n;
+    }
+    A.fill("Truncation parameter", "Fix", trunc_c > 0 ? trunc_c : 10000., {}, p0, 1);
+    A.fill("Switch for fit of Amplitudes or Heights", "Fix", (double)do_amp, {}, p0 + 1, 1);
+    return p0 + 2;
+}
+// everything of the inputs that is not the vector; last, every prior keyword of the vector must be one the sampler knows
+int finish(tamcmc_inputs &out, const ModelFile &mf, const double (&extra)[10], int model_id, int prior_class, const std::string &model) {
+    for (int k = 0; k < 10; k++) out.extra[k] = extra[k];
+    out.range[0] = mf.range[0]; out.range[1] = mf.range[1];
+    out.dnu = mf.dnu; out.c_l = mf.c_l;
+    out.model_id = model_id;
+    out.prior_class = prior_class;  // Config/default/priors_ctrl.list
+    out.model_name = model;
+    for (const std::string &p : out.all.prior_names)
+        if (prior_id(p) < 0) return fail(TAMCMC_IO_ERR_SYNTAX, "unknown prior keyword: " + p);
+    return TAMCMC_IO_OK;
+}
+
+// build_init_local (io_local.cpp:329-1176) for model_MS_local_basic and model_MS_local_Hnlm, + set_noise_params_local (:1178-1238)
+int build_local(const ModelFile &mf, double resol, tamcmc_inputs &out) {
+    const double G = 6.667e-8, Dnu_sun = 135.1, R_sun = 6.96342e5, M_sun = 1.98855e30;
+    const double rho_sun = (double)(M_sun * 1e3 / (4 * pi * std::pow(R_sun * 1e5, 3) / 3));
+    const double rho = std::pow(mf.dnu / Dnu_sun, 2.) * rho_sun;
+    std::string model;
+    int do_amp, lmax;
+    if (int rc = read_switches(mf, model, do_amp)) return rc;
+    const bool hnlm = (model == "model_MS_local_Hnlm");  // one height per (n, l, m >= 0) instead of the inclination
+    if (model != "model_MS_local_basic" && !hnlm) return fail(TAMCMC_IO_ERR_UNSUPPORTED, "model not covered by this loader: " + model);
+    if (int rc = max_degree(mf, lmax)) return rc;
+    ModeColumns m;  // the modes of the listed degrees inside the slice's range, with their heights and widths
+    if (int rc = read_eigen_table(mf, lmax, true, true, m)) return rc;
+    const int *Nf = m.Nf;
+    const int Ntot = (int)m.f.size();
     if (Ntot == 0) return fail(TAMCMC_IO_ERR_EMPTY_RANGE, "no mode inside the slice's frequency range");
-    if (do_amp)  // heights -> squared amplitudes pi*H*W (:569-583)
-        for (int i = 0; i < Ntot; i++) h[(size_t)i] = (double)(pi * w[(size_t)i] * h[(size_t)i]);
+    if (do_amp) heights_to_amplitudes(m);
     const std::string hname = do_amp ? "Amplitude_l" : "Height_l";
 
     Block height, width, freq, snlm, inc, noise;
     const int Nheights = hnlm ? Nf[0] + 2 * Nf[1] + 3 * Nf[2] + 4 * Nf[3] : Ntot;  // (:592-593, :1076-1078)
     height.init(Nheights); width.init(Ntot); freq.init(Ntot); snlm.init(6); inc.init(1); noise.init(1);
     // Hnlm: only the l=0 heights are filled here; those of l >= 1 wait for the inclination (:592-596)
-    const std::vector<double> h0(h.begin(), h.begin() + Nf[0]);
-    const std::vector<int> rh0(rh.begin(), rh.begin() + Nf[0]);
+    const std::vector<double> h0(m.h.begin(), m.h.begin() + Nf[0]);
+    const std::vector<int> rh0(m.rh.begin(), m.rh.begin() + Nf[0]);
     int pos_prior_height = -1;  // Hnlm: index of the height keyword among the common parameters (:350, :769, :808)
     // ---- defaults (:586-673): Jeffreys on heights and widths, GUG on frequencies
     if (hnlm) height.fill_vect(h0, rh0, hname, "Jeffreys", {Hmin, Hmax, -9999., -9999.}, 0, 0);
-    else height.fill_vect(h, rh, hname, "Jeffreys", {Hmin, Hmax, -9999., -9999.}, 0, 0);
+    else height.fill_vect(m.h, m.rh, hname, "Jeffreys", {Hmin, Hmax, -9999., -9999.}, 0, 0);
     const std::vector<double> wdef = {resol, mf.dnu > 0 ? mf.dnu / 3. : 20., -9999., -9999.};
-    width.fill_vect(w, rw, "Width_l", "Jeffreys", wdef, 0, 0);
+    width.fill_vect(m.w, m.rw, "Width_l", "Jeffreys", wdef, 0, 0);
     for (int i = 0; i < Ntot; i++) {
-        const double s = 0.01 * std::fabs(fmax[(size_t)i] - fmin[(size_t)i]);
-        freq.fill("Frequency_l", rf[(size_t)i] ? "GUG" : "Fix", f[(size_t)i], {fmin[(size_t)i], fmax[(size_t)i], s, s}, i, 0);
+        const double s = 0.01 * std::fabs(m.fmax[(size_t)i] - m.fmin[(size_t)i]);
+        freq.fill("Frequency_l", m.rf[(size_t)i] ? "GUG" : "Fix", m.f[(size_t)i], {m.fmin[(size_t)i], m.fmax[(size_t)i], s, s}, i, 0);
     }
-    double extra[4] = {0, 0, 0.2, 0};  // :700-705
+    double extra[10] = {0, 0, 0.2, 0};  // :700-705
     double trunc_c = -1;
     bool cosi = false, sini = false;
-    auto no_auto = [&](const Common &c) { return c.prior == "Fix_Auto" ? fail(TAMCMC_IO_ERR_SYNTAX, c.name + " cannot be Fix_Auto") : 0; };
-    // ---- the keywords of "# Controls and priors for common parameters" (:707-969)
+    // ---- the keywords (:707-969), in file order: a later line overrides an earlier one
     for (size_t ic = 0; ic < mf.common.size(); ic++) {
         const Common &c = mf.common[ic];
-        const std::string &n = c.name;
-        if (n == "trunc_c") {
+        int rc = 0;
+        if (c.name == "trunc_c") {
             if (c.prior != "Fix") return fail(TAMCMC_IO_ERR_SYNTAX, "trunc_c must be 'Fix'");
             trunc_c = c.v[0];
-        } else if (n == "height" || n == "Height" || n == "amplitude" || n == "Amplitude") {
+        } else if (is_height(c)) {
             if (hnlm) pos_prior_height = (int)ic;
             if (c.prior == "Fix_Auto") {  // Jeffreys between input/Y and input*X per mode (:748-802)
-                const bool amp = (n == "amplitude" || n == "Amplitude");
+                const bool amp = named(c, "amplitude");
                 for (int i = 0; i < (hnlm ? Nf[0] : Ntot); i++) {
                     const double s = amp ? (double)(pi * mf.dnu / 3.) : 1.0;
-                    height.fill(hname, rh[(size_t)i] ? "Jeffreys" : "Fix", h[(size_t)i],
-                                {s * h[(size_t)i] / c.v[0], s * h[(size_t)i] * c.v[1], -9999., -9999.}, i, 0);
+                    height.fill(hname, m.rh[(size_t)i] ? "Jeffreys" : "Fix", m.h[(size_t)i],
+                                {s * m.h[(size_t)i] / c.v[0], s * m.h[(size_t)i] * c.v[1], -9999., -9999.}, i, 0);
                 }
             } else if (hnlm) height.fill_vect(h0, rh0, hname, c.prior, c.v, 0, 0);  // prior parameters from the FIRST number (:809)
-            else height.fill_vect(h, rh, hname, c.prior, c.v, 0, 1);
-        } else if (n == "width" || n == "Width") {
-            if (c.prior == "Fix_Auto") width.fill_vect(w, rw, "Width_l", "Jeffreys", wdef, 0, 0);
-            else width.fill_vect(w, rw, "Width_l", c.prior, c.v, 0, 0);  // (i0 = 0 for free widths, :845-852)
-        } else if (n == "splitting_a1" || n == "Splitting_a1") {
-            if (int rc = no_auto(c)) return rc;
-            snlm.fill("Splitting_a1", c.prior, c.v[0], c.v, 0, 1);
-        } else if (n == "asphericity_eta" || n == "Asphericity_eta") {
-            if (c.prior == "Fix_Auto") {  // the centrifugal term, always fixed (:887-905)
-                snlm.names[1] = "Asphericity_eta0";
-                snlm.prior_names[1] = "Fix";
-                snlm.relax[1] = 0;
-                snlm.inputs[1] = (c.v[0] == 1 && mf.dnu > 0) ? 3. / (4. * M_PI * rho * G) : 0.0;
-            } else snlm.fill("Asphericity_eta", c.prior, c.v[0], c.v, 1, 1);
-        } else if (n == "splitting_a3" || n == "Splitting_a3") {
-            if (int rc = no_auto(c)) return rc;
-            snlm.fill("Splitting_a3", c.prior, c.v[0], c.v, 2, 1);
-        } else if (n == "asymetry" || n == "Asymetry") {
-            if (int rc = no_auto(c)) return rc;
-            snlm.fill("Lorentzian_asymetry", c.prior, c.v[0], c.v, 5, 1);
-        } else if (n == "inclination" || n == "Inclination") {
-            if (int rc = no_auto(c)) return rc;
-            inc.fill("Inclination", c.prior, c.v[0] >= 90 ? 89.99999 : c.v[0], c.v, 0, 1);
-        } else if (n == "sqrt(splitting_a1).cosi") {
-            if (int rc = no_auto(c)) return rc;
-            snlm.fill("sqrt(splitting_a1).cosi", c.prior, c.v[0], c.v, 3, 1);
-            cosi = true;
-        } else if (n == "sqrt(splitting_a1).sini") {
-            if (int rc = no_auto(c)) return rc;
-            snlm.fill("sqrt(splitting_a1).sini", c.prior, c.v[0], c.v, 4, 1);
-            sini = true;
-        }
-        // freq_smoothness, Visibility_l*: irrelevant for a local fit (:709-720); model_fullname etc. handled above
+            else height.fill_vect(m.h, m.rh, hname, c.prior, c.v, 0, 1);
+        } else if (named(c, "width")) {
+            if (c.prior == "Fix_Auto") width.fill_vect(m.w, m.rw, "Width_l", "Jeffreys", wdef, 0, 0);
+            else width.fill_vect(m.w, m.rw, "Width_l", c.prior, c.v, 0, 0);  // (i0 = 0 for free widths, :845-852)
+        } else if (named(c, "splitting_a1")) rc = put_keyword(c, snlm, "Splitting_a1", 0);
+        else if (named(c, "asphericity_eta")) {
+            if (c.prior == "Fix_Auto")  // the centrifugal term, always fixed (:887-905)
+                snlm.fix_at(1, "Asphericity_eta0", (c.v[0] == 1 && mf.dnu > 0) ? 3. / (4. * M_PI * rho * G) : 0.0);
+            else snlm.fill("Asphericity_eta", c.prior, c.v[0], c.v, 1, 1);
+        } else if (named(c, "splitting_a3")) rc = put_keyword(c, snlm, "Splitting_a3", 2);
+        else if (named(c, "asymetry")) rc = kw_asymmetry(c, snlm, 5);
+        else if (named(c, "inclination")) rc = kw_inclination(c, inc);
+        else if (c.name == "sqrt(splitting_a1).cosi" || c.name == "sqrt(splitting_a1).sini") rc = kw_cos_sin(c, snlm, cosi, sini);
+        // freq_smoothness and the visibilities: irrelevant for a local fit (:709-720); the switches were read above
+        if (rc) return rc;
     }
     if (cosi != sini) return fail(TAMCMC_IO_ERR_SYNTAX, "sqrt(splitting_a1).cosi and .sini must both appear");
     if (hnlm) {
@@ -426,7 +544,7 @@ int build_local(const ModelFile &mf, double resol, tamcmc_inputs &out) {
             for (int en = 0; en < Nf[el]; en++, src++)
                 for (int em = 0; em <= el; em++)
                     height.fill("H(" + std::to_string(en) + "," + std::to_string(el) + "," + std::to_string(em) + ")", pname,
-                                h[(size_t)src] * V[el + em], pv, ind++, 0);
+                                m.h[(size_t)src] * V[el + em], pv, ind++, 0);
         }
         extra[3] = 2;  // (:1052; priors_local's normalisation block is commented out: nothing reads it)
         inc.fill("Empty", "Fix", 0, inc.prior_col(0), 0, 1);  // :1022
@@ -469,38 +587,10 @@ int build_local(const ModelFile &mf, double resol, tamcmc_inputs &out) {
     int *pl = out.plength;
     pl[0] = Nheights; pl[1] = 0; pl[2] = Nf[0]; pl[3] = Nf[1]; pl[4] = Nf[2]; pl[5] = Nf[3];
     pl[6] = 6; pl[7] = Ntot; pl[8] = 1; pl[9] = 1; pl[10] = 2;
-    int N = 0;
-    for (int k = 0; k < 11; k++) N += pl[k];
-    Block &A = out.all;
-    A.init(N);
-    auto put = [&](Block &b, int pos) {  // IO_models::add_param, io_models.cpp:122-146
-        for (int i = 0; i < b.n; i++) {
-            A.names[(size_t)(pos + i)] = b.names[(size_t)i];
-            A.prior_names[(size_t)(pos + i)] = b.prior_names[(size_t)i];
-            A.inputs[(size_t)(pos + i)] = b.inputs[(size_t)i];
-            A.relax[(size_t)(pos + i)] = b.relax[(size_t)i];
-            for (int k = 0; k < 4; k++) A.pr(k, pos + i) = b.pr(k, i);
-        }
-    };
-    int p0 = 0;
-    put(height, p0); p0 += pl[0] + pl[1];
-    put(freq, p0); p0 += pl[2] + pl[3] + pl[4] + pl[5];
-    put(snlm, p0); p0 += pl[6];
-    put(width, p0); p0 += pl[7];
-    put(noise, p0); p0 += pl[8];
-    put(inc, p0); p0 += pl[9];
-    A.fill("Truncation parameter", "Fix", trunc_c > 0 ? trunc_c : 10000., {}, p0, 1);  // non-positive c -> full Lorentzian (:1108-1110)
-    A.fill("Switch for fit of Amplitudes or Heights", "Fix", (double)do_amp, {}, p0 + 1, 1);
-    for (int k = 0; k < 10; k++) out.extra[k] = k < 4 ? extra[k] : 0.0;
-    out.range[0] = mf.range[0]; out.range[1] = mf.range[1];
-    out.dnu = mf.dnu; out.c_l = mf.c_l;
-    out.model_id = hnlm ? TAMCMC_MODEL_MS_LOCAL_HNLM : TAMCMC_MODEL_MS_LOCAL_BASIC;
-    out.prior_class = 3;  // io_local, Config/default/priors_ctrl.list
-    out.model_name = model;
-    for (int i = 0; i < N; i++)
-        if (prior_id(A.prior_names[(size_t)i]) < 0) return fail(TAMCMC_IO_ERR_SYNTAX, "unknown prior keyword: " + A.prior_names[(size_t)i]);
-    return TAMCMC_IO_OK;
+    assemble(out, {&height, &freq, &snlm, &width, &noise, &inc}, trunc_c, do_amp);
+    return finish(out, mf, extra, hnlm ? TAMCMC_MODEL_MS_LOCAL_HNLM : TAMCMC_MODEL_MS_LOCAL_BASIC, 3 /* io_local */, model);
 }
+
 
 // set_noise_params (io_ms_global.cpp:1447-1536): first two Harvey profiles fixed, the third and the white noise Gaussian
 void fill_noise_global(const ModelFile &mf, Block &noise) {
@@ -532,20 +622,11 @@ void fill_noise_global(const ModelFile &mf, Block &noise) {
 }
 
 // build_init_MS_Global (io_ms_global.cpp:362-1445) for model_MS_Global_aj_HarveyLike and
-// model_MS_Global_a1etaa3_HarveyLike_Classic, + set_noise_params (:1447-1536)
+// model_MS_Global_a1etaa3_HarveyLike_Classic (and its _v2), + set_noise_params (:1447-1536)
 int build_global(const ModelFile &mf, double resol, tamcmc_inputs &out) {
-    const long double pi = 3.141592653589793238L;
-    const double Hmin = 1, Hmax = 10000;
     std::string model;
-    int do_amp = 0;
-    for (const auto &c : mf.common) {
-        if (c.name == "model_fullname") model = c.prior;
-        if (c.name == "fit_squareAmplitude_instead_Height") {
-            if (c.prior != "bool") return fail(TAMCMC_IO_ERR_SYNTAX, "fit_squareAmplitude_instead_Height must be 'bool'");
-            do_amp = c.v[0] != 0;
-        }
-    }
-    if (model.empty()) return fail(TAMCMC_IO_ERR_SYNTAX, "the .model file has no model_fullname");
+    int do_amp, lmax;
+    if (int rc = read_switches(mf, model, do_amp)) return rc;
     const bool v2 = (model == "model_MS_Global_a1etaa3_HarveyLike_Classic_v2");  // the Classic path, nine height ratios for the inclination
     const bool aj = (model == "model_MS_Global_aj_HarveyLike"), classic = (model == "model_MS_Global_a1etaa3_HarveyLike_Classic") || v2;
     if (model == "model_MS_Global_a1etaa3_HarveyLike_Classic_v3")
@@ -554,107 +635,63 @@ int build_global(const ModelFile &mf, double resol, tamcmc_inputs &out) {
     if (!aj && !classic) return fail(TAMCMC_IO_ERR_UNSUPPORTED, "model not covered by this loader: " + model);
     double extra[10] = {1, 2., 1e6, 0.50, 0.20, 0.15, 0.05, 0.05, 0, -1};  // :403-413
     if (aj) extra[9] = 9;                                                    // :494-499
-    int lmax = 0;
-    for (const auto &m : mf.modes) lmax = m.l > lmax ? m.l : lmax;
-    if (lmax > 3) return fail(TAMCMC_IO_ERR_SYNTAX, "degrees above 3 are not supported");
-    // ---- frequencies of every degree, heights and widths of l=0 only (:530-580)
-    std::vector<double> f, fmin, fmax, h, w;
-    std::vector<int> rf, rh, rw;
-    int Nf[4] = {0, 0, 0, 0};
-    for (int el = 0; el <= lmax; el++)
-        for (const auto &e : mf.eigen) {
-            if ((int)e[0] != el) continue;
-            int match = -1, nmatch = 0;
-            for (size_t k = 0; k < mf.modes.size(); k++)
-                if (mf.modes[k].l == el && mf.modes[k].f > e[1] - 1e-2 && mf.modes[k].f < e[1] + 1e-2) { match = (int)k; nmatch++; }
-            if (nmatch != 1) return fail(TAMCMC_IO_ERR_SYNTAX, "eigen-table frequency without a unique entry in the mode list");
-            f.push_back(e[1]); fmin.push_back(e[2]); fmax.push_back(e[3]);
-            rf.push_back(mf.modes[(size_t)match].rf);
-            if (el == 0) {
-                w.push_back(e[4]); h.push_back(e[5]);
-                rw.push_back(mf.modes[(size_t)match].rW); rh.push_back(mf.modes[(size_t)match].rH);
-            }
-            Nf[el]++;
-        }
-    const int Nh = (int)h.size(), Nfreq = (int)f.size();
+    if (int rc = max_degree(mf, lmax)) return rc;
+    ModeColumns m;  // frequencies of every degree, heights and widths of l=0 only (:530-580)
+    if (int rc = read_eigen_table(mf, lmax, false, false, m)) return rc;
+    const int *Nf = m.Nf;
+    const int Nh = (int)m.h.size(), Nfreq = (int)m.f.size();
     if (Nh == 0) return fail(TAMCMC_IO_ERR_EMPTY_RANGE, "no l=0 mode in the eigen table");
-    if (do_amp)
-        for (int i = 0; i < Nh; i++) h[(size_t)i] = (double)(pi * w[(size_t)i] * h[(size_t)i]);
+    if (do_amp) heights_to_amplitudes(m);
     const std::string hname = do_amp ? "Amplitude_l0" : "Height_l0";
     Block height, width, freq, snlm, vis, inc, noise;
     height.init(Nh); width.init(Nh); freq.init(Nfreq); vis.init(lmax); inc.init(1); noise.init(10);
     // ---- defaults (:640-677)
-    for (int i = 0; i < Nh; i++) height.fill(hname, rh[(size_t)i] ? "Jeffreys" : "Fix", h[(size_t)i], {Hmin, Hmax, -9999., -9999.}, i, 0);
+    height.fill_vect(m.h, m.rh, hname, "Jeffreys", {Hmin, Hmax, -9999., -9999.}, 0, 0);
     const std::vector<double> wdef = {resol, mf.dnu / 3., -9999., -9999.};
-    auto wval = [&](int i) { return w[(size_t)i] < mf.dnu / 3. ? w[(size_t)i] : mf.dnu / 3.1; };
-    for (int i = 0; i < Nh; i++) width.fill("Width_l0", rw[(size_t)i] ? "Jeffreys" : "Fix", wval(i), wdef, i, 0);
+    auto wval = [&](int i) { return m.w[(size_t)i] < mf.dnu / 3. ? m.w[(size_t)i] : mf.dnu / 3.1; };
+    for (int i = 0; i < Nh; i++) width.fill("Width_l0", m.rw[(size_t)i] ? "Jeffreys" : "Fix", wval(i), wdef, i, 0);
     for (int i = 0; i < Nfreq; i++)
-        freq.fill("Frequency_l", rf[(size_t)i] ? "GUG" : "Fix", f[(size_t)i], {fmin[(size_t)i], fmax[(size_t)i], 0.01 * mf.dnu, 0.01 * mf.dnu}, i, 0);
+        freq.fill("Frequency_l", m.rf[(size_t)i] ? "GUG" : "Fix", m.f[(size_t)i], {m.fmin[(size_t)i], m.fmax[(size_t)i], 0.01 * mf.dnu, 0.01 * mf.dnu}, i, 0);
     // ---- splitting block (:700-726): classic 6 slots; aj 12 a-coefficients + eta0 switch + asymmetry
     snlm.init(aj ? 14 : 6);
     if (aj) snlm.fill("eta0_switch", "Fix", 0, {}, 12, 0);
     double trunc_c = -1;
     bool cosi = false, sini = false;
     int aj_count = 0;
-    auto no_auto = [&](const Common &c) { return c.prior == "Fix_Auto" ? fail(TAMCMC_IO_ERR_SYNTAX, c.name + " cannot be Fix_Auto") : 0; };
     static const char *aj_names[12] = {"a1_0", "a1_1", "a2_0", "a2_1", "a3_0", "a3_1", "a4_0", "a4_1", "a5_0", "a5_1", "a6_0", "a6_1"};
+    // ---- the keywords, in file order: a later line overrides an earlier one
     for (const auto &c : mf.common) {
-        const std::string &n = c.name;
-        if (n == "freq_smoothness" || n == "Freq_smoothness") {
-            if (c.prior != "bool") return fail(TAMCMC_IO_ERR_SYNTAX, "freq_smoothness must be 'bool'");
-            extra[0] = c.v[0];
-            extra[1] = c.v[1];
-        } else if (n == "trunc_c") {
+        int rc = 0;
+        if (named(c, "freq_smoothness")) rc = kw_freq_smoothness(c, extra);
+        else if (c.name == "trunc_c") {
             if (c.prior == "Fix") trunc_c = c.v[0];
             else if (!to_double(c.prior, &trunc_c)) return fail(TAMCMC_IO_ERR_SYNTAX, "trunc_c must be 'Fix <value>' (or a bare value)");
-        } else if (n == "Frequency" || n == "frequency") {
+        } else if (named(c, "frequency")) {
             if (c.prior != "GUG" && c.prior != "Uniform") return fail(TAMCMC_IO_ERR_SYNTAX, "Frequency prior must be GUG or Uniform");
             for (int i = 0; i < Nfreq; i++) {
-                const std::vector<double> v = (c.prior == "GUG") ? std::vector<double>{fmin[(size_t)i], fmax[(size_t)i], c.v[3], c.v[4]}
-                                                                 : std::vector<double>{fmin[(size_t)i], fmax[(size_t)i], -9999., -9999.};
-                freq.fill("Frequency_l", rf[(size_t)i] ? c.prior : "Fix", f[(size_t)i], v, i, 0);
+                const std::vector<double> v = (c.prior == "GUG") ? std::vector<double>{m.fmin[(size_t)i], m.fmax[(size_t)i], c.v[3], c.v[4]}
+                                                                 : std::vector<double>{m.fmin[(size_t)i], m.fmax[(size_t)i], -9999., -9999.};
+                freq.fill("Frequency_l", m.rf[(size_t)i] ? c.prior : "Fix", m.f[(size_t)i], v, i, 0);
             }
-        } else if (n == "height" || n == "Height" || n == "amplitude" || n == "Amplitude") {
-            if (int rc = no_auto(c)) return rc;
-            for (int i = 0; i < Nh; i++) height.fill(hname, rh[(size_t)i] ? c.prior : "Fix", h[(size_t)i], c.v, i, 0);  // values from the FIRST number (:880-886)
-        } else if (n == "width" || n == "Width") {
+        } else if (is_height(c)) rc = kw_height_l0(c, m, hname, height);
+        else if (named(c, "width")) {
             const bool au = (c.prior == "Fix_Auto");
-            for (int i = 0; i < Nh; i++) width.fill("Width_l", rw[(size_t)i] ? (au ? "Jeffreys" : c.prior) : "Fix", wval(i), au ? wdef : c.v, i, 0);
-        } else if (n == "splitting_a1" || n == "Splitting_a1") {
-            if (int rc = no_auto(c)) return rc;
-            snlm.fill("Splitting_a1", c.prior, c.v[0], c.v, 0, 1);
-        } else if (n == "asphericity_eta" || n == "Asphericity_eta") {  // kept as a fixed 0: the model computes eta0 itself (:956-962)
-            snlm.names[1] = "Asphericity_eta";
-            snlm.prior_names[1] = "Fix";
-            snlm.relax[1] = 0;
-            snlm.inputs[1] = 0;
-        } else if (n == "splitting_a3" || n == "Splitting_a3") {
-            if (int rc = no_auto(c)) return rc;
-            snlm.fill("Splitting_a3", c.prior, c.v[0], c.v, 2, 1);
-        } else if (n == "asymetry" || n == "Asymetry") {
-            if (int rc = no_auto(c)) return rc;
-            snlm.fill("Lorentzian_asymetry", c.prior, c.v[0], c.v, aj ? snlm.n - 1 : 5, 1);
-        } else if (n == "visibility_l1" || n == "Visibility_l1" || n == "visibility_l2" || n == "Visibility_l2" || n == "visibility_l3" ||
-                   n == "Visibility_l3") {
-            if (int rc = no_auto(c)) return rc;
-            const int k = n.back() - '0';
-            if (lmax >= k) vis.fill(std::string("Visibility_l") + n.back(), c.prior, c.v[0], c.v, k - 1, 1);
-        } else if (n == "inclination" || n == "Inclination") {
-            if (int rc = no_auto(c)) return rc;
-            inc.fill("Inclination", c.prior, c.v[0] >= 90 ? 89.99999 : c.v[0], c.v, 0, 1);
-        } else if (n == "sqrt(splitting_a1).cosi" || n == "sqrt(splitting_a1).sini") {
-            if (int rc = no_auto(c)) return rc;
-            const bool is_cos = (n == "sqrt(splitting_a1).cosi");
-            snlm.fill(n, c.prior, c.v[0], c.v, is_cos ? 3 : 4, 1);
-            (is_cos ? cosi : sini) = true;
-        } else if (aj) {  // settings_aj_splittings, :1718-1850
+            for (int i = 0; i < Nh; i++) width.fill("Width_l", m.rw[(size_t)i] ? (au ? "Jeffreys" : c.prior) : "Fix", wval(i), au ? wdef : c.v, i, 0);
+        } else if (named(c, "splitting_a1")) rc = put_keyword(c, snlm, "Splitting_a1", 0);
+        else if (named(c, "asphericity_eta")) snlm.fix_at(1, "Asphericity_eta", 0);  // the model computes eta0 itself (:956-962)
+        else if (named(c, "splitting_a3")) rc = put_keyword(c, snlm, "Splitting_a3", 2);
+        else if (named(c, "asymetry")) rc = kw_asymmetry(c, snlm, aj ? snlm.n - 1 : 5);
+        else if (is_visibility(c)) rc = kw_visibility(c, lmax, vis);
+        else if (named(c, "inclination")) rc = kw_inclination(c, inc);
+        else if (c.name == "sqrt(splitting_a1).cosi" || c.name == "sqrt(splitting_a1).sini") rc = kw_cos_sin(c, snlm, cosi, sini);
+        else if (aj) {  // settings_aj_splittings, :1718-1850
             for (int k = 0; k < 12; k++)
-                if (n == aj_names[k]) {
-                    if (c.prior == "Fix_Auto") return fail(TAMCMC_IO_ERR_SYNTAX, n + " cannot be Fix_Auto");
-                    snlm.fill(n, c.prior, c.v[0], c.v, k, 1);
+                if (c.name == aj_names[k]) {
+                    if (int e = put_keyword(c, snlm, c.name, k)) return e;
                     aj_count++;
                 }
         }
+        if (rc) return rc;
     }
     if (aj && aj_count != 12) return fail(TAMCMC_IO_ERR_SYNTAX, "the aj model needs the 12 keywords a1_0 ... a6_1 (:1178-1181)");
     if (cosi != sini) return fail(TAMCMC_IO_ERR_SYNTAX, "sqrt(splitting_a1).cosi and .sini must both appear");
@@ -680,38 +717,9 @@ int build_global(const ModelFile &mf, double resol, tamcmc_inputs &out) {
     int *pl = out.plength;
     pl[0] = Nh; pl[1] = lmax; pl[2] = Nf[0]; pl[3] = Nf[1]; pl[4] = Nf[2]; pl[5] = Nf[3];
     pl[6] = snlm.n; pl[7] = Nh; pl[8] = 10; pl[9] = inc.n; pl[10] = 2;
-    int N = 0;
-    for (int k = 0; k < 11; k++) N += pl[k];
-    Block &A = out.all;
-    A.init(N);
-    auto put = [&](Block &b, int pos) {
-        for (int i = 0; i < b.n; i++) {
-            A.names[(size_t)(pos + i)] = b.names[(size_t)i];
-            A.prior_names[(size_t)(pos + i)] = b.prior_names[(size_t)i];
-            A.inputs[(size_t)(pos + i)] = b.inputs[(size_t)i];
-            A.relax[(size_t)(pos + i)] = b.relax[(size_t)i];
-            for (int k = 0; k < 4; k++) A.pr(k, pos + i) = b.pr(k, i);
-        }
-    };
-    int p0 = 0;
-    put(height, p0); p0 += pl[0];
-    put(vis, p0); p0 += pl[1];
-    put(freq, p0); p0 += pl[2] + pl[3] + pl[4] + pl[5];
-    put(snlm, p0); p0 += pl[6];
-    put(width, p0); p0 += pl[7];
-    put(noise, p0); p0 += pl[8];
-    put(inc, p0); p0 += pl[9];
-    A.fill("Truncation parameter", "Fix", trunc_c > 0 ? trunc_c : 10000., {}, p0, 1);
-    A.fill("Switch for fit of Amplitudes or Heights", "Fix", (double)do_amp, {}, p0 + 1, 1);
-    for (int k = 0; k < 10; k++) out.extra[k] = extra[k];
-    out.range[0] = mf.range[0]; out.range[1] = mf.range[1];
-    out.dnu = mf.dnu; out.c_l = mf.c_l;
-    out.model_id = aj ? TAMCMC_MODEL_MS_GLOBAL_AJ : (v2 ? TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC_V2 : TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC);
-    out.prior_class = 2;  // io_MS_Global, Config/default/priors_ctrl.list
-    out.model_name = model;
-    for (int i = 0; i < N; i++)
-        if (prior_id(A.prior_names[(size_t)i]) < 0) return fail(TAMCMC_IO_ERR_SYNTAX, "unknown prior keyword: " + A.prior_names[(size_t)i]);
-    return TAMCMC_IO_OK;
+    assemble(out, {&height, &vis, &freq, &snlm, &width, &noise, &inc}, trunc_c, do_amp);
+    const int id = aj ? TAMCMC_MODEL_MS_GLOBAL_AJ : (v2 ? TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC_V2 : TAMCMC_MODEL_MS_GLOBAL_A1ETAA3_CLASSIC);
+    return finish(out, mf, extra, id, 2 /* io_MS_Global */, model);
 }
 
 // build_init_asymptotic (io_asymptotic.cpp:32-838, settings_aj_splittings_RGB :841-955) for the red-giant models
@@ -719,53 +727,25 @@ int build_global(const ModelFile &mf, double resol, tamcmc_inputs &out) {
 // and priors: set_width_App2016_params_v2 (io_ms_global.cpp:1625-1720).  The l=1 modes are not listed: the mode list carries ONE
 // l=1 placeholder line, whose slot becomes the block [delta01, DP1, alpha_g, q, sigma_Hl1, -, Wfactor, Hfactor, fref.., ferr..].
 int build_asymptotic(const ModelFile &mf, double resol, tamcmc_inputs &out) {
-    const long double pi = 3.141592653589793238L;
-    const double Hmin = 1, Hmax = 10000;
     std::string model;
-    int do_amp = 0;
-    for (const auto &c : mf.common) {
-        if (c.name == "model_fullname") model = c.prior;
-        if (c.name == "fit_squareAmplitude_instead_Height") {
-            if (c.prior != "bool") return fail(TAMCMC_IO_ERR_SYNTAX, "fit_squareAmplitude_instead_Height must be 'bool'");
-            do_amp = c.v[0] != 0;
-        }
-    }
-    if (model.empty()) return fail(TAMCMC_IO_ERR_SYNTAX, "the .model file has no model_fullname");
+    int do_amp, lmax;
+    if (int rc = read_switches(mf, model, do_amp)) return rc;
     const bool app = (model == "model_RGB_asympt_aj_AppWidth_HarveyLike_v4"), cte = (model == "model_RGB_asympt_aj_CteWidth_HarveyLike_v4");
     if (!app && !cte) return fail(TAMCMC_IO_ERR_UNSUPPORTED, "model not covered by this loader: " + model);
     double numax = mf.numax, err_numax = mf.err_numax;
     if (app && numax <= 0) return fail(TAMCMC_IO_ERR_SYNTAX, "the AppWidth model needs a positive numax ('!n' line; :100-109)");
     if (cte && numax != -9999 && numax <= 0) return fail(TAMCMC_IO_ERR_SYNTAX, "numax, when given, must be positive (:113-121)");
     if (numax > 0 && err_numax <= 0) err_numax = 0.05 * numax;  // :397-401
-    int lmax = 0;
-    for (const auto &m : mf.modes) lmax = m.l > lmax ? m.l : lmax;
-    if (lmax > 3) return fail(TAMCMC_IO_ERR_SYNTAX, "degrees above 3 are not supported");
-    // ---- eigen table by degree (:146-197): frequencies of every degree, heights and widths of l=0
-    std::vector<double> f, fmin, fmax, h, w;
-    std::vector<int> rf, rh, rw;
-    int Nf[4] = {0, 0, 0, 0};
-    for (int el = 0; el <= lmax; el++)
-        for (const auto &e : mf.eigen) {
-            if ((int)e[0] != el) continue;
-            int match = -1, nmatch = 0;
-            for (size_t k = 0; k < mf.modes.size(); k++)
-                if (mf.modes[k].l == el && mf.modes[k].f > e[1] - 1e-2 && mf.modes[k].f < e[1] + 1e-2) { match = (int)k; nmatch++; }
-            if (nmatch != 1) return fail(TAMCMC_IO_ERR_SYNTAX, "eigen-table frequency without a unique entry in the mode list");
-            f.push_back(e[1]); fmin.push_back(e[2]); fmax.push_back(e[3]);
-            rf.push_back(mf.modes[(size_t)match].rf);
-            if (el == 0) {
-                w.push_back(e[4]); h.push_back(e[5]);
-                rw.push_back(mf.modes[(size_t)match].rW); rh.push_back(mf.modes[(size_t)match].rH);
-            }
-            Nf[el]++;
-        }
-    const int Nh = (int)h.size();
+    if (int rc = max_degree(mf, lmax)) return rc;
+    ModeColumns m;  // frequencies of every degree, heights and widths of l=0 (:146-197)
+    if (int rc = read_eigen_table(mf, lmax, false, false, m)) return rc;
+    const int *Nf = m.Nf;
+    const int Nh = (int)m.h.size();
     if (Nh < 2) return fail(TAMCMC_IO_ERR_EMPTY_RANGE, "the red-giant models need at least two l=0 modes in the eigen table");
     // the slot of the l=1 block is opened when the walk over the listed frequencies meets the first l=1 entry (:327-339): without
     // one, the reference writes the l=2 frequencies over the block
     if (Nf[1] < 1) return fail(TAMCMC_IO_ERR_SYNTAX, "the mode list needs one l=1 placeholder line (its slot holds the mixed-mode parameters)");
-    if (do_amp)
-        for (int i = 0; i < Nh; i++) h[(size_t)i] = (double)(pi * w[(size_t)i] * h[(size_t)i]);
+    if (do_amp) heights_to_amplitudes(m);
     const std::string hname = do_amp ? "Amplitude_l0_rgb" : "Height_l0_rgb";
     // ---- nodes of the bias spline (:251-283)
     const int Nferr = (int)mf.hyper.size();
@@ -790,13 +770,13 @@ int build_asymptotic(const ModelFile &mf, double resol, tamcmc_inputs &out) {
     height.init(Nh); vis.init(lmax); inc.init(1); noise.init(10); snlm.init(10);
     width.init(app ? 6 : 1);
     freq.init(Nf[0] + Nmixed + Nf[2] + Nf[3]);
-    for (int i = 0; i < Nh; i++) height.fill(hname, rh[(size_t)i] ? "Jeffreys" : "Fix", h[(size_t)i], {Hmin, Hmax, -9999., -9999.}, i, 0);
+    height.fill_vect(m.h, m.rh, hname, "Jeffreys", {Hmin, Hmax, -9999., -9999.}, 0, 0);
     // l=0, then (after the block) l=2 and l=3 frequencies (:321-340)
     auto put_freqs = [&](const std::string &name, const std::string &prior, double s1, double s2) {
         int cpt = 0;
-        for (int i = 0; i < (int)f.size(); i++) {
+        for (int i = 0; i < (int)m.f.size(); i++) {
             if (i < Nf[0] || i >= Nf[0] + Nf[1]) {
-                freq.fill(name, rf[(size_t)i] ? prior : "Fix", f[(size_t)i], {fmin[(size_t)i], fmax[(size_t)i], s1, s2}, cpt, 0);
+                freq.fill(name, m.rf[(size_t)i] ? prior : "Fix", m.f[(size_t)i], {m.fmin[(size_t)i], m.fmax[(size_t)i], s1, s2}, cpt, 0);
                 cpt++;
             } else if (i == Nf[0]) cpt += Nmixed;
         }
@@ -821,68 +801,55 @@ int build_asymptotic(const ModelFile &mf, double resol, tamcmc_inputs &out) {
     double extra[10] = {1, 2., 0.2, 0, 3, 0, 0, 0, 0, 0};  // :413-424: smoothness on, 2 muHz, |a3/a1| <= 0.2, no height normalisation, v4 priors
     double trunc_c = -1, model_type = -1, bias_type = -1;
     int aj_count = 0;
-    auto no_auto = [&](const Common &c) { return c.prior == "Fix_Auto" ? fail(TAMCMC_IO_ERR_SYNTAX, c.name + " cannot be Fix_Auto") : 0; };
     auto fixed_only = [&](const Common &c) { return c.prior != "Fix" ? fail(TAMCMC_IO_ERR_SYNTAX, c.name + " must be 'Fix <value>'") : 0; };
     static const struct { const char *a, *b, *c; int pos; } rot[8] = {
         {"rot_env", "Rot_env", "a1_env", 0}, {"rot_core", "Rot_core", "a1_core", 1}, {"a2_core", "", "", 2}, {"a2_env", "", "", 3},
         {"a3_env", "", "", 4}, {"a4_env", "", "", 5}, {"a5_env", "", "", 6}, {"a6_env", "", "", 7}};  // slots as the reference fills them (:846-925)
+    // ---- the keywords, in file order: a later line overrides an earlier one.  Splitting_a1, Splitting_a3 and the cos/sin pair are
+    //      NOT read here: slot 0 of this splitting block is rot_env
     for (const auto &c : mf.common) {
         const std::string &n = c.name;
-        if (n == "freq_smoothness" || n == "Freq_smoothness") {
-            if (c.prior != "bool") return fail(TAMCMC_IO_ERR_SYNTAX, "freq_smoothness must be 'bool'");
-            extra[0] = c.v[0];
-            extra[1] = c.v[1];
-        } else if (n == "trunc_c") {
-            if (int rc = fixed_only(c)) return rc;
+        int rc = 0;
+        if (named(c, "freq_smoothness")) rc = kw_freq_smoothness(c, extra);
+        else if (n == "trunc_c") {
+            if (int e = fixed_only(c)) return e;
             trunc_c = c.v[0];
         } else if (n == "model_type") {
-            if (int rc = fixed_only(c)) return rc;
+            if (int e = fixed_only(c)) return e;
             model_type = c.v[0];
         } else if (n == "bias_type") {
-            if (int rc = fixed_only(c)) return rc;
+            if (int e = fixed_only(c)) return e;
             bias_type = (Nfix != nnames - 1) ? c.v[0] : 0;  // all nodes fixed: no bias (:462-468)
-        } else if (n == "Frequency" || n == "frequency") {
+        } else if (named(c, "frequency")) {
             if (c.prior != "GUG" && c.prior != "Uniform") return fail(TAMCMC_IO_ERR_SYNTAX, "Frequency prior must be GUG or Uniform");
             put_freqs("Frequency_l", c.prior, c.prior == "GUG" ? c.v[3] : -9999., c.prior == "GUG" ? c.v[4] : -9999.);
         } else if (n == "delta01") {
             if (c.prior == "Fix_Auto") freq.fill("delta01", "Uniform", 0.5 * mf.dnu / 100, {-mf.dnu / 100, mf.dnu / 100, -9999., -9999.}, Nf[0], 0);
             else freq.fill("delta01", c.prior, c.v[0], c.v, Nf[0], 1);
         } else if (n == "DP1" || n == "alpha_g" || n == "q" || n == "sigma_Hl1" || n == "Wfactor" || n == "Hfactor") {
-            if (int rc = no_auto(c)) return rc;
             const int off = n == "DP1" ? 1 : n == "alpha_g" ? 2 : n == "q" ? 3 : n == "sigma_Hl1" ? 4 : n == "Wfactor" ? 6 : 7;
-            freq.fill(n, c.prior, c.v[0], c.v, Nf[0] + off, 1);
-        } else if (n == "height" || n == "Height" || n == "amplitude" || n == "Amplitude") {
-            if (int rc = no_auto(c)) return rc;
-            for (int i = 0; i < Nh; i++) height.fill(hname, rh[(size_t)i] ? c.prior : "Fix", h[(size_t)i], c.v, i, 0);
-        } else if ((n == "width" || n == "Width") && cte) {  // one width: the mean of the listed l=0 widths (:633-648)
+            rc = put_keyword(c, freq, n, Nf[0] + off);
+        } else if (is_height(c)) rc = kw_height_l0(c, m, hname, height);
+        else if (named(c, "width") && cte) {  // one width: the mean of the listed l=0 widths (:633-648)
             if (c.prior != "Fix_Auto") return fail(TAMCMC_IO_ERR_SYNTAX, "the CteWidth model takes 'Width Fix_Auto'");
             double mean = 0;
-            for (int i = 0; i < Nh; i++) mean = mean + w[(size_t)i] / Nh;
+            for (int i = 0; i < Nh; i++) mean = mean + m.w[(size_t)i] / Nh;
             width.fill("Width_l", "Jeffreys", mean, {resol, mf.dnu / 3., -9999., -9999.}, 0, 0);
-        } else if (n == "asymetry" || n == "Asymetry") {
-            if (int rc = no_auto(c)) return rc;
-            snlm.fill("Lorentzian_asymetry", c.prior, c.v[0], c.v, 9, 1);
-        } else if (n == "visibility_l1" || n == "Visibility_l1" || n == "visibility_l2" || n == "Visibility_l2" || n == "visibility_l3" ||
-                   n == "Visibility_l3") {
-            if (int rc = no_auto(c)) return rc;
-            const int k = n.back() - '0';
-            if (lmax >= k) vis.fill(std::string("Visibility_l") + n.back(), c.prior, c.v[0], c.v, k - 1, 1);
-        } else if (n == "inclination" || n == "Inclination") {
-            if (int rc = no_auto(c)) return rc;
-            inc.fill("Inclination", c.prior, c.v[0] >= 90 ? 89.99999 : c.v[0], c.v, 0, 1);
-        } else if (n == "asphericity_eta" || n == "Asphericity_eta") {
-            snlm.names[8] = "eta0_switch"; snlm.prior_names[8] = "Fix"; snlm.relax[8] = 0; snlm.inputs[8] = 0;
-        } else if (n == "eta0_switch") {
-            if (int rc = fixed_only(c)) return rc;
+        } else if (named(c, "asymetry")) rc = kw_asymmetry(c, snlm, 9);
+        else if (is_visibility(c)) rc = kw_visibility(c, lmax, vis);
+        else if (named(c, "inclination")) rc = kw_inclination(c, inc);
+        else if (named(c, "asphericity_eta")) snlm.fix_at(8, "eta0_switch", 0);
+        else if (n == "eta0_switch") {
+            if (int e = fixed_only(c)) return e;
             snlm.fill("eta0_switch", "Fix", c.v[0], c.v, 8, 1);
         } else {
             for (const auto &r : rot)
                 if (n == r.a || n == r.b || n == r.c) {
-                    if (int rc = no_auto(c)) return rc;
-                    snlm.fill(r.a, c.prior, c.v[0], c.v, r.pos, 1);
+                    if (int e = put_keyword(c, snlm, r.a, r.pos)) return e;
                     aj_count++;
                 }
         }
+        if (rc) return rc;
     }
     if (aj_count != 8) return fail(TAMCMC_IO_ERR_SYNTAX, "the red-giant models need the 8 keywords rot_env, rot_core, a2_core, a2_env, a3_env ... a6_env (:712-718)");
     if ((model_type == -1) != (bias_type == -1)) return fail(TAMCMC_IO_ERR_SYNTAX, "model_type and bias_type must both be given (:744-748)");
@@ -904,48 +871,34 @@ int build_asymptotic(const ModelFile &mf, double resol, tamcmc_inputs &out) {
         width.fill("width:Appourchaux_v2:DeltaGammadip", "Uniform", o[5], {0., 15., -9999., -9999.}, 5, 0);
     }
     fill_noise_global(mf, noise);
-    // ---- assemble (:724-822)
+    // ---- assemble (:724-822): heights, visibilities, frequencies with the mixed-mode block, splitting block, widths, noise,
+    //      inclination, then the six trailing parameters
     int *pl = out.plength;
     pl[0] = Nh; pl[1] = lmax; pl[2] = Nf[0]; pl[3] = Nmixed; pl[4] = Nf[2]; pl[5] = Nf[3];
     pl[6] = snlm.n; pl[7] = width.n; pl[8] = 10; pl[9] = 1; pl[10] = 6;
-    int N = 0;
-    for (int k = 0; k < 11; k++) N += pl[k];
+    const int p0 = assemble(out, {&height, &vis, &freq, &snlm, &width, &noise, &inc}, trunc_c, do_amp);
     Block &A = out.all;
-    A.init(N);
-    auto put = [&](Block &b, int pos) {
-        for (int i = 0; i < b.n; i++) {
-            A.names[(size_t)(pos + i)] = b.names[(size_t)i];
-            A.prior_names[(size_t)(pos + i)] = b.prior_names[(size_t)i];
-            A.inputs[(size_t)(pos + i)] = b.inputs[(size_t)i];
-            A.relax[(size_t)(pos + i)] = b.relax[(size_t)i];
-            for (int k = 0; k < 4; k++) A.pr(k, pos + i) = b.pr(k, i);
-        }
-    };
-    int p0 = 0;
-    put(height, p0); p0 += pl[0];
-    put(vis, p0); p0 += pl[1];
-    put(freq, p0); p0 += pl[2] + pl[3] + pl[4] + pl[5];
-    put(snlm, p0); p0 += pl[6];
-    put(width, p0); p0 += pl[7];
-    put(noise, p0); p0 += pl[8];
-    put(inc, p0); p0 += pl[9];
-    A.fill("Truncation parameter", "Fix", trunc_c > 0 ? trunc_c : 10000., {}, p0, 1);
-    A.fill("Switch for fit of Amplitudes or Heights", "Fix", (double)do_amp, {}, p0 + 1, 1);
-    A.fill("Maximum limit on random values generated by N(0,sigma_m)", "Fix", mf.dnu / 10., {}, p0 + 2, 1);
-    A.fill("model type ", "Fix", model_type, {}, p0 + 3, 1);
-    A.fill("bias type ", "Fix", bias_type, {}, p0 + 4, 1);
-    A.fill("Nferr ", "Fix", (double)Nferr, {}, p0 + 5, 1);
+    A.fill("Maximum limit on random values generated by N(0,sigma_m)", "Fix", mf.dnu / 10., {}, p0, 1);
+    A.fill("model type ", "Fix", model_type, {}, p0 + 1, 1);
+    A.fill("bias type ", "Fix", bias_type, {}, p0 + 2, 1);
+    A.fill("Nferr ", "Fix", (double)Nferr, {}, p0 + 3, 1);
     if (bias_type == 0 && Nfix != nnames - 1)  // no bias asked for: the node values are pinned to 0 (:825-833)
-        for (int i = 0; i < N; i++)
+        for (int i = 0; i < A.n; i++)
             if (A.names[(size_t)i] == "ferr_bias") A.fill("ferr_bias", "Fix", 0, {}, i, 1);
-    for (int k = 0; k < 10; k++) out.extra[k] = extra[k];
-    out.range[0] = mf.range[0]; out.range[1] = mf.range[1];
-    out.dnu = mf.dnu; out.c_l = mf.c_l;
-    out.model_id = app ? 25 : 27;  // TAMCMC_MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4 / _CTEWIDTH_V4
-    out.prior_class = 4;           // io_asymptotic, Config/default/priors_ctrl.list
-    out.model_name = model;
-    for (int i = 0; i < N; i++)
-        if (prior_id(A.prior_names[(size_t)i]) < 0) return fail(TAMCMC_IO_ERR_SYNTAX, "unknown prior keyword: " + A.prior_names[(size_t)i]);
+    return finish(out, mf, extra, app ? TAMCMC_MODEL_RGB_ASYMPT_AJ_APPWIDTH_V4 : TAMCMC_MODEL_RGB_ASYMPT_AJ_CTEWIDTH_V4, 4 /* io_asymptotic */, model);
+}
+
+// the three `.model` loaders: read the file (slice_ind < 0: ONE range), build, hand the inputs over only when both succeeded
+int load_model(const char *model_path, int slice_ind, double resol, int (*build)(const ModelFile &, double, tamcmc_inputs &),
+                      tamcmc_inputs **out) {
+    if (!model_path || !out) return fail(TAMCMC_IO_ERR_ARG, "bad argument");
+    ModelFile mf;
+    int rc = read_model_file(model_path, slice_ind, mf);
+    if (rc) return rc;
+    tamcmc_inputs *in = new tamcmc_inputs();
+    rc = build(mf, resol, *in);
+    if (rc) { delete in; return rc; }
+    *out = in;
     return TAMCMC_IO_OK;
 }
 
@@ -1006,39 +959,14 @@ int tamcmc_io_select_range(const double *table, int64_t nrows, int64_t ncols, in
 }
 
 int tamcmc_io_load_model_local(const char *model_path, int slice_ind, double resol, tamcmc_inputs **out) {
-    if (!model_path || !out || slice_ind < 0) return fail(TAMCMC_IO_ERR_ARG, "bad argument");
-    ModelFile mf;
-    int rc = read_model_file(model_path, slice_ind, mf);
-    if (rc) return rc;
-    tamcmc_inputs *in = new tamcmc_inputs();
-    rc = build_local(mf, resol, *in);
-    if (rc) { delete in; return rc; }
-    *out = in;
-    return TAMCMC_IO_OK;
+    if (slice_ind < 0) return fail(TAMCMC_IO_ERR_ARG, "bad argument");
+    return load_model(model_path, slice_ind, resol, build_local, out);
 }
-
 int tamcmc_io_load_model_global(const char *model_path, double resol, tamcmc_inputs **out) {
-    if (!model_path || !out) return fail(TAMCMC_IO_ERR_ARG, "bad argument");
-    ModelFile mf;
-    int rc = read_model_file(model_path, -1, mf);
-    if (rc) return rc;
-    tamcmc_inputs *in = new tamcmc_inputs();
-    rc = build_global(mf, resol, *in);
-    if (rc) { delete in; return rc; }
-    *out = in;
-    return TAMCMC_IO_OK;
+    return load_model(model_path, -1, resol, build_global, out);
 }
-
 int tamcmc_io_load_model_asymptotic(const char *model_path, double resol, tamcmc_inputs **out) {
-    if (!model_path || !out) return fail(TAMCMC_IO_ERR_ARG, "bad argument");
-    ModelFile mf;
-    int rc = read_model_file(model_path, -1, mf);
-    if (rc) return rc;
-    tamcmc_inputs *in = new tamcmc_inputs();
-    rc = build_asymptotic(mf, resol, *in);
-    if (rc) { delete in; return rc; }
-    *out = in;
-    return TAMCMC_IO_OK;
+    return load_model(model_path, -1, resol, build_asymptotic, out);
 }
 
 // Config::read_inputs_prior_Simple_Matrix (config.cpp:560-664), the dialect of the Gaussian-envelope fits (config.cpp:1996-2007):
