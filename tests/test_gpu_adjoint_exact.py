@@ -27,6 +27,9 @@ import adjoint_reference as ar
 pytestmark = pytest.mark.gpu
 
 CONFIGS = [("fast", 64, 8), ("fast", 256, 4), ("fast_direct", 64, 8), ("fast_direct", 256, 4)]   # as test_gpu_adjoint.py
+# the geometries that have no DELTA kernel (the adjoint batch is allowed in any geometry, fd_route.h): on the smallest case of each test
+NO_DELTA_CONFIGS = [(mode, wg, K) for mode in ("fast", "fast_direct") for wg, K in ((256, 1), (256, 2), (64, 16))]
+SMALLEST_FIELD_CASE, SMALLEST_CASE = "corner", "id11"   # (16 rows on 4000 bins, the 50-digit reference shared; 6 rows on 4000 bins)
 U = Fraction(1, 2 ** 53)
 TOL_G = 1e-11
 
@@ -58,7 +61,7 @@ def test_fields_against_the_50_digit_definition(pkg, synth, ctxs, name):
     c = ac.case(synth, name)
     s, y = c.star, ac.spectrum(pkg, c)
     E = c.idx.size + 1
-    for cfg in CONFIGS:
+    for cfg in CONFIGS + (NO_DELTA_CONFIGS if name == SMALLEST_FIELD_CASE else []):
         ctx = _configured(pkg, ctxs, cfg, s, y)
         tabs, noise, nh, nn, status = ctx.fd_batch_tables(s.model_id, c.P, s.plength, c.idx, c.h)
         assert (status == 0).all()
@@ -123,10 +126,17 @@ def test_contraction_replayed_exactly(pkg, synth, ctxs, name):
     id3, id11, id13: base asymmetry != 0 with the asymmetry free, so G[row][15] is contracted -- asserted.  rows64 / rows68 / rows132 /
     id12 / id14: base asymmetry 0, where the component's likelihood share is exactly 0 (the header's rule).  corner_neg: negative steps.
     rows68_asym: steps of 2e-3 relative, so that perturbed rows have another window than the base row -- asserted on the exported tables
-    -- which the kernel must not read.  corner_negnoise: a negative Harvey height and a negative white noise in the vector."""
+    -- which the kernel must not read.  corner_negnoise: a negative Harvey height and a negative white noise in the vector.
+    id11, the smallest case, also at 256 x 1, 256 x 2 and 64 x 16 in both FAST modes: the geometries whose base launch no other adjoint
+    test runs."""
+    for cfg in [CONFIGS[0]] + (NO_DELTA_CONFIGS if name == SMALLEST_CASE else []):
+        _contraction_replayed_exactly(pkg, synth, ctxs, name, cfg)
+
+
+def _contraction_replayed_exactly(pkg, synth, ctxs, name, cfg):
     c = ac.case(synth, name)
     s, y = c.star, ac.spectrum(pkg, c)
-    ctx = _configured(pkg, ctxs, CONFIGS[0], s, y)
+    ctx = _configured(pkg, ctxs, cfg, s, y)
     E = c.idx.size + 1
     G, Gn = ctx.adjoint_table(s.model_id, c.P, s.plength, ac.TEMPS, ac.P_EXP)
     tabs, noise, nh, nn, status = ctx.fd_batch_tables(s.model_id, c.P, s.plength, c.idx, c.h)
@@ -136,7 +146,7 @@ def test_contraction_replayed_exactly(pkg, synth, ctxs, name):
     if c.rows is not None:
         assert all(tabs[ch * E].size == c.rows for ch in range(3))
     worst, seen, live, dev = _replay(name, G, Gn, tabs, noise, nn, g, c.P, c.idx, c.h, ac.TEMPS, ac.P_EXP, E, 3)
-    print("\n%s: %d rows, worst |dS_dev - dS_exact| at %.3f of the rounding bound; fields contracted %s" % (name, tabs[0].size, worst, sorted(seen)))
+    print("\n%s %s: %d rows, worst |dS_dev - dS_exact| at %.3f of the rounding bound; fields contracted %s" % (name, cfg, tabs[0].size, worst, sorted(seen)))
     # the comparison is not between zeros: a component without a term is the asymmetry at asym = 0, an entry of a Harvey term with tau = 0
     # or (ids 13, 14) a height the model never reads
     dead_ok = c.unread(pkg) if name in ("id13", "id14") else np.zeros((3, c.idx.size), dtype=bool)

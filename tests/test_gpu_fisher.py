@@ -18,6 +18,8 @@ import fisher_numpy as fn
 pytestmark = pytest.mark.gpu
 
 CONFIGS = [("fast", 64, 8), ("fast", 256, 4), ("fast_direct", 64, 8), ("fast_direct", 256, 4)]   # arithmetic, workgroup, bins per thread
+# the geometries that have no DELTA kernel (the Rows route is allowed in any geometry, fd_route.h): on the smallest case, c2
+NO_DELTA_CONFIGS = [(mode, wg, K) for mode in ("fast", "fast_direct") for wg, K in ((256, 1), (256, 2), (64, 16))]
 
 
 @pytest.fixture(scope="module")
@@ -54,11 +56,24 @@ def test_weighted_gram_is_exact_on_small_integers(pkg, ctxs, N):
             assert np.array_equal(c.weighted_gram(A, wt), G)
 
 
+def test_weighted_gram_does_not_see_the_tile_geometry(pkg, ctxs):
+    """The Gram kernel has its own slabs (FISHER_SLAB bins per workgroup): the likelihood tile's geometry option must not leak into it.
+    N = 17 on a context set to 64 x 16, then back at 64 x 8."""
+    c = ctxs["fast"]
+    c.set_option(pkg.OPT_WORKGROUP, 64)
+    c.set_option(pkg.OPT_BINS_PER_THREAD, 16)
+    try:
+        test_weighted_gram_is_exact_on_small_integers(pkg, ctxs, 17)
+    finally:
+        c.set_option(pkg.OPT_BINS_PER_THREAD, 8)
+
+
 @pytest.mark.parametrize("name", ["c2", "corner", "c3_asym"])
 def test_fisher_within_the_row_tolerance_of_the_yardstick(pkg, oracle, synth, ctxs, name):
     """c2: Nv 21, 4000 bins; corner: Nv 33, 4000 bins, l = 3 rows, clamped windows, asymmetry, a switched-off Harvey term (two variables whose
     rows of F are zero); c3_asym: Nv 57, 20 000 bins, four 16x16 blocks per side.
-    The largest |F_dev - F_ref| / B of every configuration is printed; DESIGN section 9 records it (it has to stay below 0.5)."""
+    The largest |F_dev - F_ref| / B of every configuration is printed; DESIGN section 9 records it (it has to stay below 0.5).
+    c2 also at 256 x 1, 256 x 2 and 64 x 16 in both FAST modes."""
     star, y, F_ref, U, happ, h = fn.cached(pkg, oracle, synth, name)
     idx = star.index_to_relax
     B = fn.bound(U, happ, star.x.size)
@@ -66,12 +81,12 @@ def test_fisher_within_the_row_tolerance_of_the_yardstick(pkg, oracle, synth, ct
     if name == "corner":
         assert dead.size == 2 and not F_ref[dead].any()
     print("\n%s: Nv %d, bound at most %.2e, median %.2e of sqrt(F_jj F_kk)" % (name, idx.size, np.max(B / fn.scale(F_ref)), np.median(B / fn.scale(F_ref))))
-    for cfg in CONFIGS:
+    for cfg in CONFIGS + (NO_DELTA_CONFIGS if name == "c2" else []):
         c = _configured(pkg, ctxs, cfg, star, y)
         F = c.fisher(star.model_id, star.params, star.plength, idx, h)[0]
         assert c.last_fisher_status == 0 and np.all(np.isfinite(F))
         ratio = np.max(np.abs(F - F_ref) / B)
-        print("%s %s: largest |F_dev - F_ref| / B = %.3f" % (name, cfg, ratio))
+        print("%s %s: largest |F_dev - F_ref| / B = %.3f (%.2e)" % (name, cfg, ratio, ratio))
         assert np.all(np.abs(F - F_ref) <= 2 * B), (cfg, np.argwhere(np.abs(F - F_ref) > 2 * B)[:4])
         assert not F[dead].any() and not F[:, dead].any()
 

@@ -458,3 +458,48 @@ def test_random_tables_on_awkward_grids(pkg, ctxs, nx):
             label = "nx %d wg %d evaluation %d" % (nx, wg, b)
             check_rows(label, {k: v[1][b] for k, v in out.items()}, ref_m[b], F, Fa)
             check_logl(label, {k: v[0][b] for k, v in out.items()}, ref_l[b])
+
+
+@pytest.mark.parametrize("wg,K", [(256, 1), (256, 2), (64, 16)])
+def test_geometries_without_a_delta_kernel_take_the_brute_force_route(pkg, oracle, synth, ctxs, wg, K):
+    """The DELTA variant of the likelihood kernel exists at 256 x 4, 64 x 8 and 64 x 4 (kernels.hip: delta_geometry); at the other three
+    geometries fd_route.h sends a windowed request down the brute-force route (the rule itself: test_fd_route.py, on the CPU).  Here the
+    GPU path: with TAMCMC_OPT_FD_WINDOWED = 1, fd_gradient and fd_gradient_posterior return the bits of TAMCMC_OPT_FD_WINDOWED = 0, and
+    tamcmc_hip_get_fd_stats (timing on) reports no delta evaluation for the call.  C2 star, 4000 bins, two chains, both FAST modes; the
+    same calls at 64 x 8 do count their delta evaluations, so the counter is known to be live."""
+    star = synth.make_c2_star(nx=4000)
+    y = _spectrum(oracle, star)
+    idx = star.index_to_relax
+    h = 1e-6 * np.maximum(np.abs(star.params[idx]), 1.0)
+    T = np.array([1.0, 1.7])
+    P = _perturbed(star, 2, np.random.default_rng(14), 0.0003)   # (0.03 %: ~1 muHz on a frequency, inside its prior of +-5 muHz)
+
+    def calls(c):
+        c.reset_kernel_stats()
+        l0, g = c.fd_gradient(star.model_id, P, star.plength, idx, h, T, 1.0)
+        l0p, pr0, gp = c.fd_gradient_posterior(star, P, h, T, 1.0)
+        return (l0, g, l0p, pr0, gp, c.last_grad_prior.copy()), c.fd_stats()
+
+    for name in ("fast", "fast_direct"):
+        c = ctxs[name]
+        c.set_option(pkg.OPT_TIMING, 1)
+        try:
+            c.set_option(pkg.OPT_WORKGROUP, wg)
+            c.set_option(pkg.OPT_BINS_PER_THREAD, K)
+            c.set_spectrum(star.x, y)
+            out = {}
+            for windowed in (0, 1):
+                c.set_option(pkg.OPT_FD_WINDOWED, windowed)
+                out[windowed], stats = calls(c)
+                assert stats == (0, 0), (name, wg, K, windowed, stats)
+            for a, b in zip(out[0], out[1]):
+                assert np.all(np.isfinite(a)) and np.array_equal(a, b), (name, wg, K)
+            assert np.all(out[1][1] != 0.0)
+            c.set_option(pkg.OPT_WORKGROUP, 64)
+            c.set_option(pkg.OPT_BINS_PER_THREAD, 8)
+            c.set_spectrum(star.x, y)
+            _, stats = calls(c)
+            assert stats[1] == 2 * 2 * (idx.size + 1) and stats[0] > 0, (name, stats)
+        finally:
+            c.set_option(pkg.OPT_TIMING, 0)
+            c.set_option(pkg.OPT_FD_WINDOWED, 1)

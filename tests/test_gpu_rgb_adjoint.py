@@ -480,3 +480,39 @@ def test_device_engine_follows_the_host_engine(pkg, small, ctx):
     finally:
         ctx.set_option(pkg.OPT_GRADIENT, pkg.GRADIENT_ADJOINT)
         ctx.set_option(pkg.OPT_RGB_DEVICE_LANGEVIN, 0)
+
+
+def test_a_geometry_without_the_delta_kernel_is_refused_and_leaves_nothing_behind(pkg, small, ctx):
+    """The hybrid batch needs the DELTA variant of the likelihood kernel for its fallback slots (fd_batch.hip, layout): at 64 x 16, which
+    has none, fd_gradient and fd_gradient_posterior return TAMCMC_ERR_BAD_ARG before anything is laid out.  The next calls at 64 x 8 give
+    the bits of a context that never saw the refusal."""
+    star, _ = small
+    idx = star.index_to_relax
+    h = _steps(star.params, idx)
+    P = np.tile(star.params, (2, 1))
+    P[1, idx] *= 1 + 0.002 * np.random.default_rng(12).standard_normal(idx.size)
+    T = [1.0, 1.7]
+    _geometry(pkg, ctx, (64, 16), star)
+    try:
+        with pytest.raises(pkg.TamcmcError) as e:
+            ctx.fd_gradient(star.model_id, P, star.plength, idx, h, T)
+        assert e.value.code == pkg.ERR_BAD_ARG
+        with pytest.raises(pkg.TamcmcError) as e:
+            ctx.fd_gradient_posterior(star, P, h, T)
+        assert e.value.code == pkg.ERR_BAD_ARG
+    finally:
+        _geometry(pkg, ctx, (64, 8), star)
+    l0, g = ctx.fd_gradient(star.model_id, P, star.plength, idx, h, T)
+    l0p, pr0, gp = ctx.fd_gradient_posterior(star, P, h, T)
+    fresh = pkg.HipContext(0, precision=pkg.PRECISION_FAST, timing=True)
+    try:
+        fresh.set_option(pkg.OPT_GRADIENT, pkg.GRADIENT_ADJOINT)
+        fresh.set_option(pkg.OPT_RGB_ADJOINT, 1)
+        _geometry(pkg, fresh, (64, 8), star)
+        l0f, gf = fresh.fd_gradient(star.model_id, P, star.plength, idx, h, T)
+        l0q, pr0q, gq = fresh.fd_gradient_posterior(star, P, h, T)
+    finally:
+        fresh.close()
+    assert np.all(np.isfinite(g)) and np.count_nonzero(g) >= 2 * (idx.size - 3)
+    for a, b in ((l0, l0f), (g, gf), (l0p, l0q), (pr0, pr0q), (gp, gq)):
+        assert np.array_equal(a, b)

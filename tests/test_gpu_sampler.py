@@ -69,9 +69,9 @@ def test_initial_state_matches_oracle(pkg, oracle, synth, ctx):
     s.close()
 
 
-def test_device_engine_follows_host_engine(pkg, oracle, synth, ctx):
-    star = _star_with_data(pkg, oracle, synth)
-    ctx.set_spectrum(star.x, star.y)
+def device_engine_follows_host_engine(pkg, ctx, star):
+    """The criterion of test_device_engine_follows_host_engine on a context that holds `star`'s spectrum, whatever its arithmetic mode
+    and tile geometry (test_gpu_engine_matrix.py runs it on four more)."""
     kw = dict(nchains=6, lambda_temp=1.5, seed=11, Nt_learn=(10**9, 10**9 + 1), periods_learn=(1,), dN_mixing=1)
     h = pkg.Sampler(ctx, star, engine="host", **kw)
     d = pkg.Sampler(ctx, star, engine="device", **kw)
@@ -87,7 +87,15 @@ def test_device_engine_follows_host_engine(pkg, oracle, synth, ctx):
     assert a["iteration"] == b["iteration"] == n
     assert abs(a["swaps"] - b["swaps"]) <= 6 and a["swap_attempts"] == b["swap_attempts"] == n - 1
     assert (sh[:, 0] != sh[0, 0]).any()  # chain 0 moved
+    info = d.info()
     h.close(); d.close()
+    return first_div, info
+
+
+def test_device_engine_follows_host_engine(pkg, oracle, synth, ctx):
+    star = _star_with_data(pkg, oracle, synth)
+    ctx.set_spectrum(star.x, star.y)
+    device_engine_follows_host_engine(pkg, ctx, star)
 
 
 @pytest.mark.parametrize("nchains,dN_mixing,learn", [(7, 1, None), (7, 3, None), (7, 7, (40, 90)), (7, 0, None), (7, 1, (5, 30)),
@@ -101,14 +109,23 @@ def test_fused_steps_are_bitwise_the_lockstep_chain(pkg, oracle, synth, ctx, nch
     still the same chains.
     Third run: the fused steps with TAMCMC_OPT_QUICK_DECIDE = 1 -- every likelihood tile takes the shortcut's fallback, decide() called
     from a tile workgroup with no output record, which by default runs about once in 1e5 tests.  Still the same chains, and the
-    counters prove which path each run took (_check_scheme_counters)."""
+    counters prove which path each run took (_check_scheme_counters).
+    Here on the FAST context at the geometry the library picks for this spectrum; test_gpu_engine_matrix.py calls the same body for
+    every arithmetic mode and every number of bins per lane the fused step is compiled for."""
     star = _star_with_data(pkg, oracle, synth)
     ctx.set_spectrum(star.x, star.y)
+    fused_steps_are_bitwise_the_lockstep_chain(pkg, ctx, star, nchains, dN_mixing, learn)
+
+
+def fused_steps_are_bitwise_the_lockstep_chain(pkg, ctx, star, nchains, dN_mixing, learn, n1=None):
+    """The body of the test of that name, on a context that holds `star`'s spectrum (its arithmetic mode and tile geometry are the
+    caller's).  n1: the length of the first call (default 150 below 8 chains, 700 from there on).  Returns the three runs' info()."""
     Nt = learn if learn else (10**9, 10**9 + 1)
     kw = dict(nchains=nchains, lambda_temp=1.4 if nchains < 10 else 1.2, seed=23, Nt_learn=Nt, periods_learn=(2,), dN_mixing=dN_mixing)
     out, infos = [], []
     fused_scheme = 0 if nchains < 8 else 3        # 3: two chain groups even on this small star (automatic: only when a launch outgrows the GPU)
-    n1 = 150 if nchains < 8 else 700
+    if n1 is None:
+        n1 = 150 if nchains < 8 else 700
     for scheme, forced in ((1, 0), (fused_scheme, 0), (fused_scheme, 1)):
         ctx.set_option(pkg.OPT_STEP_SCHEME, scheme)
         ctx.set_option(pkg.OPT_QUICK_DECIDE, forced)
@@ -142,6 +159,7 @@ def test_fused_steps_are_bitwise_the_lockstep_chain(pkg, oracle, synth, ctx, nch
     assert (out[0][0][:, 0] != out[0][0][0, 0]).any()
     if dN_mixing:
         assert 0 < state["swaps"] <= state["swap_attempts"]
+    return infos
 
 
 def _star_with_close_prior_edges(pkg, oracle, synth):

@@ -10,6 +10,8 @@ logL, relative to the reference's: 1e-12 (STRICT), 1e-11 (both FAST modes).
 Which path a tile took is observable: FAST and FAST_DIRECT run the same near-field and per-bin background code, so their rows are equal
 bit for bit on a tile with no far row and no background series, and differ on a tile that has either.  That pins the far gate and the
 gate of the background series from both sides.
+Every case runs at both geometries of its tile size (one wave x 4, 8, 16 bins per lane; four waves x 1, 2, 4), and which geometry took a
+bin must not show where the arithmetic is stated per bin: test_rows_do_not_show_the_geometry.
 """
 import numpy as np
 import pytest
@@ -31,7 +33,9 @@ K_STRICT = 4.0 * STRICT_WORST_RATIO
 FAST_TOL = 1e-12
 U = 2.0 ** -53
 
-GEOMS = ((64, 8), (256, 4), (64, 4))   # (workgroup, bins per thread): tiles of 512, 1024, 256 bins
+# (workgroup, bins per thread): tiles of 512, 1024, 256 bins from the one-wave / four-wave kernel, then the other kernel's tile of each size
+GEOMS = ((64, 8), (256, 4), (64, 4), (256, 1), (256, 2), (64, 16))
+PAIRS = (((64, 4), (256, 1)), ((64, 8), (256, 2)), ((64, 16), (256, 4)))   # the two geometries of each tile size: 256, 512, 1024 bins
 PARAMS = [(wg, K, c.name) for wg, K in GEOMS for c in tc.cases(wg * K)]
 
 
@@ -110,6 +114,34 @@ def test_directed_case(pkg, ctxs, wg, K, name):
         check_logl(label, {k: v[0][b] for k, v in out.items()}, ref.logL[1][b])
         check_paths(case, b, got["fast"], got["fast_direct"])
     print("STRICT worst ratio of %s/%d: %.2f" % (name, wg * K, worst))
+
+
+@pytest.mark.parametrize("tile_bins,name", [(tb, c.name) for tb in (256, 512, 1024) for c in tc.cases(tb)])
+def test_rows_do_not_show_the_geometry(pkg, ctxs, tile_bins, name):
+    """STRICT is the reference's operation order PER BIN (strict_mult and the STRICT branch of likelihood_terms, loglike_tile.h: rows in
+    table order, one IEEE operation per statement, no value of the tile in any of them), so which lane of which workgroup takes a bin must
+    not show: every case's STRICT row is the same bits at all six geometries -- the two kernels at each tile size and the three tile sizes.
+    FAST_DIRECT is guaranteed less, and that is asserted: its per-bin argument is formed from the bin's offset to the TILE CENTRE
+    (fast_mult: t = fma(x - x_c, 2/gamma, -A_m) with A_m staged per tile) and the common-denominator branch is chosen from a bound on the
+    tile (F_SAFE), so the row depends on the tile's bins -- but on nothing else of the geometry: the two geometries of one tile size
+    (64x4 / 256x1, 64x8 / 256x2, 64x16 / 256x4) stage the same scalars and run the same statements per bin, and the library is built
+    without contraction (every fused operation is an explicit fma).  Their rows are equal bit for bit; across tile sizes they are not
+    claimed equal (x_c differs: roundings of ~1e-16 t) and not compared.  FAST adds sums over lanes (the tile polynomial's coefficients
+    are reduced over WGS / 16 parts in an order that follows the workgroup size): no equality is claimed for it."""
+    ref = tc.reference(tile_bins, name)
+    case = ref.case
+    strict, direct = {}, {}
+    for wg, K in GEOMS:
+        out = run_modes(pkg, {k: ctxs[k] for k in ("strict", "fast_direct")}, case, ref, wg, K)
+        strict[wg, K], direct[wg, K] = out["strict"][1], out["fast_direct"][1]
+    first = strict[GEOMS[0]]
+    assert np.all(np.isfinite(first))
+    for geom in GEOMS[1:]:
+        diff = np.argwhere(strict[geom] != first)
+        assert diff.size == 0, ("STRICT", name, tile_bins, GEOMS[0], geom, len(diff), diff[:4].tolist())
+    for ga, gb in PAIRS:
+        diff = np.argwhere(direct[ga] != direct[gb])
+        assert diff.size == 0, ("FAST_DIRECT", name, tile_bins, ga, gb, len(diff), diff[:4].tolist())
 
 
 def test_far_rows_take_the_polynomial_and_near_rows_do_not(pkg, ctxs):
