@@ -147,9 +147,9 @@ extern "C" {
 #define TAMCMC_OPT_ENVELOPE_DEVICE_ENGINE 13 /* value: 0/1 (default 0) -- 1: tamcmc_sampler_create builds the device-resident engine (engine = 1,
                                         use_drift = 0) for the Gaussian-envelope models, ids 0 and 1; 0: it refuses them with
                                         TAMCMC_ERR_BAD_MODEL.  Read when the sampler is created: changing it afterwards does not affect an
-                                        existing sampler.  The Langevin step of these ids stays on the host-driven engine (engine = 1 with
-                                        use_drift = 1: TAMCMC_ERR_BAD_MODEL whatever this option says); see tamcmc_sampler.h.  Any other
-                                        value: TAMCMC_ERR_BAD_ARG */
+                                        existing sampler.  It admits use_drift = 0 only: the Langevin step of these ids on the device-resident
+                                        engine has its own option, TAMCMC_OPT_ENVELOPE_DEVICE_LANGEVIN, and neither implies the other; see
+                                        tamcmc_sampler.h.  Any other value: TAMCMC_ERR_BAD_ARG */
 #define TAMCMC_OPT_FACTOR_REFRESH 14 /* value R: 0 (default) or 1 -- every adapting iteration factors (Sigma + eps2 I) sigma from scratch; 2 ... 65536 --
                                         the factor follows the Robbins-Monro step by a rank-one update in O(Nvars^2), with a scheduled full
                                         factorisation every R-th adapting iteration (both engines, both samplers, every model; the law and
@@ -160,12 +160,20 @@ extern "C" {
                                         likelihood's share from the analytic gradient, one pass over the bins per chain instead of
                                         Nvars + 1 (see tamcmc_hip_envelope_gradient_sums).  Read at every call.  hstep is still required: it
                                         sets the prior's forward and backward points and is not read by the likelihood's share.
-                                        TAMCMC_GRADIENT_ADJOINT keeps refusing these ids, and the device-resident engine keeps refusing
-                                        use_drift = 1 for them.  Any other value: TAMCMC_ERR_BAD_ARG */
+                                        TAMCMC_GRADIENT_ADJOINT keeps refusing these ids.  The option concerns these host routes only: the
+                                        device-resident engine's Langevin step (TAMCMC_OPT_ENVELOPE_DEVICE_LANGEVIN) has one gradient route,
+                                        the analytic one, and does not read it.  Any other value: TAMCMC_ERR_BAD_ARG */
 #define TAMCMC_OPT_RGB_FISHER 16     /* value: 0/1 (default 0) -- 1: tamcmc_hip_fisher (and with it tamcmc_sampler_seed_proposal_fisher) accepts the
                                         red-giant models, ids 25 and 27, on a FAST or FAST_DIRECT context; 0: it refuses them with
                                         TAMCMC_ERR_BAD_MODEL, whatever TAMCMC_OPT_RGB_ADJOINT says.  Read at every call; nothing else
                                         changes with it.  Any other value: TAMCMC_ERR_BAD_ARG */
+#define TAMCMC_OPT_ENVELOPE_DEVICE_LANGEVIN 17 /* value: 0/1 (default 0) -- 1: tamcmc_sampler_create builds the device-resident engine's Langevin
+                                        sampler (engine = 1, use_drift = 1) for the Gaussian-envelope models, ids 0 and 1; 0: it refuses
+                                        them with TAMCMC_ERR_BAD_MODEL, whatever TAMCMC_OPT_ENVELOPE_DEVICE_ENGINE says.  Independent of that
+                                        option: 13 admits use_drift = 0, 17 admits use_drift = 1.  Read when the sampler is created: changing
+                                        it afterwards does not affect an existing sampler.  One gradient route, the analytic gradient with
+                                        its chain rule on the device in double (tamcmc_sampler.h); TAMCMC_OPT_ENVELOPE_GRADIENT and
+                                        TAMCMC_OPT_PRECISION are not read.  Any other value: TAMCMC_ERR_BAD_ARG */
 #define TAMCMC_FISHER_SLAB 2048     /* bins per workgroup (and per partial matrix) of the Gram kernel of tamcmc_hip_fisher / _weighted_gram */
 
 /* One (n,l) multiplet: <=7 Lorentzian m-components on its truncation window.

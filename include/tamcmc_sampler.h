@@ -96,10 +96,18 @@ int64_t tamcmc_sampler_nvars(const tamcmc_sampler *s);
  *                                  chain from a gradient taken on the new route.
  *                                  Nchains (Nvars + 1) <= 65535.  Host-driven engine: random walk or Langevin, any arithmetic mode
  *                                  (tamcmc_hip_fd_gradient_posterior; the adjoint routes: FAST / FAST_DIRECT)
- *   Gaussian-envelope models       host-driven engine: random walk or Langevin.  Device engine (engine = 1): opt-in, random walk only --
- *     (ids 0/1)                    TAMCMC_ERR_BAD_MODEL at tamcmc_sampler_create unless the context has
- *                                  TAMCMC_OPT_ENVELOPE_DEVICE_ENGINE = 1 at that moment, and with use_drift = 1 whatever the option says:
- *                                  the Langevin step of these ids stays on the host-driven engine.  prior_class must equal model_id.
+ *   Gaussian-envelope models       host-driven engine: random walk or Langevin.  Device engine (engine = 1): opt-in, one option per
+ *     (ids 0/1)                    step -- TAMCMC_ERR_BAD_MODEL at tamcmc_sampler_create unless the context has, at that moment,
+ *                                  TAMCMC_OPT_ENVELOPE_DEVICE_ENGINE = 1 for use_drift = 0 or TAMCMC_OPT_ENVELOPE_DEVICE_LANGEVIN = 1 for
+ *                                  use_drift = 1; neither option implies the other.  prior_class must equal model_id.
+ *                                  Langevin step (use_drift = 1): lockstep kernels only (TAMCMC_INFO_ITER_LOCKSTEP), nothing crosses
+ *                                  PCIe inside an iteration.  One gradient route, the analytic gradient of tamcmc_hip.h
+ *                                  (tamcmc_hip_envelope_gradient_sums) with its chain rule on the device in double;
+ *                                  TAMCMC_OPT_ENVELOPE_GRADIENT is not read.  Under TAMCMC_GRADIENT_ADJOINT tamcmc_sampler_run returns
+ *                                  TAMCMC_ERR_BAD_MODEL before anything is enqueued: the chains, the counters and the held gradients
+ *                                  stay where they were and a later call continues them.  tamcmc_sampler_get_gradient and
+ *                                  _get_last_test as for the other device Langevin samplers; tamcmc_sampler_get_envelope_rows gives
+ *                                  the rows of the last proposals.  The rest of this entry is the random walk's (use_drift = 0):
  *                                  Runs of three or more iterations without adaptation take ONE launch per iteration (k_env_step: every 1024-bin tile of a chain
  *                                  settles the previous test, proposes and evaluates; counted by TAMCMC_INFO_ITER_FUSED /
  *                                  _FUSED_STRETCHES) while Nx <= 32768 (id 1) or 6144 (id 0, whose step repeats the xi pass over the whole
@@ -208,6 +216,14 @@ int tamcmc_sampler_get_tables(const tamcmc_sampler *s, int32_t *shape, void *row
  * A proposal whose log-prior is -inf or NaN, or whose status is not TAMCMC_OK, is rejected whatever its row holds. */
 #define TAMCMC_ENVELOPE_ROW_N 24
 int tamcmc_sampler_get_envelope_rows(const tamcmc_sampler *s, double *rows, double *params, double *logprior, int32_t *status);
+
+/* Audit entry of the device-resident engine's Langevin step for the Gaussian-envelope models (ids 0 / 1 created with
+ * TAMCMC_OPT_ENVELOPE_DEVICE_LANGEVIN; anything else: TAMCMC_ERR_BAD_MODEL; before the first tamcmc_sampler_run: TAMCMC_ERR_BAD_ARG): the
+ * sums the analytic gradient's kernels folded for the LAST iteration's proposals, as the device's chain rule read them -- S [Nchains]
+ * (logL = -p S / T), the tile sums [Nchains x 16] and the xi sums [Nchains x 12] in the kernels' own layout -- read
+ * from the engine's buffers.  With the rows of tamcmc_sampler_get_envelope_rows they are everything the chain rule starts from: a
+ * replay in another arithmetic needs nothing else.  Any pointer may be NULL. */
+int tamcmc_sampler_get_envelope_gradient_sums(const tamcmc_sampler *s, double *S, double *tile_sums, double *xi_sums);
 /* moves [Nchains]: for every chain the number of iterations since creation whose record carries moved = 1 -- the flag the reference
  * stores per iteration and chain (MALA.cpp:543-545; a swap exchanges the pair's flags, :436, :446) and its acceptance diagnostic counts
  * per buffer (Outputs::reject_rate / count_accepted_vals, outputs.cpp:1824-1858).  Differences between two calls / the iterations in

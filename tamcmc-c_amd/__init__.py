@@ -31,6 +31,7 @@ OPT_GRADIENT, GRADIENT_FD, GRADIENT_ADJOINT = 9, 0, 1  # gradient batches: finit
 OPT_RGB_DEVICE_LANGEVIN = 11  # 1: Sampler(use_drift=1, engine="device") is built for the red-giant ids 25 / 27 (default 0: ERR_BAD_MODEL); read at creation
 OPT_ENVELOPE_DEVICE_ENGINE = 13  # 1: Sampler(engine="device", use_drift=0) is built for the Gaussian-envelope ids 0 / 1 (default 0: ERR_BAD_MODEL); read at creation
 OPT_FACTOR_REFRESH = 14  # R: 0 / 1 a full factorisation in every adapting iteration (default); 2 ... 65536 rank-one steps of the proposal factor, a full one every R-th; read at creation
+OPT_ENVELOPE_DEVICE_LANGEVIN = 17  # 1: Sampler(engine="device", use_drift=1) is built for the Gaussian-envelope ids 0 / 1 (default 0: ERR_BAD_MODEL); independent of option 13; read at creation
 OPT_ENVELOPE_GRADIENT = 15  # 1: fd_gradient / fd_gradient_posterior (and the host engine's Langevin step) take the analytic likelihood share for ids 0 / 1 (default 0: brute force); read at every call
 ENVELOPE_GRAD_N, ENVELOPE_KSI_N = 13, 9  # row quantities / xi sums per vector of HipContext.envelope_gradient_sums
 OPT_RGB_ADJOINT = 12  # 1: under GRADIENT_ADJOINT the red-giant ids 25 / 27 take the hybrid adjoint batch (default 0: ERR_BAD_MODEL); read at every call

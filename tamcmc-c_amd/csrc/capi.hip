@@ -55,6 +55,7 @@ int tamcmc_hip_create(tamcmc_hip_ctx **out, int device) {
 // (private, host_capi.cpp) a sampler borrows the context for its whole life
 void tamcmc_hip_ctx_attach(tamcmc_hip_ctx *c) { if (c) c->attached++; }
 int tamcmc_hip_envelope_device_engine(const tamcmc_hip_ctx *c) { return c ? c->envelope_device_engine : 0; }
+int tamcmc_hip_envelope_device_langevin(const tamcmc_hip_ctx *c) { return c ? c->envelope_device_langevin : 0; }
 int tamcmc_hip_factor_refresh(const tamcmc_hip_ctx *c) { return c ? c->factor_refresh : 0; }
 void tamcmc_hip_ctx_detach(tamcmc_hip_ctx *c) {
     if (!c) return;
@@ -122,6 +123,10 @@ int tamcmc_hip_set_option(tamcmc_hip_ctx *c, int option, int64_t value) {
     case TAMCMC_OPT_ENVELOPE_DEVICE_ENGINE:
         if (value < 0 || value > 1) return TAMCMC_ERR_BAD_ARG;
         c->envelope_device_engine = (int)value;
+        return TAMCMC_OK;
+    case TAMCMC_OPT_ENVELOPE_DEVICE_LANGEVIN:
+        if (value < 0 || value > 1) return TAMCMC_ERR_BAD_ARG;
+        c->envelope_device_langevin = (int)value;
         return TAMCMC_OK;
     case TAMCMC_OPT_FACTOR_REFRESH:
         if (value < 0 || value > 65536) return TAMCMC_ERR_BAD_ARG;

@@ -84,6 +84,7 @@ struct tamcmc_hip_ctx {
     int rgb_adjoint = 0;  // 1: under TAMCMC_GRADIENT_ADJOINT the red-giant ids take the hybrid batch (fd_batch.hip; read at every call)
     int rgb_fisher = 0;  // 1: tamcmc_hip_fisher accepts the red-giant ids (fisher.hip: k_fisher_freeze_rgb; read at every call)
     int envelope_device_engine = 0;  // 1: the device-resident engine is built for the Gaussian-envelope ids 0 / 1 (read at sampler creation)
+    int envelope_device_langevin = 0;  // 1: ... and its Langevin step (use_drift = 1) for ids 0 / 1; independent of envelope_device_engine (read at sampler creation)
     int factor_refresh = 0;  // R of TAMCMC_OPT_FACTOR_REFRESH: < 2 a full factorisation per adapting iteration, else rank-one steps (read at sampler creation)
     int envelope_gradient = 0;  // 1: the gradient batches of ids 0 / 1 take the analytic likelihood share (envelope.hip; read at every call)
     // resident spectrum

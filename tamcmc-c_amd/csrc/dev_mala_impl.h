@@ -11,7 +11,10 @@
 //   k_mala_settle   parallel-tempering swap on the post-test outcomes (MALA.cpp:397-461; the stored gradients follow the positions,
 //                   their likelihood share re-tempered), settled state + records, then the next proposal x' = x + drift + L z.
 // Nothing crosses PCIe inside an iteration; the host only enqueues.  Neither kernel knows a model: the red-giant ids (25 / 27, opt-in:
-// TAMCMC_OPT_RGB_DEVICE_LANGEVIN) differ in how the batch builds its tables only (fd_batch.hip: k_fd_rgb_perturb + the pre-step).
+// TAMCMC_OPT_RGB_DEVICE_LANGEVIN) differ in how the batch builds its tables only (fd_batch.hip: k_fd_rgb_perturb + the pre-step).  The
+// Gaussian-envelope ids (0 / 1, opt-in: TAMCMC_OPT_ENVELOPE_DEVICE_LANGEVIN) have no table: their batch is the analytic gradient
+// (k_env_mala_front -> k_env_ksi_grad / k_env_grad / k_env_grad_fold -> k_env_mala_chain), and the two kernels take the likelihood's
+// share as a ready derivative (the READY instantiations; everything behind the gradient is the same text).
 
 struct MalaArgs {
     const double *S, *lpp, *lpm;  // sums / log-priors (forward, backward) of the last finite-difference batch (fd_batch.h)
@@ -21,28 +24,42 @@ struct MalaArgs {
     double fd_step_rel, delta;
     double *grad_prop, *gradP_prop, *drift_cur;  // [C][Nv] gradient (and the prior's share) at the proposals; drift used by the proposals
     double *out;                  // [C][5] post-test outcome: acc, r, logL, logPr, logPost
+    const double *dlogL;          // READY (ids 0 / 1): [C][Nv] d logL / d theta_k, tempered -- the likelihood's share as a ready derivative; S = C sums
 };
 
 // Gradient of the tempered log-posterior at the batch's base point of chain c (compute_gradients, host_mala.cpp; the host's assembly is
 // assemble_gradient, fd_batch.hip): lane k -> g[k], gp[k] (the prior's share) in LDS.  base = the base point's parameter vector.  L0 / pr0 / st0 of the base
 // evaluation are returned to every lane.
+// READY: the likelihood's share is a ready derivative (M.dlogL; LikelihoodShare::Derivative of grad_assemble.h) -- the Gaussian-envelope
+// ids, whose analytic gradient k_env_mala_chain leaves there; no evaluation of theirs can fail, so no status is read.
+template <bool READY>
 __device__ void mala_gradient(const DevSamplerArgs &a, const MalaArgs &M, int c, const double *base, double *g, double *gp, double &L0,
                               double &pr0, int &st0) {
     const int Nv = a.Nv, E = M.E, C = a.C;
     const double T = a.Tcoefs[c];
     auto scaled = [&](double S) { return (-(double)a.pl * S) / T; };  // call_likelihood, model_def.cpp:399-401
-    st0 = M.st[(size_t)c * E];
-    L0 = (st0 != TAMCMC_OK) ? (double)NAN : scaled(M.deltas ? M.S[c] : M.S[(size_t)c * E]);
+    st0 = READY ? TAMCMC_OK : M.st[(size_t)c * E];
+    L0 = (st0 != TAMCMC_OK) ? (double)NAN : scaled((READY || M.deltas) ? M.S[c] : M.S[(size_t)c * E]);
     pr0 = M.lpp[(size_t)c * E];
     for (int k = threadIdx.x; k < Nv; k += blockDim.x) {
         const size_t e = (size_t)c * E + k + 1;
         const double x0 = base[a.index_to_relax[k]];
-        volatile double xp = x0 + M.h[k];
-        const double happ = xp - x0;  // the step actually applied (k_fd_unpack adds the same two doubles)
-        double dl;
-        if (M.st[e] != TAMCMC_OK || st0 != TAMCMC_OK) dl = NAN;
-        else dl = M.deltas ? scaled(M.S[(size_t)C + e]) : scaled(M.S[e]) - L0;
-        double gv = dl / happ;
+        double happ;  // the step actually applied (k_fd_unpack / k_env_mala_front add the same two doubles)
+        if (READY) {
+            const double xp = x0 + M.h[k];  // (IEEE arithmetic, no reassociation: the same value without the volatile's stack slot)
+            happ = xp - x0;
+        } else {
+            volatile double xp = x0 + M.h[k];
+            happ = xp - x0;
+        }
+        double gv;
+        if (READY) gv = M.dlogL[(size_t)c * Nv + k];
+        else {
+            double dl;
+            if (M.st[e] != TAMCMC_OK || st0 != TAMCMC_OK) dl = NAN;
+            else dl = M.deltas ? scaled(M.S[(size_t)C + e]) : scaled(M.S[e]) - L0;
+            gv = dl / happ;
+        }
         if (!isfinite(gv)) gv = 0.0;
         const double prp = M.lpp[e], prm = M.lpm[e];
         double gpv;
@@ -77,14 +94,77 @@ __device__ void mala_drift(const DevSamplerArgs &a, const MalaArgs &M, int m, co
     __syncthreads();
 }
 
+// ---- Gaussian-envelope ids 0 / 1 (opt-in: TAMCMC_OPT_ENVELOPE_DEVICE_LANGEVIN): the gradient batch of a Langevin iteration.  No table and
+// no finite differences of the likelihood: k_env_mala_front (rows, log-priors) -> envelope.hip's analytic kernels on those rows
+// (envelope_grad_stage_enqueue) -> k_env_mala_chain (row quantities -> parameters), then k_mala_test<true> / k_mala_ginit<true>.
+struct EnvMalaArgs {
+    double *pts;            // [C][2 Nv + 1][Np] the base, forward and backward points
+    double *lpp, *lpm;      // [C][Nv + 1] their log-priors, in the finite-difference batch's layout (slot 0: the base point, in both)
+    const double *h;        // [Nv] the steps (k_mala_steps, k_mala_settle)
+    const double *gsum, *ksum;  // [C][16], [C][12] the folded sums of k_env_grad_fold
+    double *dlogL;          // [C][Nv] d logL / d theta_k, tempered
+    double hx;              // the trapezoid step x(1) - x(0)
+};
+
+// Front of the batch.  One thread per point, C (2 Nv + 1) of them: its vector -- the base point `base` [C][Np], theta_k + h_k (the
+// double addition mala_gradient's applied step repeats) or theta_k - h_k -- and its log-prior by pr::prior_serial, as k_env_prior
+// (envelope.hip) does it.  The base point's thread also leaves the chain's row (env_row) where the kernels behind it and the audit
+// entry read it, and the chain's log-prior and status.
+__global__ void __launch_bounds__(64) k_env_mala_front(const DevSamplerArgs a, const EnvMalaArgs V, const double *base) {
+    const int Nv = a.Nv, Np = a.desc.Np, NP = 2 * Nv + 1, E = Nv + 1;
+    const int v = blockIdx.x * 64 + threadIdx.x;
+    if (v >= a.C * NP) return;
+    const int c = v / NP, pt = v - c * NP;
+    const double *b = base + (size_t)c * Np;
+    double *f = V.pts + (size_t)v * Np;
+    for (int i = 0; i < Np; i++) f[i] = b[i];
+    if (pt > 0) {
+        const int k = pt <= Nv ? pt - 1 : pt - 1 - Nv, j = a.index_to_relax[k];
+        f[j] = pt <= Nv ? b[j] + V.h[k] : b[j] - V.h[k];
+    }
+    // (both calls inlined HERE: as one more ordinary call site they change how the compiler inlines the two functions into k_iterate
+    // and k_env_step, which must keep their registers)
+    int st = TAMCMC_OK;
+    double lp;
+    [[clang::always_inline]] lp = (double)pr::prior_serial(a.desc.prior_class, f, nullptr, (long)Np, a.desc.priors, a.desc.priors_switch, nullptr, &st);
+    if (pt == 0) {
+        V.lpp[(size_t)c * E] = lp;
+        V.lpm[(size_t)c * E] = lp;
+        a.logPr_prop[c] = lp;
+        a.status_prop[c] = st;
+        [[clang::always_inline]] env_row(a.desc.model_id, b, a.env_rows[c]);
+    } else if (pt <= Nv) V.lpp[(size_t)c * E + pt] = lp;
+    else V.lpm[(size_t)c * E + pt - Nv] = lp;
+}
+
+// The chain rule on the device, one workgroup of two waves per chain: lane 0 of wave 0 turns the folded sums into dS / d(row
+// quantity), lane 0 of wave 1 forms the row quantities' Jacobian at the base point -- env_grad_rows and env_row_jacobian
+// (envelope_row.h), the text the host runs in long double, here in double --, then lane k contracts them for theta_k
+// (env_chain_contract) and tempers the result as mala_gradient's `scaled` does; an exact zero stays +0.
+__global__ void __launch_bounds__(128) k_env_mala_chain(const DevSamplerArgs a, const EnvMalaArgs V, const double *base) {
+    __shared__ double s_dS[ENV_GRAD_N], s_J[ENV_GRAD_N * 19];
+    const int c = blockIdx.x, tid = threadIdx.x, Nv = a.Nv, id = a.desc.model_id;
+    const int NpJ = id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN ? 19 : 10;
+    if (tid == 0)
+        env_grad_rows<double>(id, a.env_rows[c], V.hx, V.gsum + (size_t)c * ENV_GRAD_NRAWMAX, V.ksum + (size_t)c * ENV_GRAD_NKRAW, s_dS, nullptr);
+    else if (tid == 64) env_row_jacobian<double>(id, base + (size_t)c * a.desc.Np, s_J);
+    __syncthreads();
+    const double T = a.Tcoefs[c];
+    for (int k = tid; k < Nv; k += 128) {
+        const double s = env_chain_contract<double>(s_dS, s_J, NpJ, a.index_to_relax[k]);
+        V.dlogL[(size_t)c * Nv + k] = s == 0.0 ? 0.0 : (-(double)a.pl * s) / T;
+    }
+}
+
 // initial gradient: the batch ran on the chains' CURRENT positions (parity P)
+template <bool READY>
 __global__ void __launch_bounds__(TB) k_mala_ginit(const DevSamplerArgs a, const MalaArgs M, const int P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     double *g = (double *)s_raw, *gp = g + a.Nv;
     const int m = blockIdx.x, Nv = a.Nv, C = a.C;
     double L0, pr0;
     int st0;
-    mala_gradient(a, M, m, a.params_cur + ((size_t)P * C + m) * a.desc.Np, g, gp, L0, pr0, st0);
+    mala_gradient<READY>(a, M, m, a.params_cur + ((size_t)P * C + m) * a.desc.Np, g, gp, L0, pr0, st0);
     for (int k = threadIdx.x; k < Nv; k += TB) {
         a.grad_cur[((size_t)P * C + m) * Nv + k] = g[k];
         a.gradP_cur[((size_t)P * C + m) * Nv + k] = gp[k];
@@ -96,7 +176,8 @@ __global__ void k_mala_steps(const DevSamplerArgs a, const MalaArgs M) {
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < a.Nv; k += gridDim.x * blockDim.x) M.h[k] = M.fd_step_rel * fmax(fabs(a.mu[k]), 1e-3);
 }
 
-// The MH test of iteration `it` for chain m, after the finite-difference batch of the proposals (state of parity P).
+// The MH test of iteration `it` for chain m, after the gradient batch of the proposals (state of parity P).
+template <bool READY>
 __global__ void __launch_bounds__(TB) k_mala_test(const DevSamplerArgs a, const MalaArgs M, const long it, const int P, const int learn,
                                                   double *scratch) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
@@ -114,7 +195,7 @@ __global__ void __launch_bounds__(TB) k_mala_test(const DevSamplerArgs a, const 
     const double *cur_v = a.vars_cur + ((size_t)P * C + m) * Nv;
     double L0, pr0;
     int st0;
-    mala_gradient(a, M, m, prop_p, g, gp, L0, pr0, st0);
+    mala_gradient<READY>(a, M, m, prop_p, g, gp, L0, pr0, st0);
     for (int k = tid; k < Nv; k += TB) { M.grad_prop[(size_t)m * Nv + k] = g[k]; M.gradP_prop[(size_t)m * Nv + k] = gp[k]; }
     mala_drift(a, M, m, g, dp, s_red);
     const double *dc = M.drift_cur + (size_t)m * Nv;

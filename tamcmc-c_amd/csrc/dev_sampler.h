@@ -102,6 +102,9 @@ class DevSampler {
     // Audit (tamcmc_sampler_get_envelope_rows), ids 0 / 1: per chain the row of the last iteration's proposal (EnvRow as 24 doubles, the
     // layout of tamcmc_sampler.h), the vector it was built from (params_prop of that iteration's parity), its log-prior and status
     int download_envelope_rows(double *rows, double *params, double *logPr, int32_t *status);
+    // Audit (tamcmc_sampler_get_envelope_gradient_sums), ids 0 / 1 with use_drift: what k_env_grad_fold left for the last iteration's
+    // proposals -- S [C], the tile sums [C x 16], the xi sums [C x 12] -- before the chain rule on the device
+    int download_envelope_sums(double *S, double *tile_sums, double *xi_sums);
     int run(long it0, long n_iter, const char *learn, double *samples, double *stats);
 };
 

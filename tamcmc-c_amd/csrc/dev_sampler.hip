@@ -37,6 +37,8 @@
 //     route evaluates it with envelope.hip's kernels on the group's stream (envelope_stage_enqueue) in place of k_loglike.  Stretches
 //     without adaptation run as ONE launch per iteration (k_env_step: every tile of a chain settles, proposes and evaluates) for
 //     spectra up to env_step_max_bins() bins (id 1: 32 768; id 0: 6 144, the measured crossover); the fused step (A) is not used.
+//     Their Langevin step (opt-in of its own: TAMCMC_OPT_ENVELOPE_DEVICE_LANGEVIN) is the Langevin engine below with the analytic gradient
+//     as its batch (dev_mala_impl.h: k_env_mala_front, envelope_grad_stage_enqueue, k_env_mala_chain), lockstep only.
 // All per-iteration state is double-buffered by parity: a workgroup reads parity P and writes parity P^1, so the swap needs no
 // inter-workgroup synchronisation inside (B) and a launch never overwrites what it still reads in (A).  Both schemes keep the
 // chains' state in the same arrays; a stretch hands over to the next with the parity only.
@@ -137,9 +139,9 @@ int DevSampler::Impl::validate(const DevSamplerInit &in) {
     rgb = is_rgb_model(in.model_id);
     env.on = is_envelope_model(in.model_id);
     if (env.on) {
-        // opt-in (TAMCMC_OPT_ENVELOPE_DEVICE_ENGINE at creation: tamcmc_sampler_create has refused already, before building anything); the
-        // Langevin step of these ids stays on the host engine
-        if (!c->envelope_device_engine || in.use_drift) return TAMCMC_ERR_BAD_MODEL;
+        // opt-in, one option per step (read at creation: tamcmc_sampler_create has refused already, before building anything):
+        // TAMCMC_OPT_ENVELOPE_DEVICE_ENGINE admits the random walk, TAMCMC_OPT_ENVELOPE_DEVICE_LANGEVIN the Langevin step; neither implies the other
+        if (!(in.use_drift ? c->envelope_device_langevin : c->envelope_device_engine)) return TAMCMC_ERR_BAD_MODEL;
         if (in.prior_class != in.model_id) return TAMCMC_ERR_BAD_MODEL;  // priors_ctrl.list pairs class 0 with id 0, class 1 with id 1
         if (in.Np < envelope_nparams(in.model_id) || c->Nx > 0x7fffffff / 2) return TAMCMC_ERR_BAD_ARG;
     }
@@ -248,6 +250,21 @@ int DevSampler::Impl::Langevin::create(Impl &I, const DevSamplerInit &in) {
     DCHK(I.mem.dalloc(&a.grad_cur, 2 * C * Nv)); DCHK(I.mem.dalloc(&a.gradP_cur, 2 * C * Nv));
     DCHK(I.mem.dalloc(&mala.grad_prop, C * Nv)); DCHK(I.mem.dalloc(&mala.gradP_prop, C * Nv)); DCHK(I.mem.dalloc(&mala.drift_cur, C * Nv));
     DCHK(I.mem.dalloc(&mala.out, C * 5));
+    if (!I.env.on) return TAMCMC_OK;
+    // ids 0 / 1: the analytic batch (dev_mala_impl.h) in place of the finite-difference one
+    const size_t Np = (size_t)in.Np, E = Nv + 1, Nx = (size_t)a.desc.Nx, ntiles = (Nx + ETILE - 1) / ETILE, nchunk = (Nx + ECHUNK - 1) / ECHUNK;
+    const bool kal = in.model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN;
+    EnvMalaArgs &k = envb.k;
+    EnvGradBuffers &g = envb.g;
+    double *gsum, *ksum;
+    DCHK(I.mem.dalloc(&k.pts, C * (2 * Nv + 1) * Np)); DCHK(I.mem.dalloc(&k.lpp, C * E)); DCHK(I.mem.dalloc(&k.lpm, C * E));
+    DCHK(I.mem.dalloc(&envb.h, Nv)); DCHK(I.mem.dalloc(&k.dlogL, C * Nv));
+    DCHK(I.mem.dalloc(&g.S, C)); DCHK(I.mem.dalloc(&gsum, C * ENV_GRAD_NRAWMAX)); DCHK(I.mem.dalloc(&ksum, C * ENV_GRAD_NKRAW));
+    DCHK(I.mem.dalloc(&g.part, C * ntiles * 2)); DCHK(I.mem.dalloc(&g.gpart, C * ntiles * (size_t)env_grad_nraw(in.model_id)));
+    if (kal) { DCHK(I.mem.dalloc(&g.ksi_part, C * nchunk * 3)); DCHK(I.mem.dalloc(&g.ksi_gpart, C * nchunk * (ENV_GRAD_NKRAW - 3))); }
+    DCHK(hipMemsetAsync(ksum, 0, C * ENV_GRAD_NKRAW * sizeof(double), c->stream));  // (id 1 never writes them)
+    g.gsum = gsum; g.ksum = ksum;
+    k.h = envb.h; k.gsum = gsum; k.ksum = ksum; k.hx = c->hx[1] - c->hx[0];
     return TAMCMC_OK;
 }
 
@@ -407,6 +424,20 @@ int DevSampler::download_envelope_rows(double *rows, double *params, double *log
     return TAMCMC_OK;
 }
 
+int DevSampler::download_envelope_sums(double *S, double *tile_sums, double *xi_sums) {
+    Impl &I = *impl;
+    tamcmc_hip_ctx *c = I.ctx;
+    if (!I.env.on || !I.lan.use_drift) return TAMCMC_ERR_BAD_MODEL;
+    if (!I.last.scheme) return TAMCMC_ERR_BAD_ARG;  // (no iteration yet: no batch)
+    if (int rc = I.ready_to_read()) return rc;
+    const size_t C = (size_t)I.a.C;
+    const EnvGradBuffers &g = I.lan.envb.g;
+    if (S) DCHK(hipMemcpy(S, g.S, C * 8, hipMemcpyDeviceToHost));
+    if (tile_sums) DCHK(hipMemcpy(tile_sums, g.gsum, C * ENV_GRAD_NRAWMAX * 8, hipMemcpyDeviceToHost));
+    if (xi_sums) DCHK(hipMemcpy(xi_sums, g.ksum, C * ENV_GRAD_NKRAW * 8, hipMemcpyDeviceToHost));
+    return TAMCMC_OK;
+}
+
 void DevSampler::info(long out[18]) const {
     const Impl &I = *impl;
     unsigned long long qc[3] = {0, 0, 0};  // (every entry point returns with the sampler's streams idle)
@@ -417,7 +448,7 @@ void DevSampler::info(long out[18]) const {
     out[8] = I.n.n_stretch; out[9] = (long)qc[0]; out[10] = (long)qc[1]; out[13] = (long)qc[2];
     out[0] = I.a.Nv; out[1] = I.a.desc.Np;
     out[2] = I.lan.use_drift ? I.lan.chol_lds : I.a.chol_in_lds;
-    out[3] = I.env.on ? (I.a.desc.Nx <= env_step_max_bins(I.model_id) ? 1 : 0) : (I.fu.ok && !I.lan.use_drift) ? 1 : 0;  // (ids 0 / 1: k_env_step)
+    out[3] = I.lan.use_drift ? 0 : I.env.on ? (I.a.desc.Nx <= env_step_max_bins(I.model_id) ? 1 : 0) : I.fu.ok ? 1 : 0;  // (ids 0 / 1: k_env_step)
     out[4] = I.grp.G; out[5] = I.n.it_fused; out[6] = I.n.it_lockstep; out[7] = I.a.C;
     out[11] = I.n.it_joint; out[12] = I.n.it_window;
 }

@@ -614,14 +614,20 @@ struct DevSampler::Impl::RunCall {
     // the kernels' arguments, the record buffers, where the adaptation works
     int prepare_langevin() {
         const size_t C = (size_t)a.C, Nv = (size_t)a.Nv, Np = (size_t)a.desc.Np;
-        FdBatch &fd = V.fd;
-        db = V.block.p;
-        fd.count_slots = c->timing && fd.hybrid();  // (hybrid red-giant batches: linearised / fallback slots of this call, counted on the device)
-        if (fd.count_slots) DCHK(fd.zero_slot_counts(c, db));
         M = V.mala;
-        const FdResults res = fd.head.results(db);  // (the device block: read by k_mala_test)
-        M.S = V.S.p; M.lpp = res.lpp; M.lpm = res.lpm; M.st = res.status;
-        M.h = fd.head.hstep(db); M.E = fd.E; M.deltas = fd.deltas() ? 1 : 0; M.fd_step_rel = V.fd_step_rel; M.delta = V.delta;
+        M.fd_step_rel = V.fd_step_rel; M.delta = V.delta;
+        if (I.env.on) {  // ids 0 / 1: the analytic batch's results, in the sampler's own buffers
+            M.S = V.envb.g.S; M.lpp = V.envb.k.lpp; M.lpm = V.envb.k.lpm; M.st = nullptr; M.dlogL = V.envb.k.dlogL;
+            M.h = V.envb.h; M.E = a.Nv + 1; M.deltas = 0;
+        } else {
+            FdBatch &fd = V.fd;
+            db = V.block.p;
+            fd.count_slots = c->timing && fd.hybrid();  // (hybrid red-giant batches: linearised / fallback slots of this call, counted on the device)
+            if (fd.count_slots) DCHK(fd.zero_slot_counts(c, db));
+            const FdResults res = fd.head.results(db);  // (the device block: read by k_mala_test)
+            M.S = V.S.p; M.lpp = res.lpp; M.lpm = res.lpm; M.st = res.status; M.dlogL = nullptr;
+            M.h = fd.head.hstep(db); M.E = fd.E; M.deltas = fd.deltas() ? 1 : 0;
+        }
         if (int rc = I.reserve_records(samples != nullptr, stats != nullptr, (size_t)n_iter)) return rc;
         args = a;
         if (!samples) args.samples = nullptr;
@@ -636,18 +642,37 @@ struct DevSampler::Impl::RunCall {
         I.n.it_lockstep += n_iter;
         if (!chol_lds && !I.adapt_scratch) DCHK(I.mem.dalloc(&I.adapt_scratch, C * (Nv * Nv + 3 * Nv)));
         if (lds_test0 + lds_adapt > 64 * 1024 && chol_lds)
-            DCHK(hipFuncSetAttribute((const void *)k_mala_test, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_test0 + lds_adapt)));
+            DCHK(hipFuncSetAttribute(I.env.on ? (const void *)k_mala_test<true> : (const void *)k_mala_test<false>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_test0 + lds_adapt)));
         return TAMCMC_OK;
     }
 
-    int batch(const double *d_params, hipEvent_t *pair) { return V.fd.enqueue(c, db, d_params, ws, pair ? pair[0] : nullptr, pair ? pair[1] : nullptr); }
+    // ids 0 / 1, the analytic batch at the vectors d_params [C][Np]: rows and log-priors, the bins (envelope.hip's kernels on the
+    // sampler's buffers), the chain rule; everything on the context stream, nothing leaves the device
+    int env_batch(const double *d_params, hipEvent_t *pair) {
+        const EnvMalaArgs &k = V.envb.k;
+        const int npts = a.C * (2 * a.Nv + 1);
+        if (pair) DCHK(hipEventRecord(pair[0], st));
+        hipLaunchKernelGGL(k_env_mala_front, dim3((npts + 63) / 64), dim3(64), 0, st, args, k, d_params);
+        DCHK(hipGetLastError());
+        if (int rc = envelope_grad_stage_enqueue(c, I.model_id, a.C, a.env_rows, V.envb.g, st)) return rc;
+        hipLaunchKernelGGL(k_env_mala_chain, dim3(a.C), dim3(128), 0, st, args, k, d_params);
+        DCHK(hipGetLastError());
+        if (pair) DCHK(hipEventRecord(pair[1], st));
+        return TAMCMC_OK;
+    }
+
+    int batch(const double *d_params, hipEvent_t *pair) {
+        if (I.env.on) return env_batch(d_params, pair);
+        return V.fd.enqueue(c, db, d_params, ws, pair ? pair[0] : nullptr, pair ? pair[1] : nullptr);
+    }
 
     // gradient at the chains' current positions (start of a run, new positions from outside)
     int initial_gradient() {
         if (V.grad_valid) return TAMCMC_OK;
         hipLaunchKernelGGL(k_mala_steps, dim3(1), dim3(256), 0, st, args, M);
         if (int rc = batch(a.params_cur + (size_t)P * a.C * a.desc.Np, nullptr)) return rc;
-        hipLaunchKernelGGL(k_mala_ginit, dim3(a.C), dim3(TB), 2 * (size_t)a.Nv * sizeof(double), st, args, M, P);
+        hipLaunchKernelGGL(I.env.on ? k_mala_ginit<true> : k_mala_ginit<false>, dim3(a.C), dim3(TB), 2 * (size_t)a.Nv * sizeof(double), st, args, M, P);
         DCHK(hipGetLastError());
         V.grad_valid = true;
         return TAMCMC_OK;
@@ -664,12 +689,12 @@ struct DevSampler::Impl::RunCall {
             hipEvent_t *pair = T.batch_pair(i, n_iter);
             if (int rc = batch(a.params_prop, pair)) return rc;
             const int learn_i = (learn && learn[i]) ? factor_step_mode(I.factor_refresh, I.n_adapt++) : 0;
-            hipLaunchKernelGGL(k_mala_test, dim3(a.C), dim3(TB), lds_test, st, args, M, it, P, learn_i, I.adapt_scratch);
+            hipLaunchKernelGGL(I.env.on ? k_mala_test<true> : k_mala_test<false>, dim3(a.C), dim3(TB), lds_test, st, args, M, it, P, learn_i, I.adapt_scratch);
             if (pair) {
                 DCHK(hipStreamSynchronize(st));
                 if (int rc = T.batch_sampled()) return rc;
                 long bins = 0;  // what the delta launch really touched (roofline bookkeeping, as fd_run does)
-                if (V.fd.route == FdBatch::Route::Windowed) DCHK(V.fd.delta_stats(db, &bins, nullptr));
+                if (!I.env.on && V.fd.route == FdBatch::Route::Windowed) DCHK(V.fd.delta_stats(db, &bins, nullptr));
                 T.batch_bins(bins);
             }
         }
@@ -682,6 +707,10 @@ struct DevSampler::Impl::RunCall {
         DCHK(copy_records(samples, stats, a, (size_t)n_iter, st));
         DCHK(hipStreamSynchronize(st));
         long lin = 0, fall = 0;
+        if (I.env.on) {  // (one pass over the bins per chain: C evaluations a batch)
+            T.total_batches(n_iter, (long)a.C, false, 0, 0);
+            return TAMCMC_OK;
+        }
         if (V.fd.count_slots) DCHK(V.fd.hybrid_stats(c, db, &lin, &fall));
         T.total_batches(n_iter, (long)V.fd.B, V.fd.route == FdBatch::Route::Windowed, lin, fall);
         return TAMCMC_OK;
@@ -692,7 +721,12 @@ struct DevSampler::Impl::RunCall {
         // Red giants under STRICT: the batch would need the host's long-double unpack of every proposal (FdBatch::h_prep), and the proposals
         // exist on the device only.  Refused here, before anything is enqueued or counted: state, iteration and gradients stay as they are
         if (I.rgb && c->precision == TAMCMC_PRECISION_STRICT) return TAMCMC_ERR_BAD_ARG;
-        if (int rc = layout_batch()) return rc;
+        // ids 0 / 1: one gradient route, the analytic one, with buffers laid out at creation; no mode table, so no table-space adjoint --
+        // refused like any route a model has not, with the chains where they were
+        if (I.env.on) {
+            if (c->gradient == TAMCMC_GRADIENT_ADJOINT) return TAMCMC_ERR_BAD_MODEL;
+            I.last.set(1, 0);  // (download_envelope_rows: the Langevin step keeps its proposals in the first half of params_prop)
+        } else if (int rc = layout_batch()) return rc;
         if (int rc = prepare_langevin()) return rc;
         if (int rc = initial_gradient()) return rc;
         if (int rc = langevin_loop()) return rc;

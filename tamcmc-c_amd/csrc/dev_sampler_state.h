@@ -110,6 +110,13 @@ struct DevSampler::Impl {
         DevBuf<double> part, S, model, bg;
         FdBatch::Buffers ws() { return FdBatch::Buffers{part, S, model, bg}; }
         MalaArgs mala{};
+        // ids 0 / 1 (TAMCMC_OPT_ENVELOPE_DEVICE_LANGEVIN): no FdBatch; the analytic batch's buffers, the sampler's own (in Impl::mem) and
+        // indexed by chain, sized once at creation (the spectrum's length is the engine's constant a.desc.Nx)
+        struct EnvBatch {
+            EnvMalaArgs k{};     // what k_env_mala_front and k_env_mala_chain read and write
+            EnvGradBuffers g;    // what envelope.hip's kernels write between them
+            double *h = nullptr; // [Nv] the steps
+        } envb;
         bool grad_valid = false;  // a.grad_cur holds the gradient at the chains' positions (upload_state and a new batch layout invalidate)
         int chol_lds = -1;
         std::vector<double> h_priors, h_extra;  // host copies of the constants the batch's head is staged from

@@ -28,6 +28,16 @@ int envelope_enqueue(tamcmc_hip_ctx *c, int model_id, int B, const double *param
 // 2) point at the FIRST of these chains' entries: every buffer is indexed by chain, so chain groups on different streams share no slot.
 int envelope_stage_enqueue(tamcmc_hip_ctx *c, int model_id, int cnt, const void *rows_dev, double *ksi_part, double *partials, hipStream_t st);
 
+// The device-resident Langevin step's door (dev_sampler.hip; TAMCMC_OPT_ENVELOPE_DEVICE_LANGEVIN): the analytic gradient's kernels --
+// k_env_ksi_grad (id 0), k_env_grad, k_env_grad_fold, the launches the gradient entries make -- for `cnt` chains whose rows
+// k_env_mala_front has left on the device, enqueued on `st`.  Every buffer is the caller's and indexed by chain:
+struct EnvGradBuffers {
+    double *ksi_part = nullptr, *ksi_gpart = nullptr;  // id 0: chunk partials, cnt x chunks x 3 and x 9
+    double *part = nullptr, *gpart = nullptr;          // tile partials, cnt x tiles x 2 and x (16 | 10)
+    double *S = nullptr, *gsum = nullptr, *ksum = nullptr;  // folded: S [cnt] (the evaluation's bits), tile sums cnt x 16, xi sums cnt x 12
+};
+int envelope_grad_stage_enqueue(tamcmc_hip_ctx *c, int model_id, int cnt, const void *rows_dev, const EnvGradBuffers &b, hipStream_t st);
+
 // tamcmc_hip_loglike_params_batch for ids 0 and 1
 int envelope_loglike_params_batch(tamcmc_hip_ctx *c, int model_id, int B, const double *params, int64_t Nparams, const double *Tcoefs,
                                   double p, double *logL, double *model, int32_t *status);

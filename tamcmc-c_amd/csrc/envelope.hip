@@ -17,7 +17,8 @@
 // Who owns what.  envelope_row.h: the row builder, the xi term, the bodies of the two passes (the model of a bin, twice); the
 // device-resident sampler's one-launch step (k_env_step, dev_env_step_impl.h) evaluates its tiles through the same bodies.  This file:
 // the kernels around those bodies, and on the host ONE staging of rows (env_stage_rows), ONE statement of the evaluation's launches
-// (env_launch_eval: the batch and the sampler's lockstep route both call it), ONE gradient run for the brute-force and the analytic
+// (env_launch_eval: the batch and the sampler's lockstep route both call it), ONE statement of the analytic gradient's launches
+// (env_launch_grad: the gradient entries and the device-resident Langevin step both call it), ONE gradient run for the brute-force and the analytic
 // likelihood share (envelope_gradient_run) behind ONE front door for the two gradient entries (envelope_gradient).  The tempered
 // log-likelihood and the gradient's assembly are grad_assemble.h's, the timing totals ctx.h's (account_kernel_time).
 //
@@ -206,6 +207,27 @@ int env_launch_eval(tamcmc_hip_ctx *c, int model_id, int cnt, const EnvRow *rows
     return TAMCMC_OK;
 }
 
+// THE launches of the analytic gradient for `cnt` rows: k_env_ksi_grad (id 0), k_env_grad, k_env_grad_fold.  The gradient entries
+// (envelope_grad_enqueue, the context's buffers) and the device-resident Langevin step (envelope_grad_stage_enqueue, the sampler's)
+// both call it: the same statements in the same orders, so S[b] has the evaluation's bits on either
+int env_launch_grad(tamcmc_hip_ctx *c, int model_id, int cnt, const EnvRow *rows, const EnvGradBuffers &b, hipStream_t st) {
+    const EnvGeom g(c);
+    const dim3 grid(g.ntiles, cnt);
+    if (model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN) {
+        hipLaunchKernelGGL(k_env_ksi_grad, dim3(g.nchunk, cnt), dim3(EWG), 0, st, c->dlogx.p, g.Nx, g.nchunk, rows, b.ksi_part, b.ksi_gpart);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL((k_env_grad<0>), grid, dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, g.Nx, g.ntiles, g.nchunk, g.h, c->xmax, rows, b.ksi_part, b.part, b.gpart);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL((k_env_grad_fold<ENV_GRAD_NRAW0>), dim3(cnt), dim3(EWG), 0, st, b.part, b.gpart, g.ntiles, b.ksi_part, b.ksi_gpart, g.nchunk, b.S, b.gsum, b.ksum);
+    } else {
+        hipLaunchKernelGGL((k_env_grad<1>), grid, dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, g.Nx, g.ntiles, g.nchunk, g.h, c->xmax, rows, nullptr, b.part, b.gpart);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL((k_env_grad_fold<ENV_GRAD_NRAW1>), dim3(cnt), dim3(EWG), 0, st, b.part, b.gpart, g.ntiles, nullptr, nullptr, 0, b.S, b.gsum, b.ksum);
+    }
+    HIPCHK(c, hipGetLastError());
+    return TAMCMC_OK;
+}
+
 // the copy of n sums (d_S) behind the kernels
 int env_fetch_sums(tamcmc_hip_ctx *c, const double *dev, size_t n) {
     HIPCHK(c, c->h_S.reserve(n));
@@ -236,6 +258,11 @@ int envelope_enqueue(tamcmc_hip_ctx *c, int model_id, int B, const double *param
 // The sampler's lockstep route: the rows are on the device already (written by k_iterate), one per chain
 int envelope_stage_enqueue(tamcmc_hip_ctx *c, int model_id, int cnt, const void *rows_dev, double *ksi_part, double *partials, hipStream_t st) {
     return env_launch_eval(c, model_id, cnt, (const EnvRow *)rows_dev, ksi_part, nullptr, partials, st, false);
+}
+
+// The device-resident Langevin step: the analytic gradient's kernels on the rows k_env_mala_front has left on the device
+int envelope_grad_stage_enqueue(tamcmc_hip_ctx *c, int model_id, int cnt, const void *rows_dev, const EnvGradBuffers &b, hipStream_t st) {
+    return env_launch_grad(c, model_id, cnt, (const EnvRow *)rows_dev, b, st);
 }
 
 int envelope_loglike_params_batch(tamcmc_hip_ctx *c, int model_id, int B, const double *params, int64_t Nparams, const double *Tcoefs,
@@ -320,22 +347,15 @@ static int envelope_grad_enqueue(tamcmc_hip_ctx *c, int model_id, int C, const d
                  total = o_chunk + (kal ? (size_t)C * g.nchunk * (ENV_GRAD_NKRAW - 3) : 0);
     if (int rc = env_stage_rows(c, model_id, C, g.ntiles, params, Nparams, c->d_envg, total)) return rc;
     hipStream_t st = c->stream;
-    const EnvRow *rows = staged_rows_dev(c);
-    double *Sdev = c->d_envg.p, *gsum = Sdev + C, *ksum = gsum + (size_t)C * ENV_GRAD_NRAWMAX, *gtile = c->d_envg.p + o_tile, *gchunk = c->d_envg.p + o_chunk;
+    EnvGradBuffers b;
+    b.S = c->d_envg.p; b.gsum = b.S + C; b.ksum = b.gsum + (size_t)C * ENV_GRAD_NRAWMAX;
+    b.gpart = c->d_envg.p + o_tile; b.ksi_gpart = c->d_envg.p + o_chunk;
+    b.part = c->d_part.p;
+    if (kal) HIPCHK(c, c->d_env.reserve((size_t)C * g.nchunk * 3));
+    b.ksi_part = c->d_env.p;
+    double *Sdev = b.S;
     if (c->timing) HIPCHK(c, hipEventRecord(c->ev0, st));
-    const dim3 grid(g.ntiles, C);
-    if (kal) {
-        HIPCHK(c, c->d_env.reserve((size_t)C * g.nchunk * 3));
-        hipLaunchKernelGGL(k_env_ksi_grad, dim3(g.nchunk, C), dim3(EWG), 0, st, c->dlogx.p, g.Nx, g.nchunk, rows, c->d_env.p, gchunk);
-        HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL((k_env_grad<0>), grid, dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, g.Nx, g.ntiles, g.nchunk, g.h, c->xmax, rows, c->d_env.p, c->d_part.p, gtile);
-    } else {
-        hipLaunchKernelGGL((k_env_grad<1>), grid, dim3(EWG), 0, st, c->dx.p, c->dy.p, c->dlogx.p, g.Nx, g.ntiles, g.nchunk, g.h, c->xmax, rows, nullptr, c->d_part.p, gtile);
-    }
-    HIPCHK(c, hipGetLastError());
-    if (kal) hipLaunchKernelGGL((k_env_grad_fold<ENV_GRAD_NRAW0>), dim3(C), dim3(EWG), 0, st, c->d_part.p, gtile, g.ntiles, c->d_env.p, gchunk, g.nchunk, Sdev, gsum, ksum);
-    else hipLaunchKernelGGL((k_env_grad_fold<ENV_GRAD_NRAW1>), dim3(C), dim3(EWG), 0, st, c->d_part.p, gtile, g.ntiles, nullptr, nullptr, 0, Sdev, gsum, ksum);
-    HIPCHK(c, hipGetLastError());
+    if (int rc = env_launch_grad(c, model_id, C, staged_rows_dev(c), b, st)) return rc;
     if (c->timing) HIPCHK(c, hipEventRecord(c->ev1, st));
     return env_fetch_sums(c, Sdev, (size_t)C * (1 + ENV_GRAD_NRAWMAX + ENV_GRAD_NKRAW));
 }
@@ -379,12 +399,7 @@ static std::vector<double> envelope_chain_rule(int model_id, int C, const double
         env_row_jacobian(model_id, params + (size_t)ch * Nparams, J.data());
         for (int k = 0; k < Nvars; k++) {
             const int j = index_to_relax[k];
-            long double s = 0.0L;  // dS/dtheta_j = sum_q dS/drow_q J[q][j]
-            if (j < NpJ)
-                for (int q = 0; q < ENV_GRAD_N; q++) {
-                    const long double Jq = J[(size_t)q * NpJ + j];
-                    if (Jq != 0.0L) s += dS[(size_t)ch * ENV_GRAD_N + q] * Jq;  // (a parameter the model does not read: exactly 0)
-                }
+            const long double s = env_chain_contract(dS.data() + (size_t)ch * ENV_GRAD_N, J.data(), NpJ, j);  // (a parameter the model does not read: exactly 0)
             gL[(size_t)ch * Nvars + k] = s == 0.0L ? 0.0 : tempered_loglike(s, p, temperature_of(Tcoefs, ch));  // (+0, not -p * 0)
         }
     }

@@ -114,77 +114,94 @@ TAMCMC_ENV_HD int env_grad_nraw(int model_id) { return model_id == TAMCMC_MODEL_
 // Folded sums of one vector -> dS / d(row quantity), in the order of tamcmc_hip_envelope_gradient_sums:
 //   id 1  [A, nu, sigma^2, N0, H_0, H_1, lna_0, lna_1, pw_0, pw_1, 0, 0, 0]
 //   id 0  [A, nu (the Gaussian's), sigma^2, N0, a_k^2 (3), ln b_k (3), c_k (3)]
-// and (id 0) the xi sums [I_k, I_k^b = c_k sum w D_k, I_k^c = -sum w D_k u_k] into ksi[9].  h: the trapezoid step x(1) - x(0).
-inline void env_grad_rows(int model_id, const EnvRow &R, double h, const double *raw, const double *kraw, long double *out, long double *ksi) {
-    for (int q = 0; q < ENV_GRAD_N; q++) out[q] = 0.0L;
-    const long double A = R.amp, s2 = R.sig2;
+// and (id 0) the xi sums [I_k, I_k^b = c_k sum w D_k, I_k^c = -sum w D_k u_k] into ksi[9] (may be null).  h: the trapezoid step
+// x(1) - x(0).  ONE text for the two arithmetics the chain rule runs in (as env_row is one text for host and device): T = long double
+// on the host (the gradient entries, envelope.hip), T = double on the device (k_env_mala_chain, dev_mala_impl.h).
+template <class T>
+TAMCMC_ENV_HD void env_grad_rows(int model_id, const EnvRow &R, double h, const double *raw, const double *kraw, T *out, T *ksi) {
+    for (int q = 0; q < ENV_GRAD_N; q++) out[q] = T(0);
+    const T A = R.amp, s2 = R.sig2;
     out[0] = raw[0];
-    out[1] = A * (long double)raw[1] / s2;
-    out[2] = A * (long double)raw[2] / (2.0L * s2 * s2);
+    out[1] = A * (T)raw[1] / s2;
+    out[2] = A * (T)raw[2] / (T(2) * s2 * s2);
     out[3] = raw[3];
     if (model_id == TAMCMC_MODEL_HARVEY_GAUSSIAN) {
         for (int q = 0; q < 2; q++) {
             if (!R.hon[q]) continue;  // a switched-off term: 0 in its three places
             out[4 + q] = raw[4 + q];
-            out[6 + q] = -(long double)R.H[q] * (long double)R.pw[q] * (long double)raw[6 + q];
-            out[8 + q] = -(long double)R.H[q] * (long double)raw[8 + q];
+            out[6 + q] = -(T)R.H[q] * (T)R.pw[q] * (T)raw[6 + q];
+            out[8 + q] = -(T)R.H[q] * (T)raw[8 + q];
         }
         return;
     }
     for (int k = 0; k < 3; k++) {
-        const long double I = kraw[k], Ib = (long double)R.c[k] * (long double)kraw[3 + k], Ic = -(long double)kraw[6 + k];
-        const long double hI = (long double)h * I, Ck = (long double)R.a2[k] / hI;
-        const long double rL = raw[4 + k], rD = raw[7 + k], rDu = raw[10 + k], rL2 = raw[13 + k];
-        const long double Kbar = (long double)kraw[3 + k] / I, Lbar = (long double)kraw[9 + k] / I;  // (Kbar + Lbar = 1)
+        const T I = kraw[k], Ib = (T)R.c[k] * (T)kraw[3 + k], Ic = -(T)kraw[6 + k];
+        const T hI = (T)h * I, Ck = (T)R.a2[k] / hI;
+        const T rL = raw[4 + k], rD = raw[7 + k], rDu = raw[10 + k], rL2 = raw[13 + k];
+        const T Kbar = (T)kraw[3 + k] / I, Lbar = (T)kraw[9 + k] / I;  // (Kbar + Lbar = 1)
         out[4 + k] = rL / hI;
         // the normalisation integral moves with b_k: c D - L I^b / I in whichever of its two forms keeps its digits ...
-        out[7 + k] = Ck * (long double)R.c[k] * (Lbar <= 0.5L ? rL * Lbar - rL2 : rD - rL * Kbar);
+        out[7 + k] = Ck * (T)R.c[k] * (Lbar <= T(0.5) ? rL * Lbar - rL2 : rD - rL * Kbar);
         out[10 + k] = Ck * (-rDu - rL * Ic / I);                      // ... and with c_k
         if (ksi) { ksi[k] = I; ksi[3 + k] = Ib; ksi[6 + k] = Ic; }
     }
 }
 
 // d(row quantity) / d(parameter): J[q * Np + j], q in the order of env_grad_rows, j < Np = 10 (id 1) or 19 (id 0).  d|p|/dp =
-// copysign(1, p); d ln(1e-3 |tc|)/dtc = 1/tc (not finite at tc = 0, where the model is not continuous).  Long double.
-inline void env_row_jacobian(int model_id, const double *p, long double *J) {
+// copysign(1, p); d ln(1e-3 |tc|)/dtc = 1/tc (not finite at tc = 0, where the model is not continuous).  T as for env_grad_rows.
+template <class T>
+TAMCMC_ENV_HD void env_row_jacobian(int model_id, const double *p, T *J) {
     const int Np = model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN ? 19 : 10;
-    for (int i = 0; i < ENV_GRAD_N * Np; i++) J[i] = 0.0L;
-    auto sgn = [](double v) { return (long double)std::copysign(1.0, v); };
-    auto at = [&](int q, int j) -> long double & { return J[q * Np + j]; };
+    for (int i = 0; i < ENV_GRAD_N * Np; i++) J[i] = T(0);
+    auto sgn = [](double v) { return (T)std::copysign(1.0, v); };
+    auto at = [&](int q, int j) -> T & { return J[q * Np + j]; };
     if (model_id == TAMCMC_MODEL_HARVEY_GAUSSIAN) {
         at(0, 7) = sgn(p[7]);
-        at(1, 8) = 1.0L;
-        at(2, 9) = 2.0L * (long double)p[9];
+        at(1, 8) = T(1);
+        at(2, 9) = T(2) * (T)p[9];
         at(3, 6) = sgn(p[6]);
         for (int q = 0; q < 2; q++) {
             at(4 + q, 3 * q) = sgn(p[3 * q]);
-            at(6 + q, 3 * q + 1) = 1.0L / (long double)p[3 * q + 1];
+            at(6 + q, 3 * q + 1) = T(1) / (T)p[3 * q + 1];
             at(8 + q, 3 * q + 2) = sgn(p[3 * q + 2]);
         }
         return;
     }
-    const long double s15 = sgn(p[15]), nu = std::fabs((long double)p[15]), mu = p[17], nm = nu + mu, lnm = std::log(std::fabs(nm));
+    const T s15 = sgn(p[15]), nu = std::fabs((T)p[15]), mu = p[17], nm = nu + mu, lnm = std::log(std::fabs(nm));
     at(0, 14) = sgn(p[14]);
     at(1, 15) = s15;
-    at(2, 16) = 2.0L * (long double)p[16];
+    at(2, 16) = T(2) * (T)p[16];
     at(3, 13) = sgn(p[13]);
     // a_0^2 = (p0 nu^p1)^2
-    const long double p0 = p[0], p1 = p[1], nup = std::pow(nu, 2.0L * p1), a02 = p0 * p0 * nup;
-    at(4, 0) = 2.0L * p0 * nup;
-    at(4, 1) = a02 * 2.0L * std::log(nu);
-    at(4, 15) = a02 * 2.0L * p1 / nu * s15;
-    at(5, 5) = 2.0L * (long double)p[5];
-    at(6, 6) = 2.0L * (long double)p[6];
+    const T p0 = p[0], p1 = p[1], nup = std::pow(nu, T(2) * p1), a02 = p0 * p0 * nup;
+    at(4, 0) = T(2) * p0 * nup;
+    at(4, 1) = a02 * T(2) * std::log(nu);
+    at(4, 15) = a02 * T(2) * p1 / nu * s15;
+    at(5, 5) = T(2) * (T)p[5];
+    at(6, 6) = T(2) * (T)p[6];
     // ln b_k = ln|p_i| + p_j ln|nu + mu|
-    static const int bi[3] = {2, 7, 10}, bj[3] = {3, 8, 11}, ci[3] = {4, 9, 12};
     for (int k = 0; k < 3; k++) {
-        const long double pj = p[bj[k]];
-        at(7 + k, bi[k]) = 1.0L / (long double)p[bi[k]];
-        at(7 + k, bj[k]) = lnm;
+        const int bi = k == 0 ? 2 : k == 1 ? 7 : 10, bj = bi + 1, ci = bi + 2;
+        const T pj = p[bj];
+        at(7 + k, bi) = T(1) / (T)p[bi];
+        at(7 + k, bj) = lnm;
         at(7 + k, 15) = pj / nm * s15;
         at(7 + k, 17) = pj / nm;
-        at(10 + k, ci[k]) = sgn(p[ci[k]]);
+        at(10 + k, ci) = sgn(p[ci]);
     }
+}
+
+// dS / dtheta_j = sum_q dS/d(row quantity q) J[q][j], q ascending; a zero of the Jacobian adds nothing, so a parameter the model does
+// not read (j >= NpJ, or a column of zeros) gives exactly +0.  T as for env_grad_rows.
+template <class T>
+TAMCMC_ENV_HD T env_chain_contract(const T *dS, const T *J, int NpJ, int j) {
+    T s = T(0);
+    if (j < NpJ)
+        for (int q = 0; q < ENV_GRAD_N; q++) {
+            const T Jq = J[q * NpJ + j];
+            if (Jq != T(0)) s += dS[q] * Jq;
+        }
+    return s;
 }
 
 #if defined(__HIPCC__)

@@ -19,6 +19,7 @@ extern "C" {
 void tamcmc_hip_ctx_attach(tamcmc_hip_ctx *c);  // capi.hip (private)
 void tamcmc_hip_ctx_detach(tamcmc_hip_ctx *c);
 int tamcmc_hip_envelope_device_engine(const tamcmc_hip_ctx *c);  // the context's TAMCMC_OPT_ENVELOPE_DEVICE_ENGINE
+int tamcmc_hip_envelope_device_langevin(const tamcmc_hip_ctx *c);  // the context's TAMCMC_OPT_ENVELOPE_DEVICE_LANGEVIN
 int tamcmc_hip_factor_refresh(const tamcmc_hip_ctx *c);          // the context's TAMCMC_OPT_FACTOR_REFRESH
 }
 
@@ -71,10 +72,11 @@ int tamcmc_sampler_create(tamcmc_sampler **out, tamcmc_hip_ctx *ctx, const tamcm
     if (!out || !ctx || !c || !c->inputs || !c->relax || !c->plength || !c->priors || !c->priors_switch) return TAMCMC_ERR_BAD_ARG;
     if (c->Nchains < 1 || c->Nparams < 1) return TAMCMC_ERR_BAD_ARG;
     *out = nullptr;
-    // Gaussian-envelope fits (ids 0, 1) on the device-resident engine: opt-in and random walk only (TAMCMC_OPT_ENVELOPE_DEVICE_ENGINE, read at
-    // this moment); refused before anything is built
+    // Gaussian-envelope fits (ids 0, 1) on the device-resident engine: opt-in, one option per step, both read at this moment --
+    // TAMCMC_OPT_ENVELOPE_DEVICE_ENGINE admits the random walk, TAMCMC_OPT_ENVELOPE_DEVICE_LANGEVIN the Langevin step, neither implies
+    // the other; refused before anything is built
     if ((c->model_id == TAMCMC_MODEL_KALLINGER2014_GAUSSIAN || c->model_id == TAMCMC_MODEL_HARVEY_GAUSSIAN) && c->engine == 1 &&
-        (c->use_drift || !tamcmc_hip_envelope_device_engine(ctx)))
+        !(c->use_drift ? tamcmc_hip_envelope_device_langevin(ctx) : tamcmc_hip_envelope_device_engine(ctx)))
         return TAMCMC_ERR_BAD_MODEL;
     auto s = std::make_unique<tamcmc_sampler>();
     Config &g = s->cfg;
@@ -355,6 +357,12 @@ int tamcmc_sampler_get_envelope_rows(const tamcmc_sampler *s, double *rows, doub
     if (!s) return TAMCMC_ERR_BAD_ARG;
     if (!s->dev) return TAMCMC_ERR_BAD_MODEL;
     return s->dev->download_envelope_rows(rows, params, logprior, status);
+}
+
+int tamcmc_sampler_get_envelope_gradient_sums(const tamcmc_sampler *s, double *S, double *tile_sums, double *xi_sums) {
+    if (!s) return TAMCMC_ERR_BAD_ARG;
+    if (!s->dev) return TAMCMC_ERR_BAD_MODEL;
+    return s->dev->download_envelope_sums(S, tile_sums, xi_sums);
 }
 
 int tamcmc_sampler_get_move_counts(const tamcmc_sampler *s, int64_t *moves) {

@@ -28,6 +28,7 @@ EXTRA_ABI += [
     ("tamcmc_sampler_get_move_counts", C.c_int, [_vp, _i64p]),
     ("tamcmc_sampler_get_tables", C.c_int, [_vp, _ip, _vp, _ip, _dp, _ip, _ip, _ip, _ip, _dp, _dp]),
     ("tamcmc_sampler_get_envelope_rows", C.c_int, [_vp, _dp, _dp, _dp, _ip]),
+    ("tamcmc_sampler_get_envelope_gradient_sums", C.c_int, [_vp, _dp, _dp, _dp]),
     ("tamcmc_sampler_get_gradient", C.c_int, [_vp, _dp, _dp, _ip]),
     ("tamcmc_sampler_get_last_test", C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     ("tamcmc_outputs_write_acceptance", C.c_int, [C.c_char_p, C.c_double, _dp, C.c_int32, C.c_int32]),
@@ -218,6 +219,16 @@ class Sampler:
         if rc != OK:
             raise TamcmcError(rc, "tamcmc_sampler_get_envelope_rows")
         return {"rows": rows, "params": par, "logprior": lp, "status": st}
+
+    def envelope_gradient_sums(self):
+        """tamcmc_sampler_get_envelope_gradient_sums (device engine, Langevin step, model ids 0 / 1): (S [Nchains], tile sums [Nchains x 16],
+        xi sums [Nchains x 12]) the analytic gradient's kernels folded for the last iteration's proposals."""
+        nc = self.nchains
+        S, tile, xi = np.zeros(nc), np.zeros((nc, 16)), np.zeros((nc, 12))
+        rc = self._L.tamcmc_sampler_get_envelope_gradient_sums(self._h, _p(S), _p(tile), _p(xi))
+        if rc != OK:
+            raise TamcmcError(rc, "tamcmc_sampler_get_envelope_gradient_sums")
+        return S, tile, xi
 
     def move_counts(self):
         """Per chain: iterations since creation whose record carries moved = 1 (tamcmc_sampler_get_move_counts)."""
