@@ -512,6 +512,54 @@ int tamcmc_hip_get_rgb_adjoint_stats(tamcmc_hip_ctx *ctx, int64_t *linearised_sl
  * noise pass + folds, fallback delta launches (moments, far-only tiles, DELTA launch, its fold), contraction (milliseconds). */
 int tamcmc_hip_get_rgb_adjoint_times(tamcmc_hip_ctx *ctx, double *ms6);
 
+/* ---------------- posterior model spectrum ---------------- */
+/* Per-bin statistics of the model M over a stream of parameter vectors (posterior draws), reduced over the SAMPLES axis on the device
+ * (csrc/model_stats.hip): the mean model and its variance, the envelope, the posterior mean of y/M -- the residual checked against
+ * chi^2 with 2 d.o.f. -- and the mean background.  It stands in for the models Diagnostics::gnuplt_model_diags (phases `buffer` and
+ * `final`) and get_models of the reference evaluate one by one on the host (diagnostics.cpp); the plots themselves are not made here.
+ * Seven planes of Nx doubles stay on the device; nothing proportional to (vectors x Nx) is stored or copied.
+ *
+ * The law.  A vector is ACCEPTED when its table status is TAMCMC_OK and its weight is > 0; the others are skipped and counted.  M is
+ * evaluated with the STRICT per-bin operation order -- the windowed Lorentzian multiplets in table order, then harvey_like: the bits
+ * tamcmc_hip_loglike_params_batch(model = ...) writes on a STRICT context -- whatever TAMCMC_OPT_PRECISION says.  Per bin i, over the
+ * accepted vectors b in arrival order, every operation rounded on its own (no fused multiply-add):
+ *     R_i  = M of the first accepted vector ever added (a reference plane, stored once)
+ *     d    = M_b,i - R_i
+ *     A1  += w_b d              A2 += w_b (d d)
+ *     mn   = M < mn ? M : mn    mx  = M > mx ? M : mx          (from +inf / -inf)
+ *     Q   += w_b (y_i / M)                                     (IEEE division)
+ *     G   += w_b Bg_b,i         Bg = the Harvey terms in order, then the white noise: M before the modes are added
+ *     W   += w_b                                               (a scalar on the host, same order)
+ * and  mean = R + A1 / W,  var = max(0, (A2 - (A1 A1) / W) / W),  ratio = Q / W,  background = G / W,  min = mn,  max = mx.
+ * The shift by R keeps the variance meaningful when the posterior spread is 1e-6 of the model: the mean lies within
+ * (n + 2) 2^-53 max|M| and the variance within 8 (n + 2) 2^-53 (sigma^2 + sigma max|d|) of their exact values over n vectors
+ * (tests/test_model_stats_reference.py, against 50-digit arithmetic; the unshifted sums fail that at a spread of 1e-12).
+ * A non-finite M propagates into mean, var and ratio of the bins it touches, like a non-finite model into logL; min and max ignore a NaN.
+ * The result of a bin depends on the sequence of accepted vectors alone: not on the chunk size, on how the vectors are split over
+ * calls, on TAMCMC_OPT_WORKGROUP / _BINS_PER_THREAD / _PRECISION, nor on zero-weight or failed vectors in between.
+ *
+ * create: the handle BORROWS the context (destroy the handle first); inputs [Nparams] and relax [Nparams] (1 = free; NULL: add_params
+ *   only) serve add_vars; plength as for tamcmc_hip_loglike_params_batch; chunk = vectors per launch (0 = default 1024, <= 65535).
+ *   Models: ids 3, 11, 12, 13, 14, 23 (host table builders) and 25, 27 (device pre-step: the per-vector status stays on the device and the
+ *   kernel skips failed vectors there).  The envelope models, ids 0 and 1, have no tables and are out of scope: TAMCMC_ERR_BAD_MODEL.
+ *   No spectrum: TAMCMC_ERR_NO_SPECTRUM.  y is read at add time.
+ * add_params: n rows of Nparams doubles, row_stride doubles apart.  add_vars: n rows of the Nvars free variables, scattered into a copy of
+ *   inputs through relax; with row_stride = Nchains Nvars, chain 0 of a tamcmc_sampler_run record [n x Nchains x Nvars] is passed in
+ *   place.  weights [n] or NULL (all 1).  A negative or non-finite weight: TAMCMC_ERR_BAD_ARG, the handle unchanged.  A vector whose table
+ *   fails is skipped and counted; the call still returns TAMCMC_OK.
+ * get: W, counts = {accepted, skipped: table failed, skipped: weight 0}, and the six results, each [Nx] or NULL.  TAMCMC_ERR_BAD_ARG on a
+ *   handle with nothing accepted.  A context whose Nx is no longer the one at creation: TAMCMC_ERR_BAD_ARG from add_* and get.
+ * reset: forgets everything added (the handle is as after create). */
+typedef struct tamcmc_model_stats tamcmc_model_stats;
+int tamcmc_hip_model_stats_create(tamcmc_model_stats **ms, tamcmc_hip_ctx *ctx, int model_id, const double *inputs, int64_t Nparams,
+                                  const int32_t *relax, const int32_t *plength, int32_t chunk);
+int tamcmc_hip_model_stats_add_params(tamcmc_model_stats *ms, int64_t n, const double *params, int64_t row_stride, const double *weights);
+int tamcmc_hip_model_stats_add_vars(tamcmc_model_stats *ms, int64_t n, const double *vars, int64_t row_stride, const double *weights);
+int tamcmc_hip_model_stats_get(const tamcmc_model_stats *ms, double *W, int64_t counts[3], double *mean, double *var, double *min, double *max,
+                               double *ratio, double *background);
+int tamcmc_hip_model_stats_reset(tamcmc_model_stats *ms);
+void tamcmc_hip_model_stats_destroy(tamcmc_model_stats *ms);
+
 #ifdef __cplusplus
 }
 #endif

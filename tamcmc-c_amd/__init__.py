@@ -90,6 +90,12 @@ ABI = [
                                             _ip, _ip, _ip, C.POINTER(C.c_int)]),
     ("tamcmc_hip_get_rgb_adjoint_stats", C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("tamcmc_hip_get_rgb_adjoint_times", C.c_int, [_vp, _dp]),
+    ("tamcmc_hip_model_stats_create", C.c_int, [C.POINTER(_vp), _vp, C.c_int, _dp, C.c_int64, _ip, _ip, C.c_int32]),
+    ("tamcmc_hip_model_stats_add_params", C.c_int, [_vp, C.c_int64, _dp, C.c_int64, _dp]),
+    ("tamcmc_hip_model_stats_add_vars", C.c_int, [_vp, C.c_int64, _dp, C.c_int64, _dp]),
+    ("tamcmc_hip_model_stats_get", C.c_int, [_vp, _dp, C.POINTER(C.c_int64), _dp, _dp, _dp, _dp, _dp, _dp]),
+    ("tamcmc_hip_model_stats_reset", C.c_int, [_vp]),
+    ("tamcmc_hip_model_stats_destroy", None, [_vp]),
 ]
 
 _lib = None
@@ -169,6 +175,7 @@ class HipContext:
             raise TamcmcError(st, "tamcmc_hip_create failed (no GPU / HIP runtime?) -- there is no CPU fallback")
         self._h = h
         self._samplers = weakref.WeakSet()  # samplers borrow the context: they are destroyed first, whatever order the caller (or the GC) uses
+        self._model_stats = weakref.WeakSet()  # ModelStats handles borrow the context too
         self.Nx = 0
         self.set_option(OPT_PRECISION, precision)
         self.set_option(OPT_TIMING, 1 if timing else 0)
@@ -181,6 +188,8 @@ class HipContext:
         if getattr(self, "_h", None):
             for smp in list(getattr(self, "_samplers", ())):
                 smp.close()
+            for ms in list(getattr(self, "_model_stats", ())):
+                ms.close()
             self._L.tamcmc_hip_destroy(self._h)
             self._h = None
 
@@ -430,6 +439,95 @@ class HipContext:
 
     def reset_kernel_stats(self):
         self._chk(self._L.tamcmc_hip_reset_kernel_stats(self._h))
+
+    def model_stats(self, star_or_model_id, inputs=None, plength=None, relax=None, chunk=0):
+        """Posterior model spectrum of this context's spectrum (tamcmc_hip_model_stats_*): a ModelStats accumulator for a synth.Star /
+        inputs.Star-like object (model_id, params, plength, relax) or for a model id with inputs, plength and, for add_vars, relax."""
+        if hasattr(star_or_model_id, "model_id"):
+            s = star_or_model_id
+            return ModelStats(self, s.model_id, s.params if inputs is None else inputs, s.plength, s.relax, chunk)
+        return ModelStats(self, star_or_model_id, inputs, plength, relax, chunk)
+
+
+class ModelStats:
+    """Per-bin mean, variance, envelope, mean y/M and mean background of the model over a stream of parameter vectors, accumulated on the
+    device (include/tamcmc_hip.h, "posterior model spectrum").  Borrows its HipContext: close it before the context."""
+
+    def __init__(self, ctx, model_id, inputs, plength, relax=None, chunk=0):
+        self._ctx, self._L = ctx, ctx._L
+        inputs, plength = _f64(inputs), _i32(plength)
+        relax = _i32(relax) if relax is not None else None
+        assert relax is None or relax.size == inputs.size
+        self.Nparams = inputs.size
+        self.Nvars = int((relax == 1).sum()) if relax is not None else 0
+        h = _vp()
+        st = self._L.tamcmc_hip_model_stats_create(C.byref(h), ctx._h, int(model_id), _p(inputs), inputs.size, _p(relax, _ip), _p(plength, _ip),
+                                                  int(chunk))
+        if st != OK:
+            raise TamcmcError(st, "tamcmc_hip_model_stats_create")
+        self._h = h
+        self.Nx = ctx.Nx
+        ctx._model_stats.add(self)
+
+    def _chk(self, st):
+        if st != OK:
+            raise TamcmcError(st, self._L.tamcmc_hip_last_error(self._ctx._h).decode())
+
+    @staticmethod
+    def _weights(weights, n):
+        if weights is None:
+            return None
+        w = _f64(weights)
+        assert w.shape == (n,)
+        return w
+
+    def add_params(self, params, weights=None):
+        """params [n x Nparams] (or one vector); weights [n] or None (all 1)."""
+        params = _f64(params)
+        if params.ndim == 1:
+            params = params[None, :]
+        assert params.ndim == 2 and params.shape[1] == self.Nparams
+        w = self._weights(weights, params.shape[0])
+        self._chk(self._L.tamcmc_hip_model_stats_add_params(self._h, params.shape[0], _p(params), self.Nparams, _p(w)))
+
+    def add_vars(self, vars_, chain=0, weights=None):
+        """vars_ [n x Nvars] rows of the free variables, or a Sampler.run record [n x Nchains x Nvars] of which `chain` is taken in place."""
+        v = _f64(vars_)
+        if v.ndim == 1:
+            v = v[None, :]
+        if v.ndim == 3:
+            n, nch, nv = v.shape
+            assert 0 <= chain < nch
+            stride, first = nch * nv, v.reshape(-1)[chain * nv:]
+        else:
+            (n, nv), stride, first = v.shape, v.shape[1], v
+        assert nv == self.Nvars
+        w = self._weights(weights, n)
+        self._chk(self._L.tamcmc_hip_model_stats_add_vars(self._h, n, _p(first) if n else None, stride, _p(w)))
+
+    def result(self):
+        """dict: mean, var, min, max, ratio, background ([Nx] each), W, and counts = (accepted, failed tables, zero weights)."""
+        out = {k: np.zeros(self.Nx) for k in ("mean", "var", "min", "max", "ratio", "background")}
+        W, counts = C.c_double(0), (C.c_int64 * 3)()
+        self._chk(self._L.tamcmc_hip_model_stats_get(self._h, C.byref(W), counts, *(_p(out[k]) for k in ("mean", "var", "min", "max", "ratio",
+                                                                                                       "background"))))
+        out["W"] = W.value
+        out["counts"] = tuple(int(c) for c in counts)
+        return out
+
+    def reset(self):
+        self._chk(self._L.tamcmc_hip_model_stats_reset(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.tamcmc_hip_model_stats_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 from . import sampler  # noqa: E402,F401  (registers the tamcmc_sampler_* symbols in EXTRA_ABI)

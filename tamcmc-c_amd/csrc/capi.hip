@@ -16,6 +16,7 @@
 #include "mode_tables.h"
 #include "envelope.h"
 #include "grad_assemble.h"
+#include "model_stats.h"
 
 #include "ctx.h"
 
@@ -447,3 +448,11 @@ int tamcmc_hip_reset_kernel_stats(tamcmc_hip_ctx *c) {
 }
 
 }  // extern "C"
+
+namespace tamcmc {
+// the host table stage of tamcmc_hip_loglike_params_batch, for the model-spectrum accumulator (model_stats.hip)
+int stage_params_host(tamcmc_hip_ctx *c, int model_id, int B, const double *params, int64_t Nparams, const int32_t *plength, int32_t *status,
+                      int *per_out, int *stride_out, int *first_err) {
+    return stage_params(c, model_id, B, params, Nparams, plength, status, per_out, stride_out, first_err);
+}
+}  // namespace tamcmc

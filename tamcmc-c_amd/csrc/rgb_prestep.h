@@ -25,6 +25,8 @@ int rgb_stage_params(tamcmc_hip_ctx *c, int model_id, int B, const double *param
 int rgb_fetch_modes(tamcmc_hip_ctx *c, int B, int b, int max_modes, double *nu_m, double *zeta, int *n_out);
 // after the caller's stream synchronisation: device-side status words -> status[] / first_err
 void rgb_collect_status(tamcmc_hip_ctx *c, int B, int32_t *status, int *first_err);
+// after rgb_stage_params(B): the same B status words in DEVICE memory, for a kernel enqueued behind the pre-step on the context's stream
+const int *rgb_status_device(tamcmc_hip_ctx *c, int B);
 #if defined(__HIPCC__)
 // Device engine: the pre-step on parameter vectors already in device memory, tables written into the engine's likelihood input block
 // (all arrays indexed by chain).  status: each vector's final status (the row builder merges what the unpack left in Prep / RowIn).

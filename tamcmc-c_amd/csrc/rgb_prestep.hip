@@ -697,4 +697,13 @@ void rgb_collect_status(tamcmc_hip_ctx *c, int B, int32_t *status, int *first_er
     }
 }
 
+// After rgb_stage_params(B): where the B status words are written on the DEVICE (valid behind the pre-step's kernels on the context's stream)
+const int *rgb_status_device(tamcmc_hip_ctx *c, int B) {
+    using namespace rgb;
+    const size_t bytes_prep = ((size_t)B * sizeof(Prep) + 15) & ~(size_t)15, bytes_rows = ((size_t)B * sizeof(RowIn) + 15) & ~(size_t)15;
+    const size_t nsolbuf = (size_t)B * MAXSOL;
+    const unsigned long long *d_norm = (const unsigned long long *)((const double *)(c->d_rgb.p + bytes_prep + bytes_rows) + 3 * nsolbuf);
+    return (const int *)(d_norm + B) + B;
+}
+
 }  // namespace tamcmc
